@@ -20,9 +20,21 @@ Timed region: W untimed warmup steps, then exactly K full optimizer steps (forwa
 gradient all-reduce, fused AdamW) bracketed by barrier + synchronize; the max over ranks is
 reported.  Rank 0 prints one JSON line.
 
-Extra fields (outside the timed region):
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline figure needs: set-up,
+the warmup, the GEMM-table guard (it decides which GEMM solutions the timed steps use), the K timed
+steps, the ``--dump-outputs`` files if asked for, and the result line (``value``, ``ms_per_step``,
+…).  ``--full`` adds every further measurement and check below that takes work of its own: the
+``reference`` engine run, the parameter checksum and rank-averaged loss (``param_checksum`` /
+``final_loss_global``: null without it), and at world > 1 the bucket-plan comparison, the steps
+without all-reduce and the bare all-reduce probe.
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the last timed step computed as
+float32 ``DIR/loss.npy`` (the step's loss) and ``DIR/params.npy`` (the updated parameters in
+``model.parameters()`` order, each tensor reduced to the same seeded sample of element positions).
+Weights, batches and sample positions are seeded, so equal arguments give equal inputs.
+
+Extra fields (outside the timed region; ``--full`` where noted):
   * ``comm``: bucket plan, wire dtype, transport, RCCL version, ranks seen by the communicator,
-    and ``allreduce_exposed_ms`` = ms/step of the timed run minus ms/step of a few further
+    and (``--full``) ``allreduce_exposed_ms`` = ms/step of the timed run minus ms/step of a few further
     steps with the gradient all-reduce switched off (the part of the collective NOT hidden
     behind the backward), and ``probe_busbw_GBps`` = ring bus bandwidth of bare all-reduces of
     one default-size bucket (RCCL over xGMI at N > 1; compare 7 links × ≈153 GB/s);
@@ -43,7 +55,7 @@ Extra fields (outside the timed region):
     and the arms run / skipped (``commtune.SWEEP_BUDGET_S``) / failed. The forced channel / protocol /
     algorithm arms run only with ``PENROZ_COMM_SWEEP_ARMS=full``. The process group has an explicit timeout
     (``PENROZ_DIST_TIMEOUT``, 300 s), so a stuck rank fails the run instead of hanging it;
-  * ``vs_reference_eager_same_gpu``: the same config through the ``reference`` engine (stock
+  * ``vs_reference_eager_same_gpu`` (``--full``): the same config through the ``reference`` engine (stock
     PyTorch eager + autocast + foreach AdamW, the reference's semantics) measured in this same
     process right after with the headline's own warmup / step counts (1 GPU only; ``--ref-steps
     0`` skips it).
@@ -169,13 +181,16 @@ def parse_args(argv=None):
     ap.add_argument("--model", default="gpt2-124m", choices=list(MODELS))
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
     ap.add_argument("--ref-steps", type=int, default=-1,
-                    help="steps of the reference engine measured after the run for vs_reference_eager_same_gpu "
-                         "(1 GPU, gpt2-124m only; default -1 = the headline's --steps after its --warmup; 0 = skip)")
+                    help="with --full: steps of the reference engine measured after the run for "
+                         "vs_reference_eager_same_gpu (1 GPU, gpt2-124m only; default -1 = the headline's --steps "
+                         "after its --warmup; 0 = skip)")
     ap.add_argument("--comm-probe-iters", type=int, default=5,
-                    help="world > 1: time this many bare all-reduces of one gradient bucket after the timed "
-                         "run and report the bus bandwidth in comm (0 = skip)")
+                    help="world > 1: iterations per arm of the first-contact sweep and, with --full, this many "
+                         "bare all-reduces of one gradient bucket after the timed run, reported as bus bandwidth "
+                         "in comm (0 = skip)")
     ap.add_argument("--nocomm-steps", type=int, default=4,
-                    help="steps without the gradient all-reduce, for allreduce_exposed_ms (world > 1; 0 = skip)")
+                    help="with --full: steps without the gradient all-reduce, for allreduce_exposed_ms "
+                         "(world > 1; 0 = skip)")
     ap.add_argument("--no-comm-sweep", dest="comm_sweep", action="store_false",
                     help="world > 1: skip the first-contact all-reduce sweep (bucket size x wire x transport) "
                          "that picks the gradient transport before the timed run")
@@ -189,6 +204,14 @@ def parse_args(argv=None):
                     help="single process only: each step's batch is the concatenation of the synthetic batches "
                          "that ranks 0..N-1 of a --gpus N run would draw (with --batch B·N), so its losses and "
                          "parameters must match that N-rank data-parallel run (rehearsal check)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: the reference "
+                         "engine (vs_reference_eager_same_gpu), the parameter checksum and rank-averaged loss, "
+                         "and at world > 1 the bucket-plan check, the steps without all-reduce and the bare "
+                         "all-reduce probe (a plain run skips all of these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (its loss, and a fixed "
+                         "seeded sample of the gradients and updated parameters) as DIR/<name>.npy (float32)")
     ap.add_argument("--profile", default=None, metavar="DIR",
                     help="after the timed steps, profile 3 more under torch.profiler into DIR "
                          "(Chrome trace + per-kernel table); set PENROZ_ROCTX=1 for roctx phase ranges")
@@ -551,6 +574,29 @@ def _via_runtime(args, cfg, device, world, rank) -> dict:
             shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_SAMPLE = 8192  # elements kept per parameter tensor (all of a smaller one)
+
+
+def _dump_outputs(out_dir: str, loss, model) -> None:
+    """``--dump-outputs``: what a caller of the timed step holds after the last timed step, as
+    float32 ``.npy`` files: ``loss.npy`` (the step's return value) and ``params.npy``, the updated
+    parameters in ``model.parameters()`` order, each reduced to the same ``DUMP_SAMPLE`` seeded
+    element positions in every run and concatenated (GPT-2 124M: a few MB instead of 652 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    g = torch.Generator().manual_seed(4321)
+    parts = []
+    with torch.no_grad():
+        for p in model.parameters():
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "params.npy"), torch.cat(parts).numpy())
+
+
 def run_rank(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -603,35 +649,39 @@ def run_rank(args):
     ms = dt / args.steps * 1e3
     tok_s = world * B * T * args.steps / dt
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:  # before anything below steps the model again
+        _dump_outputs(args.dump_outputs, loss, model)
 
     comm = _comm_info(runner, world)
     comm.update(first_contact)
-    # the loss averaged over ranks (= the single-process loss of the concatenated batch) and a
-    # parameter checksum: what the multi-rank rehearsal tests compare against a --data-ranks run
-    gl = loss.detach().float().reshape(1).clone()
-    if world > 1:
-        gl = gl.to(device) if device.type == "cuda" else gl
-        dist.all_reduce(gl, op=dist.ReduceOp.SUM)
-        gl /= world
-        # every rank must have built the same gradient buckets (boundaries decide which
-        # elements each collective sums): gathered and compared, not assumed
-        red = _reducer_of(runner)
-        plan_b = [list(b) for b in red.buckets] if red is not None else None
-        plans = [None] * world
-        dist.all_gather_object(plans, plan_b)
-        if any(p_ != plan_b for p_ in plans):
-            raise SystemExit(f"bench.py: ranks built different gradient buckets: {plans}")
-        comm["bucket_plans_agree"] = world
-    global_loss = float(gl.item())
-    with torch.no_grad():
-        param_checksum = float(sum(p.detach().double().abs().sum() for p in model.parameters()))
-    if world > 1 and args.nocomm_steps > 0:  # outside the timed region
+    global_loss = param_checksum = None
+    if args.full:
+        # the loss averaged over ranks (= the single-process loss of the concatenated batch) and a
+        # parameter checksum: what the multi-rank rehearsal tests compare against a --data-ranks run
+        gl = loss.detach().float().reshape(1).clone()
+        if world > 1:
+            gl = gl.to(device) if device.type == "cuda" else gl
+            dist.all_reduce(gl, op=dist.ReduceOp.SUM)
+            gl /= world
+            # every rank must have built the same gradient buckets (boundaries decide which
+            # elements each collective sums): gathered and compared, not assumed
+            red = _reducer_of(runner)
+            plan_b = [list(b) for b in red.buckets] if red is not None else None
+            plans = [None] * world
+            dist.all_gather_object(plans, plan_b)
+            if any(p_ != plan_b for p_ in plans):
+                raise SystemExit(f"bench.py: ranks built different gradient buckets: {plans}")
+            comm["bucket_plans_agree"] = world
+        global_loss = float(gl.item())
+        with torch.no_grad():
+            param_checksum = float(sum(p.detach().double().abs().sum() for p in model.parameters()))
+    if args.full and world > 1 and args.nocomm_steps > 0:  # outside the timed region
         dt0, _ = _timed(_make_step(runner, pool, device, sync_grads=False), args.nocomm_steps, world, device)
         comm["ms_per_step_without_allreduce"] = dt0 / args.nocomm_steps * 1e3
         comm["allreduce_exposed_ms"] = max(0.0, ms - comm["ms_per_step_without_allreduce"])
     elif world == 1:
         comm["allreduce_exposed_ms"] = 0.0
-    if world > 1 and args.comm_probe_iters > 0:  # outside the timed region
+    if args.full and world > 1 and args.comm_probe_iters > 0:  # outside the timed region
         comm.update(_allreduce_probe(device, world, args.comm_probe_iters))
 
     if args.profile:  # outside the timed region
@@ -656,7 +706,7 @@ def run_rank(args):
         if runtime.get("tokensPerSec_mean"):
             runtime["ratio_vs_executor"] = runtime["tokensPerSec_mean"] / tok_s
     ref_tok_s = None
-    if (world == 1 and device.type == "cuda" and args.engine == "fused" and args.ref_steps != 0
+    if (args.full and world == 1 and device.type == "cuda" and args.engine == "fused" and args.ref_steps != 0
             and args.model == "gpt2-124m"):
         if not args.via_runtime:
             ex = getattr(runner, "exec", None)

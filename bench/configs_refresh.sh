@@ -9,7 +9,7 @@ run() {  # name, time limit, command...
   timeout -k 10 $lim "$@" > gpurun_out/cfg_run.log 2>&1 || { echo "$name FAILED"; tail -20 gpurun_out/cfg_run.log; exit 1; }
   echo "$name $(grep '^{' gpurun_out/cfg_run.log | tail -1 | cut -c1-1500)" | tee -a $LOG | cut -c1-300
 }
-run headline 300 python bench.py --steps 20 --warmup 5
+run headline 300 python bench.py --steps 20 --warmup 5 --full
 run gpt2-hf 300 python bench.py --model gpt2-hf --steps 10 --warmup 3 --ref-steps 0
 run gpt2-hf-nodropout 300 env PENROZ_BENCH_HF_PDROP=0 python bench.py --model gpt2-hf --steps 10 --warmup 3 --ref-steps 0
 run gpt2-xl 500 python bench.py --model gpt2-xl --steps 5 --warmup 2 --ref-steps 0

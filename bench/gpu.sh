@@ -2,7 +2,8 @@
 #
 #   bash bench/gpu.sh check                  GPU tests + smoke + headline bench
 #   bash bench/gpu.sh tests [-k EXPR]        GPU tests only (optionally a subset)
-#   bash bench/gpu.sh bench [bench.py args]  headline bench (default 20 timed / 5 warmup steps)
+#   bash bench/gpu.sh bench [bench.py args]  headline bench (default 20 timed / 5 warmup steps;
+#                                            --full adds the eager comparison and the checksums)
 #   bash bench/gpu.sh ab "VAR=a" "VAR=b"     same-box A/B of the headline bench, two passes
 #                                            (any arms x workloads: python bench/ab.py --help)
 #   bash bench/gpu.sh prof [tag] [-- cmd]    rocprofv3 kernel trace + per-step summary (default cmd:

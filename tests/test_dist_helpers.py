@@ -262,9 +262,11 @@ def test_rendezvous_linux_is_ipv4_loopback_without_gloo_overrides():
     assert addr == "127.0.0.1" and env == {}
 
 
+# the IPv6 cases carry explicit ids: the generated ones would hold "::1", and "::" is what separates
+# the parts of a test's node id
 @pytest.mark.parametrize("platform,family,addr,ifname", [
-    ("darwin", "ipv6", "::1", "lo0"), ("darwin", "ipv4", "127.0.0.1", None),
-    ("win32", "ipv6", "::1", None), ("win32", "ipv4", "127.0.0.1", None)])
+    pytest.param("darwin", "ipv6", "::1", "lo0", id="darwin-ipv6-loopback-lo0"), ("darwin", "ipv4", "127.0.0.1", None),
+    pytest.param("win32", "ipv6", "::1", None, id="win32-ipv6-loopback-None"), ("win32", "ipv4", "127.0.0.1", None)])
 def test_rendezvous_off_linux_follows_the_active_family(platform, family, addr, ifname):
     with mock.patch.object(LA, "detect_active_ip_family", return_value=family):
         got, env = LA.rendezvous_env("cpu", platform=platform)

@@ -56,7 +56,7 @@ def test_bench_cli_help():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
                        timeout=120)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--profile"):
+    for flag in ("--gpus", "--steps", "--warmup", "--profile", "--full", "--dump-outputs"):
         assert flag in r.stdout
 
 
@@ -90,12 +90,49 @@ def _json_line(out: str) -> dict:
     return json.loads(lines[0])
 
 
+def _bench_in_process(argv, monkeypatch, capsys) -> dict:
+    import bench
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("PENROZ_ENGINE", os.environ.get("PENROZ_ENGINE", "generic"))  # restored afterwards
+    capsys.readouterr()
+    bench.main(argv)
+    return _json_line(capsys.readouterr().out)
+
+
+def test_bench_plain_run_is_lean_and_dumps_repeatable_outputs(tmp_path, monkeypatch, capsys):
+    """A plain run reports the headline fields and skips the extras that ``--full`` adds;
+    ``--dump-outputs`` writes the last timed step's loss and the sampled updated parameters as
+    float32 ``.npy``, identical from run to run and untouched by ``--full``."""
+    import numpy as np
+    common = ["--gpus", "1", "--device", "cpu", "--model", "tiny", "--steps", "3", "--warmup", "1"]
+    a = _bench_in_process(common + ["--dump-outputs", str(tmp_path / "a")], monkeypatch, capsys)
+    b = _bench_in_process(common + ["--full", "--dump-outputs", str(tmp_path / "b")], monkeypatch, capsys)
+    for d in (a, b):
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "tokens/s" and d["higher_is_better"] is True and d["dtype"] == "fp32"
+        assert abs(d["value"] - 4 * 32 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert a["param_checksum"] is None and a["final_loss_global"] is None
+    assert b["param_checksum"] > 0 and b["final_loss_global"] == b["final_loss"] == a["final_loss"]
+    assert sorted(os.listdir(tmp_path / "a")) == ["loss.npy", "params.npy"]
+    for name in ("loss.npy", "params.npy"):
+        x, y = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert x.dtype == np.float32 and x.shape == y.shape and np.array_equal(x, y), name
+        assert np.isfinite(x).all()
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == pytest.approx(a["final_loss"], rel=1e-6)
+    import bench
+    import torch
+    model, _ = bench._build(bench.parse_args(common), bench.MODELS["tiny"], torch.device("cpu"), "generic", 1)
+    n = sum(min(p.numel(), bench.DUMP_SAMPLE) for p in model.parameters())
+    assert np.load(tmp_path / "a" / "params.npy").shape == (n,)
+
+
 @pytest.mark.slow
 def test_bench_self_launches_ranks_cpu_gloo():
     """`python bench.py --gpus 2` (no torchrun) spawns 2 ranks itself; rank 0 prints ONE JSON line
     with n_gpus == 2 and the communicator's view of the group (2-rank gloo rehearsal)."""
     r = _run_bench(["--gpus", "2", "--device", "cpu", "--model", "tiny", "--steps", "2", "--warmup", "1",
-                    "--nocomm-steps", "1"])
+                    "--nocomm-steps", "1", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2"
@@ -394,7 +431,7 @@ def test_bench_multi_rank_cpu_matches_single_process(world):
     rank-averaged loss and the parameters after the run equal one process training on the
     concatenated batches (``--data-ranks``)."""
     common = ["--device", "cpu", "--model", "tiny", "--steps", "3", "--warmup", "1", "--nocomm-steps", "0",
-              "--comm-probe-iters", "2"]
+              "--comm-probe-iters", "2", "--full"]
     r = _run_bench(["--gpus", str(world)] + common, env_extra={"OMP_NUM_THREADS": "1"}, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
