@@ -8,8 +8,11 @@
 //       torch.optim keeps for them) updated in fp32 registers.
 // Math = torch.optim.AdamW / Adam single-tensor path: decoupled decay p *= 1 − lr·wd (AdamW)
 // or g += wd·p (Adam); m = lerp(m, g, 1 − β1); v = β2·v + (1 − β2)·g²;
-// p −= (lr / bc1) · m / (sqrt(v) / sqrt(bc2) + eps). Bias corrections come from the host in
-// double precision. ``grad_scale`` multiplies the gradient first (micro-step averaging).
+// p −= (lr / bc1) · m / (sqrt(v) / sqrt(bc2) + eps). Bias corrections and the factors 1 − β1,
+// 1 − β2, 1 − lr·wd come from the host in double precision, rounded once: formed in fp32, 1 − β2
+// at β2 = 0.999 is off by 3e-5 relative, which showed as up to 7x the single-step rounding bound
+// against an fp64 step (tests/test_optimizer_kernels_gpu.py).
+// ``grad_scale`` multiplies the gradient first (micro-step averaging).
 #include "common.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -19,17 +22,23 @@ namespace penroz {
 
 struct AdamHyper {
   float lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt, grad_scale;
+  float omb1, omb2, decay;  // 1 − β1, 1 − β2, 1 − lr·wd
   int maximize, decoupled;
 };
 
+// Every instantiation (flat, row-split mode 0 with its constant zero gradient, mode 1, multi-tensor)
+// must round identically: the row-split step promises the dense step's bits. Left to the compiler,
+// the multiply-adds were contracted differently per instantiation (mode 0 vs the flat kernel with
+// L2 decay differed in v and p), so the fused operations are written out and contraction is off.
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamHyper& h) {
+#pragma clang fp contract(off)
   g *= h.grad_scale;
   if (h.maximize) g = -g;
-  if (h.decoupled) p *= 1.f - h.lr * h.wd;
-  else g += h.wd * p;
-  m += (g - m) * (1.f - h.b1);
-  v = h.b2 * v + (1.f - h.b2) * g * g;
-  const float denom = sqrtf(v) * h.inv_bc2_sqrt + h.eps;
+  if (h.decoupled) p *= h.decay;
+  else g = __builtin_fmaf(h.wd, p, g);
+  m = __builtin_fmaf(g - m, h.omb1, m);
+  v = __builtin_fmaf(h.omb2 * g, g, h.b2 * v);
+  const float denom = __builtin_fmaf(sqrtf(v), h.inv_bc2_sqrt, h.eps);
   p -= h.step_size * m / denom;
 }
 
@@ -181,6 +190,9 @@ static AdamHyper make_hyper(double lr, double b1, double b2, double eps, double 
   h.step_size = (float)(lr / bc1);
   h.inv_bc2_sqrt = (float)(1.0 / std::sqrt(bc2));
   h.grad_scale = (float)grad_scale;
+  h.omb1 = (float)(1.0 - b1);
+  h.omb2 = (float)(1.0 - b2);
+  h.decay = (float)(1.0 - lr * wd);
   h.maximize = maximize ? 1 : 0;
   h.decoupled = decoupled ? 1 : 0;
   return h;
@@ -196,7 +208,12 @@ static void flat_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::
   if (shadow.has_value() && shadow->defined()) {
     TORCH_CHECK(shadow->scalar_type() == torch::kBFloat16 && shadow->numel() == p.numel());
     sp = reinterpret_cast<bf16*>(shadow->data_ptr());
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(sp) % 8 == 0, "flat shadow must be 8-B aligned");
   }
+  // the kernel reads the base as float4 (and the shadow as two packed words): a range of the flat
+  // buffers must start on a multiple of 4 elements (every executor segment / bucket does)
+  for (auto* t : {&p, &g, &m, &v})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "flat buffers must be 16-B aligned");
   const int64_t n = p.numel();
   const char* ge = std::getenv("PENROZ_ADAM_GRID");
   // one float4 per thread, non-temporal loads and stores by default: 1.36x (GPT-2 124M flat size)

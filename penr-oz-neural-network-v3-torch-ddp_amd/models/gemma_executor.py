@@ -228,7 +228,7 @@ class GemmaExecutor(GPTExecutor):
         if self.device.type != "cuda" or os.environ.get("PENROZ_DGRAD_T", "1") == "0" or not _ext.available():
             return
         s = self.spec
-        srcs = [(id(s.head.weight), lambda: self.bf16(s.head.weight))]
+        srcs = [(id(s.head.weight), lambda: self.head_w())]  # the head's copy covers its pad rows
         for b in s.blocks:
             srcs += [(id(b.qkv.weight), lambda b=b: self.bf16(b.qkv.weight)),
                      (id(b.o.weight), lambda b=b: self.bf16(b.o.weight)),
@@ -318,7 +318,7 @@ class GemmaExecutor(GPTExecutor):
             self.s_attn = self.s_mlp = None
         self.lnf_out = e(N, C)
         self.head_chunk = _head_chunk_rows(N, V)
-        self._head_bufs = [e(self.head_chunk, (V + 7) // 8 * 8) for _ in range(2 if self.head_chunk < N else 1)]
+        self._head_bufs = [e(self.head_chunk, self._logit_ld()) for _ in range(2 if self.head_chunk < N else 1)]
         self.tmp_c = e(N, C)                               # branch outputs (O / down GEMMs)
         # per-block scratch shared by all blocks: flat buffers sized for the widest block, viewed
         # per block as [N, width] (``_rows``); a view keeps the buffer's data_ptr, so the
@@ -466,7 +466,7 @@ class GemmaExecutor(GPTExecutor):
     def _train_micro_step(self, idx: Tensor, targets: Tensor, scale: float, sync: bool, capture: bool) -> Tensor:
         s = self.spec
         B, T = idx.shape
-        N, C, mode = B * T, s.C, s.mode
+        N, C, V, mode = B * T, s.C, s.V, s.mode
         seed = self._step_seed
         self._step_seed += 1000
         f, gr = self.f32, self.grad
@@ -482,25 +482,27 @@ class GemmaExecutor(GPTExecutor):
         self._defer_reductions(True)
         tg = targets.reshape(-1)
         if cap:
-            full = self._full_logits()
+            full = self._full_logits(padded=True)
             acts = [self.resid[0].view(B, T, C).clone()] + [r.view(B, T, C).clone() for r in self.resid[1:]] + \
-                   [self.lnf_out.view(B, T, C).float().clone(), full.view(B, T, -1).clone()]
+                   [self.lnf_out.view(B, T, C).float().clone(), full[:, :V].reshape(B, T, V).clone()]
             chunks = [(0, N, full)]
             dh_caps = [torch.empty(N, C, dtype=torch.float32, device=self.device) for _ in range(self.L + 1)]
         else:
             chunks = [(r0, min(N, r0 + self.head_chunk), None) for r0 in range(0, N, self.head_chunk)]
             dh_caps = None
         loss = torch.zeros((), dtype=torch.float32, device=self.device)
-        w_head = self._dgrad(s.head.weight, self.bf16(s.head.weight))
+        w_head = self._dgrad(s.head.weight, self.head_w())
         for i, (r0, r1, lg) in enumerate(chunks):
             if lg is None:
                 lg = self._head_logits(r0, r1, self._reuse(self._head_bufs[i % len(self._head_bufs)]))
-            loss += fused_ops.cross_entropy_fwd_bwd(lg, tg[r0:r1], scale / N).sum()
-            torch.mm(lg, w_head, out=self.d_c[r0:r1])
-            self._wgrad(lg, self.lnf_out[r0:r1], s.head.weight)
+            # as GPTExecutor: CE on the V real columns; the pad columns stay the pad rows' exact
+            # zeros, so the padded dgrad / wgrad equal the unpadded ones (pad rows get 0)
+            loss += fused_ops.cross_entropy_fwd_bwd(lg[:, :V], tg[r0:r1], scale / N).sum()
+            torch.mm(lg[:, : w_head.shape[0]], w_head, out=self.d_c[r0:r1])
+            self._wgrad_into(id(s.head.weight), lg, self.lnf_out[r0:r1], self.head_grad())
         loss *= scale / N
         if cap:
-            grads_cap = [full.view(B, T, -1).clone(), self.d_c.view(B, T, C).float().clone()]
+            grads_cap = [full[:, :V].reshape(B, T, V).clone(), self.d_c.view(B, T, C).float().clone()]
         # final combine (last block's MLP side + the final norm): dh_in none
         lb = s.blocks[-1]
         pm = lb.post_mlp

@@ -16,12 +16,12 @@ from penroz.ops import _ext
 import bench
 
 
-def tiny(V=512, C=256, L=2, H=4, P=256, gelu=None):
+def tiny(V=512, C=256, L=2, H=4, P=256, gelu=None, optim=None):
     layers = bench.gpt2_layers(V=V, C=C, L=L, H=H, P=P)
     if gelu:
         for blk in layers[2:2 + L]:
             blk["residual"][1]["sequential"][2] = {"gelu": {"approximate": gelu}}
-    return NeuralNetworkModel("t", Mapper(layers, {"adamw": {"lr": 1e-3, "betas": [0.9, 0.95]}}))
+    return NeuralNetworkModel("t", Mapper(layers, optim or {"adamw": {"lr": 1e-3, "betas": [0.9, 0.95]}}))
 
 
 @pytest.mark.parametrize("gelu", [None, "tanh"])
@@ -238,3 +238,77 @@ def test_executors_share_one_high_priority_stream(monkeypatch):
     s1, s2 = e1._main_stream(), e2._main_stream()
     assert s1 is s2 is a
     assert e1._side is e2._side  # one side stream per device and process too
+
+
+# ---- the lm_head's zero pad rows (V = 509 -> 512 rows in the flat buffers) ------------------------
+PAD_V = 509
+ADAM_L2 = {"adam": {"lr": 1e-3, "betas": [0.9, 0.95], "weight_decay": 0.1}}
+
+
+def _train_steps(m, steps, fuse, V=PAD_V):
+    from penroz.models.model import _FusedRunner
+    runner = _FusedRunner(m, torch.device("cuda"), False)
+    # distinct tokens within a step: the wte scatter-add (atomics) has one addend per row, so a run
+    # does not depend on their order and two runs can be compared bitwise
+    g = torch.Generator().manual_seed(7)
+    data = torch.stack([torch.randperm(V, generator=g)[:130].view(2, 65) for _ in range(steps)]).cuda()
+    losses = []
+    for i in range(steps):
+        runner.zero_grad()
+        b = data[i]
+        losses.append(float(runner.exec.train_micro_step(b[:, :-1].contiguous(), b[:, 1:].contiguous(), 1.0,
+                                                         sync=True, fuse_optimizer=fuse)))
+        runner.step()
+    return losses
+
+
+def _tiny_seeded(seed, **kw):
+    torch.manual_seed(seed)
+    return tiny(V=PAD_V, **kw).cuda()
+
+
+@pytest.mark.parametrize("optim", [None, ADAM_L2], ids=["adamw", "adam_l2"])
+def test_head_pad_rows_stay_zero_through_optimizer_steps(optim):
+    """3 steps with the optimizer fused into the backward and 3 with the separate step, AdamW and
+    Adam (L2): the pad rows of the masters, the bf16 shadow, the gradient and both moments stay
+    exactly zero, and the state_dict shows the [V, C] head."""
+    m = _tiny_seeded(0, optim=optim)
+    losses = _train_steps(m, 3, True) + _train_steps(m, 3, False)
+    assert all(math.isfinite(v) for v in losses)
+    ex = m._get_executor(torch.device("cuda"))
+    assert isinstance(ex, GPTExecutor) and ex.head_pad_rows() == 3 and ex.Vp == 512
+    torch.cuda.synchronize()
+    C = ex.spec.C
+    off = ex.offsets[id(ex.spec.head.weight)]
+    s, e = off + PAD_V * C, off + ex.Vp * C
+    f = m.optimizer._flat
+    assert f is not None and f["param"] is ex.flat
+    for name, buf in (("flat", ex.flat), ("shadow", ex.shadow), ("flat_grad", ex.flat_grad), ("m", f["m"]),
+                      ("v", f["v"])):
+        assert buf[s:e].abs().max().item() == 0.0, f"pad rows of {name} moved"
+        assert buf[off:s].abs().max().item() > 0.0, name  # the real rows did train
+    head = next(n for n, p in m.named_parameters() if p is ex.spec.head.weight)
+    assert tuple(m.state_dict()[head].shape) == (PAD_V, C)
+
+
+def test_head_pad_off_gives_the_same_training(monkeypatch):
+    """PENROZ_HEAD_PAD=0 (no pad rows) runs the same 3 steps. Asked for: the loss curve to 1e-5 and
+    the head weights to 1e-6; measured on the MI355X both are bitwise equal (the pad columns add
+    exact zeros and the GEMMs reduce over C in the same order at both widths), so that is asserted
+    (the tokens of a step are distinct: see ``_train_steps``)."""
+    monkeypatch.delenv("PENROZ_HEAD_PAD", raising=False)
+    a = _tiny_seeded(1)
+    la = _train_steps(a, 3, True)
+    exa = a._get_executor(torch.device("cuda"))
+    assert exa.head_pad_rows() == 3
+    wa = exa.spec.head.weight.detach().clone()
+    monkeypatch.setenv("PENROZ_HEAD_PAD", "0")
+    b = _tiny_seeded(1)
+    lb = _train_steps(b, 3, True)
+    exb = b._get_executor(torch.device("cuda"))
+    assert exb.head_pad_rows() == 0 and exb.Vp == PAD_V
+    wb = exb.spec.head.weight.detach()
+    print(f"loss padded {la} unpadded {lb}; head max |diff| {(wa - wb).abs().max().item():.3g}, "
+          f"bitwise {torch.equal(wa, wb)}")
+    assert la == lb, "loss curves differ"
+    assert torch.equal(wa, wb), "head weights differ"

@@ -28,13 +28,14 @@ DEV = "cuda"
 
 
 def _gemma(model_type="gemma3_text", V=512, C=256, L=2, H=4, Hkv=2, D=64, F=512, seed=0, act="gelu_pytorch_tanh",
-           **extra):
+           optim=None, **extra):
     torch.manual_seed(seed)
     cfg = SimpleNamespace(model_type=model_type, vocab_size=V, hidden_size=C, intermediate_size=F, num_hidden_layers=L,
                           num_attention_heads=H, num_key_value_heads=Hkv, head_dim=D, rms_norm_eps=1e-6,
                           rope_theta=10000.0, rope_local_base_freq=10000.0, attention_dropout=0.0,
                           hidden_activation=act, query_pre_attn_scalar=D, sliding_window=512, **extra)
-    m = NeuralNetworkModel("g", Mapper(Mapper.from_hf_config(cfg), {"adamw": {"lr": 1e-3, "betas": [0.9, 0.95]}}))
+    m = NeuralNetworkModel("g", Mapper(Mapper.from_hf_config(cfg),
+                                       optim or {"adamw": {"lr": 1e-3, "betas": [0.9, 0.95]}}))
     with torch.no_grad():  # non-trivial norm weights, so every dγ path carries signal
         for n, p in m.named_parameters():
             if p.dim() == 1:
@@ -50,14 +51,13 @@ def test_match_modes(model_type, mode):
     assert spec is not None and spec.mode == mode and (spec.H, spec.Hkv, spec.D, spec.F) == (4, 2, 64, 512)
 
 
-@pytest.mark.parametrize("model_type", ["gemma3_text", "gemma2", "gemma"])
-def test_one_step_matches_fp32_reference(model_type):
-    m = _gemma(model_type).to(DEV)
+def _one_step_matches_fp32_reference(model_type, V):
+    m = _gemma(model_type, V=V).to(DEV)
     ref = copy.deepcopy(m)
     B, T = 4, 128
     g = torch.Generator(device=DEV).manual_seed(1)
-    x = torch.randint(0, 512, (B, T), device=DEV, generator=g)
-    y = torch.randint(0, 512, (B, T), device=DEV, generator=g)
+    x = torch.randint(0, V, (B, T), device=DEV, generator=g)
+    y = torch.randint(0, V, (B, T), device=DEV, generator=g)
     _ext.FORCE_TORCH = True
     try:
         _, loss_ref = ref(x, y, skip_softmax=True)
@@ -74,7 +74,57 @@ def test_one_step_matches_fp32_reference(model_type):
         rel = ((ex.grad(p) - r.grad).norm() / (r.grad.norm() + 1e-12)).item()
         worst = max(worst, rel)
         assert rel < 5e-2, f"{model_type} {n}: rel grad err {rel}"
-    print(f"{model_type}: loss {loss.item():.5f} vs {loss_ref.item():.5f}, worst rel grad err {worst:.4f}")
+    print(f"{model_type} V={V}: loss {loss.item():.5f} vs {loss_ref.item():.5f}, worst rel grad err {worst:.4f}")
+    return ex
+
+
+@pytest.mark.parametrize("model_type", ["gemma3_text", "gemma2", "gemma"])
+def test_one_step_matches_fp32_reference(model_type):
+    _one_step_matches_fp32_reference(model_type, 512)
+
+
+# V = 1000: the lm_head weight carries 24 zero pad rows (up to a multiple of 128), which no HF Gemma
+# vocabulary and no V = 512 test has
+PAD_V = 1000
+
+
+@pytest.mark.parametrize("model_type", ["gemma3_text", "gemma2"])
+def test_one_step_matches_fp32_reference_with_padded_head(model_type):
+    ex = _one_step_matches_fp32_reference(model_type, PAD_V)
+    assert ex.head_pad_rows() == 24 and ex.Vp == 1024
+    torch.cuda.synchronize()
+    assert ex.head_grad()[PAD_V:].abs().max().item() == 0.0, "pad rows must get an exactly zero gradient"
+
+
+@pytest.mark.parametrize("model_type", ["gemma3_text", "gemma2"])
+def test_eval_loss_and_logits_with_padded_head_match_fp32_reference(model_type):
+    """``eval_loss`` and ``logits_for`` (inherited from the GPT executor) at a padded head: the loss
+    within the one-step bound (2e-2); the logits are [B, T, V] and within 2e-2 of the fp32 model in
+    relative norm — about 13 bf16 roundings lie on the path (per block QKV, attention, O, gate|up,
+    activation, down; the final norm output), each ≤ 2⁻⁹ relative: √13 · 2⁻⁹ ≈ 7e-3, times 3."""
+    m = _gemma(model_type, V=PAD_V).to(DEV)
+    ref = copy.deepcopy(m)
+    B, T = 2, 96
+    g = torch.Generator(device=DEV).manual_seed(5)
+    x = torch.randint(0, PAD_V, (B, T), device=DEV, generator=g)
+    y = torch.randint(0, PAD_V, (B, T), device=DEV, generator=g)
+    _ext.FORCE_TORCH = True
+    try:
+        with torch.no_grad():
+            acts_ref, loss_ref = ref(x, y, skip_softmax=True)
+            logits_ref = acts_ref[-1]
+    finally:
+        _ext.FORCE_TORCH = False
+    ex = GemmaExecutor(m, torch.device(DEV))
+    assert ex.head_pad_rows() == 24
+    loss = ex.eval_loss(x, y)
+    assert abs(loss.item() - loss_ref.item()) < 2e-2, (loss.item(), loss_ref.item())
+    logits = ex.logits_for(x)
+    assert tuple(logits.shape) == (B, T, PAD_V)
+    logits_ref = logits_ref.float().reshape(B, T, PAD_V)
+    rel = ((logits.float() - logits_ref).norm() / logits_ref.norm()).item()
+    print(f"{model_type}: eval loss {loss.item():.5f} vs {loss_ref.item():.5f}, logits rel err {rel:.4f}")
+    assert rel < 2e-2, rel
 
 
 # Gemma-4-like heterogeneous layer list (reference mappers.py:206-233): alternating sliding / full
@@ -283,11 +333,12 @@ def test_bf16_params_train_and_keep_state_dict():
     assert abs(c_mod.item() - c_ex.item()) < 0.1, (c_mod.item(), c_ex.item())
 
 
-def _train(m, steps, fuse, micro=1):
+def _train(m, steps, fuse, micro=1, vocab=512, data=None):
     from penroz.models.model import _FusedRunner
     runner = _FusedRunner(m, torch.device(DEV), False)
     g = torch.Generator(device=DEV).manual_seed(7)
-    data = torch.randint(0, 512, (steps * micro, 2, 65), device=DEV, generator=g)
+    if data is None:
+        data = torch.randint(0, vocab, (steps * micro, 2, 65), device=DEV, generator=g)
     losses = []
     for i in range(steps):
         runner.zero_grad()
@@ -316,7 +367,7 @@ def test_optimizer_in_backward_matches_the_separate_step(micro):
             assert torch.equal(p, q), n
 
 
-@pytest.mark.parametrize("V,steps", [(512, 3), (16384, 8)])
+@pytest.mark.parametrize("V,steps", [(512, 3), (16384, 8), (1000, 3)])  # 1000: padded lm_head rows
 def test_row_split_embedding_adamw_matches_dense(monkeypatch, V, steps):
     """The embedding table's AdamW split into untouched rows (during the forward, zero gradient)
     and touched rows (after the embedding backward, gradient cleared) == the dense fused step; the
@@ -396,3 +447,61 @@ def test_new_session_after_segment_transposes_uses_fresh_weights(monkeypatch):
         a, b = ex.grad(p), ref.grad(q)
         rel = ((a - b).norm() / (b.norm() + 1e-12)).item()
         assert rel < 1e-2, f"{n}: rel grad err {rel}"
+
+
+# ---- the lm_head's zero pad rows (V = 1000 -> 1024 rows in the flat buffers) ----------------------
+ADAM_L2 = {"adam": {"lr": 1e-3, "betas": [0.9, 0.95], "weight_decay": 0.1}}
+
+
+def _head_name(m, ex):
+    return next(n for n, p in m.named_parameters() if p is ex.spec.head.weight)
+
+
+@pytest.mark.parametrize("optim", [None, ADAM_L2], ids=["adamw", "adam_l2"])
+def test_head_pad_rows_stay_zero_through_optimizer_steps(optim):
+    """3 steps with the optimizer fused into the backward and 3 with the separate step, AdamW and
+    Adam (L2): the pad rows of the masters, the bf16 shadow, the gradient and both moments stay
+    exactly zero, and the state_dict shows the [V, C] head."""
+    m = _gemma("gemma3_text", V=PAD_V, seed=9, optim=optim).to(DEV)
+    la = _train(m, 3, True, vocab=PAD_V)
+    lb = _train(m, 3, False, vocab=PAD_V)
+    assert all(torch.isfinite(torch.tensor(la + lb)))
+    ex = m._get_executor(torch.device(DEV))
+    assert isinstance(ex, GemmaExecutor) and ex.head_pad_rows() == 24
+    torch.cuda.synchronize()
+    C = ex.spec.C
+    off = ex.offsets[id(ex.spec.head.weight)]
+    s, e = off + PAD_V * C, off + ex.Vp * C
+    f = m.optimizer._flat
+    assert f is not None and f["param"] is ex.flat
+    for name, buf in (("flat", ex.flat), ("shadow", ex.shadow), ("flat_grad", ex.flat_grad), ("m", f["m"]),
+                      ("v", f["v"])):
+        assert buf[s:e].abs().max().item() == 0.0, f"pad rows of {name} moved"
+        assert buf[off:s].abs().max().item() > 0.0, name  # the real rows did train
+    assert tuple(m.state_dict()[_head_name(m, ex)].shape) == (PAD_V, C)
+    assert tuple(ex.spec.head.weight.shape) == (PAD_V, C)
+
+
+def test_head_pad_off_gives_the_same_training(monkeypatch):
+    """PENROZ_HEAD_PAD=0 (no pad rows) runs the same 3 steps. Asked for: the loss curve to 1e-5 and
+    the head weights to 1e-6; measured on the MI355X both are bitwise equal (the pad columns add
+    exact zeros and the GEMMs reduce over C in the same order at both widths), so that is asserted.
+    Every step's tokens are distinct, so the embedding scatter-add (atomics) has one addend per row
+    and the whole run is order-independent."""
+    monkeypatch.delenv("PENROZ_HEAD_PAD", raising=False)
+    gen = torch.Generator().manual_seed(7)
+    data = torch.stack([torch.randperm(PAD_V, generator=gen)[:130].view(2, 65) for _ in range(3)]).to(DEV)
+    a = _gemma("gemma3_text", V=PAD_V, seed=9).to(DEV)
+    la = _train(a, 3, True, data=data)
+    assert a._get_executor(torch.device(DEV)).head_pad_rows() == 24
+    wa = a._get_executor(torch.device(DEV)).spec.head.weight.detach().clone()
+    monkeypatch.setenv("PENROZ_HEAD_PAD", "0")
+    b = _gemma("gemma3_text", V=PAD_V, seed=9).to(DEV)
+    lb = _train(b, 3, True, data=data)
+    exb = b._get_executor(torch.device(DEV))
+    assert exb.head_pad_rows() == 0 and exb.Vp == PAD_V
+    wb = exb.spec.head.weight.detach()
+    print(f"loss padded {la} unpadded {lb}; head max |diff| {(wa - wb).abs().max().item():.3g}, "
+          f"bitwise {torch.equal(wa, wb)}")
+    assert la == lb, "loss curves differ"
+    assert torch.equal(wa, wb), "head weights differ"

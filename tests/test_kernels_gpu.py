@@ -241,7 +241,7 @@ def test_cross_entropy_any_vocab_padded_rows(V):
     _close(logits, x.float() @ w.float().t(), 0.1, 0.01)
 
 
-@pytest.mark.parametrize("n", [10007, 10_000_003])  # the second runs the 2-group unrolled trips
+@pytest.mark.parametrize("n", [10007, 10_000_003])  # one float4 per thread plus a scalar tail (n % 4 == 3)
 def test_adamw_flat_matches_torch(n):
     torch.manual_seed(0)
     p = torch.randn(n, device=DEV)
