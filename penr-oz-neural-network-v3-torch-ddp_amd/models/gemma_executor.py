@@ -1,5 +1,7 @@
 """Fused Gemma-family training / eval executor for MI355X (the Gemma analogue of
-:class:`penroz.models.executor.GPTExecutor`).
+:class:`penroz.models.executor.GPTExecutor`; both derive from
+:class:`penroz.models.flat_executor.FlatExecutor`, which holds everything below that does not
+depend on the block structure).
 
 A layer list of the reference's Gemma layout (``mappers.py:179-262``: ScaledEmbedding →
 TransformerBlock(RMSNorm → QKV → RoPE attention (GQA) → O; RMSNorm → GatedMLP; optional post-norms)
@@ -32,23 +34,20 @@ models — what ``/import/`` produces — train with fp32 masters while ``state_
 """
 from __future__ import annotations
 
-import logging
+import os
 from dataclasses import dataclass, field
+from functools import partial
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
 from penroz.models import layers as L
-from penroz.models.executor import GPTExecutor, _head_chunk_rows, _is
+from penroz.models.flat_executor import FlatExecutor
 from penroz.ops import _ext
 from penroz.ops import attention as attn_ops
-from penroz.ops import fused as fused_ops
-from penroz.ops import gemm as gemm_ops
 from penroz.ops import rope as rope_ops
 from penroz.utils.profiling import trace_range
-
-log = logging.getLogger(__name__)
 
 _ACT_KIND = {"gelu": 0, "gelu_tanh": 1, "silu": 2}  # elementwise.hip act_f kinds
 
@@ -89,13 +88,9 @@ class GemmaSpec:
     act: int = 1
     param_dtype: torch.dtype = torch.float32
 
-    # the GPTExecutor helpers read these names
-    @property
-    def lnf(self):
-        return self.norm_f
 
-
-class GemmaExecutor(GPTExecutor):
+class GemmaExecutor(FlatExecutor):
+    PATTERN = "Gemma"
     # the critical path on the high-priority stream: round 5 measured it slightly slower at B = 8;
     # with one stream per role per process (round 6) it is faster: Gemma-3 1B B = 8 66.85 / 66.87
     # -> 66.30 / 66.29 ms (same box, profiles/notes_r6.md §15)
@@ -111,7 +106,7 @@ class GemmaExecutor(GPTExecutor):
     @staticmethod
     def match(model, require_fp32: bool = False) -> GemmaSpec | None:
         ls = list(model.layers)
-        if ls and _is(ls[-1], L.SoftmaxOnLast):
+        if ls and isinstance(ls[-1], L.SoftmaxOnLast):
             ls = ls[:-1]
         if len(ls) < 4 or type(ls[0]) is not L.ScaledEmbedding or type(ls[-2]) is not L.RMSNorm:
             return None
@@ -175,28 +170,10 @@ class GemmaExecutor(GPTExecutor):
         return spec
 
     # ------------------------------------------------------------------ setup
-    def __init__(self, model, device):
-        spec = self.match(model)
-        if spec is None:
-            raise ValueError("model does not match the Gemma pattern")
-        _ext.kernels()
-        if device.type == "cuda":
-            gemm_ops.load_tuned_gemms()
-        self.model = model
-        self.spec = spec
-        self.device = device
-        self.L = len(spec.blocks)
-        self._flatten()
-        self._acts_shape = None
-        self.reducer = None
-        self._captured = None
-        self._step_seed = 0
-        self._reduce_pending = False
-        import os
-        self._overlap_opt = os.environ.get("PENROZ_OVERLAP_OPT", "1") != "0"
-        self._opt_apply, self._opt_done = None, False
-        self._side_init()
+    def _init_model_state(self):
         self._rope_tables = {}
+        self._row_split = None   # (start, end, token rows) of a row-split embedding step in flight
+        self._emb_mask = None    # [V] int32: 1 on the rows this step's tokens touch
 
     def _param_order(self):
         s = self.spec
@@ -221,63 +198,15 @@ class GemmaExecutor(GPTExecutor):
         F, C = b.F, self.spec.C
         return self.flat_grad[off:off + 2 * F * C].view(2 * F, C)
 
-    # ---- transposed bf16 weight copies for the data-gradient GEMMs (see GPTExecutor) ---------
-    def _init_transposed(self):
-        import os
-        self._tw, self._t_ready, self._t_fresh = {}, None, set()
-        if self.device.type != "cuda" or os.environ.get("PENROZ_DGRAD_T", "1") == "0" or not _ext.available():
-            return
+    def _dgrad_sources(self):
         s = self.spec
-        srcs = [(id(s.head.weight), lambda: self.head_w())]  # the head's copy covers its pad rows
+        srcs = [(s.head.weight, self.head_w)]  # the head's copy covers its pad rows
         for b in s.blocks:
-            srcs += [(id(b.qkv.weight), lambda b=b: self.bf16(b.qkv.weight)),
-                     (id(b.o.weight), lambda b=b: self.bf16(b.o.weight)),
-                     (id(b.mlp.gate_proj.weight), lambda b=b: self.gu_bf16(b)),
-                     (id(b.mlp.down_proj.weight), lambda b=b: self.bf16(b.mlp.down_proj.weight))]
-        srcs = [(k, f) for k, f in srcs if f().shape[0] % 64 == 0 and f().shape[1] % 64 == 0]
-        self.shadow_t = torch.empty(sum(f().numel() for _, f in srcs), dtype=torch.bfloat16, device=self.device)
-        off = 0
-        for key, f in srcs:
-            w = f()
-            n = w.numel()
-            self._tw[key] = (f, self.shadow_t[off:off + n].view(w.shape[1], w.shape[0]))
-            off += n
-
-    def _refresh_transposed(self):
-        if not self._tw:
-            return
-        k = _ext.kernels()
-        side = getattr(self, "_side", None)
-        if side is None:
-            for key, (f, t) in self._tw.items():
-                if key not in self._t_fresh:
-                    k.transpose_bf16(f(), t)
-            self._t_fresh.clear()
-            return
-        todo = [(f, t) for key, (f, t) in self._tw.items() if key not in self._t_fresh]
-        self._t_fresh.clear()
-        if not todo:  # all rebuilt after their segments' optimizer passes (the main stream joined)
-            return
-        main = torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(side):
-            side.wait_stream(main)
-            for f, t in todo:
-                k.transpose_bf16(f(), t)
-            self._t_ready = torch.cuda.Event()
-            self._t_ready.record(side)
-
-    def _tw_source(self, entry) -> Tensor:
-        return entry[0]()
-
-    def _dgrad(self, key_param: Tensor, src: Tensor) -> Tensor:
-        """The weight operand of dx = dy·W: the transposed copy (viewed back as [out, in]) or ``src``."""
-        tw = self._tw.get(id(key_param)) if self._tw else None
-        if tw is None:
-            return src
-        if self._t_ready is not None:
-            torch.cuda.current_stream(self.device).wait_event(self._t_ready)
-            self._t_ready = None
-        return tw[1].t()
+            srcs += [(b.qkv.weight, partial(self.bf16, b.qkv.weight)),
+                     (b.o.weight, partial(self.bf16, b.o.weight)),
+                     (b.mlp.gate_proj.weight, partial(self.gu_bf16, b)),  # [gate; up] as one weight
+                     (b.mlp.down_proj.weight, partial(self.bf16, b.mlp.down_proj.weight))]
+        return srcs
 
     # ------------------------------------------------------------------ buffers
     def _alloc(self, B: int, T: int):
@@ -317,8 +246,7 @@ class GemmaExecutor(GPTExecutor):
         else:
             self.s_attn = self.s_mlp = None
         self.lnf_out = e(N, C)
-        self.head_chunk = _head_chunk_rows(N, V)
-        self._head_bufs = [e(self.head_chunk, self._logit_ld()) for _ in range(2 if self.head_chunk < N else 1)]
+        self._alloc_head(N)
         self.tmp_c = e(N, C)                               # branch outputs (O / down GEMMs)
         # per-block scratch shared by all blocks: flat buffers sized for the widest block, viewed
         # per block as [N, width] (``_rows``); a view keeps the buffer's data_ptr, so the
@@ -371,10 +299,9 @@ class GemmaExecutor(GPTExecutor):
     # follow the embedding backward, which leaves the table's gradient all-zero again, so zero_grad
     # skips the 1.2 GB range. Bitwise the same update as the dense step. PENROZ_EMB_ROW_ADAM=0: off.
     def _row_split_begin(self, idx: Tensor):
-        import os
         self._row_split = None
         app = self._opt_apply
-        side = getattr(self, "_side", None)
+        side = self._side
         C = self.spec.C
         # (world > 1: a row untouched here may be touched on another rank — the averaged table
         # gradient is dense, so the per-bucket optimizer updates the table as a whole)
@@ -386,7 +313,7 @@ class GemmaExecutor(GPTExecutor):
         V = self.spec.V
         if (ee - es) != V * C or es % 4:
             return
-        if getattr(self, "_emb_mask", None) is None:
+        if self._emb_mask is None:
             self._emb_mask = torch.zeros(V, dtype=torch.int32, device=self.device)
         rows = idx.reshape(-1).to(torch.int64)
         main = torch.cuda.current_stream(self.device)
@@ -399,7 +326,7 @@ class GemmaExecutor(GPTExecutor):
         self._row_split = (es, ee, rows)
 
     def _segment_done(self, seg_index: int, sync: bool):
-        rs = getattr(self, "_row_split", None)
+        rs = self._row_split
         if rs is None or seg_index != self.L + 1 or self._opt_apply is None or not sync:
             return super()._segment_done(seg_index, sync)
         es, ee, rows = rs
@@ -472,7 +399,7 @@ class GemmaExecutor(GPTExecutor):
         f, gr = self.f32, self.grad
         k = _ext.kernels()
         self._refresh_transposed()
-        self._micro_since_zero = getattr(self, "_micro_since_zero", 0) + 1
+        self._micro_since_zero += 1
         self._row_split_begin(idx)
         with trace_range("forward"):
             self._forward(idx, training=True, dropout_seed=seed)
@@ -481,26 +408,13 @@ class GemmaExecutor(GPTExecutor):
         head_range.__enter__()
         self._defer_reductions(True)
         tg = targets.reshape(-1)
+        full = dh_caps = None
         if cap:
             full = self._full_logits(padded=True)
             acts = [self.resid[0].view(B, T, C).clone()] + [r.view(B, T, C).clone() for r in self.resid[1:]] + \
                    [self.lnf_out.view(B, T, C).float().clone(), full[:, :V].reshape(B, T, V).clone()]
-            chunks = [(0, N, full)]
             dh_caps = [torch.empty(N, C, dtype=torch.float32, device=self.device) for _ in range(self.L + 1)]
-        else:
-            chunks = [(r0, min(N, r0 + self.head_chunk), None) for r0 in range(0, N, self.head_chunk)]
-            dh_caps = None
-        loss = torch.zeros((), dtype=torch.float32, device=self.device)
-        w_head = self._dgrad(s.head.weight, self.head_w())
-        for i, (r0, r1, lg) in enumerate(chunks):
-            if lg is None:
-                lg = self._head_logits(r0, r1, self._reuse(self._head_bufs[i % len(self._head_bufs)]))
-            # as GPTExecutor: CE on the V real columns; the pad columns stay the pad rows' exact
-            # zeros, so the padded dgrad / wgrad equal the unpadded ones (pad rows get 0)
-            loss += fused_ops.cross_entropy_fwd_bwd(lg[:, :V], tg[r0:r1], scale / N).sum()
-            torch.mm(lg[:, : w_head.shape[0]], w_head, out=self.d_c[r0:r1])
-            self._wgrad_into(id(s.head.weight), lg, self.lnf_out[r0:r1], self.head_grad())
-        loss *= scale / N
+        loss = self._head_backward(tg, scale, N, full)
         if cap:
             grads_cap = [full[:, :V].reshape(B, T, V).clone(), self.d_c.view(B, T, C).float().clone()]
         # final combine (last block's MLP side + the final norm): dh_in none
@@ -523,11 +437,11 @@ class GemmaExecutor(GPTExecutor):
             db = self.d_branch2[rb]
             # ---- MLP: down dgrad / wgrad, packed gated backward, gate|up dgrad / wgrad
             d_g = self._rows(self.d_g, N, b.F)
-            torch.mm(db, self._dgrad(b.mlp.down_proj.weight, self.bf16(b.mlp.down_proj.weight)), out=d_g)
+            torch.mm(db, self._dgrad_w(b.mlp.down_proj.weight), out=d_g)
             self._wgrad(db, self.g[l], b.mlp.down_proj.weight)
             dgu = self._rows(self._reuse(self.d_gu2[l & 1]), N, 2 * b.F)
             k.gated_act_bwd_packed(d_g, self.gu[l], dgu, s.act)
-            torch.mm(dgu, self._dgrad(b.mlp.gate_proj.weight, self.gu_bf16(b)), out=self.d_c)
+            torch.mm(dgu, self._dgrad_w(b.mlp.gate_proj.weight), out=self.d_c)
             self._wgrad_into(id(b.mlp.gate_proj.weight), dgu, self.y_mlp[l], self.gu_grad(b))
             # ---- attention combine: dy = d(pre-MLP norm output), dh_in = dresid (grad of mid[l])
             pa = b.post_attn
@@ -539,7 +453,7 @@ class GemmaExecutor(GPTExecutor):
                               gr(pa.weight) if pa is not None else None, gr(b.pre_mlp.weight))
             # ---- attention: O dgrad / wgrad, flash backward, inverse RoPE, QKV dgrad / wgrad
             datt = self._rows(self._reuse(self.d_att2[l & 1]), N, H * D)
-            torch.mm(db, self._dgrad(b.o.weight, self.bf16(b.o.weight)), out=datt)
+            torch.mm(db, self._dgrad_w(b.o.weight), out=datt)
             self._wgrad(db, self.att[l], b.o.weight)
             d_qkv = self._rows(self.d_qkv, N, QKV)
             attn_ops.flash_bwd(datt.view(B, T, H * D), self.qkv[l].view(B, T, -1), self.att[l].view(B, T, H * D),
@@ -547,7 +461,7 @@ class GemmaExecutor(GPTExecutor):
             cos, sin = self._rope(b, T)
             dqr = self._rows(self._reuse(self.d_qkv_raw2[l & 1]), N, QKV)
             k.rope_qkv(d_qkv.view(B, T, -1), cos, sin, H, Hkv, D, True, dqr)
-            torch.mm(dqr, self._dgrad(b.qkv.weight, self.bf16(b.qkv.weight)), out=self.d_c)
+            torch.mm(dqr, self._dgrad_w(b.qkv.weight), out=self.d_c)
             self._wgrad(dqr, self.y_in[l], b.qkv.weight)
             # ---- the combine that produced y_in[l]: block l-1's MLP combine (or the embedding norm)
             if l > 0:
@@ -570,25 +484,10 @@ class GemmaExecutor(GPTExecutor):
         gw = gr(s.emb.weight)
         gw.index_add_(0, idx.reshape(-1), self.dresid, alpha=float(s.emb.scale))
         self._segment_done(self.L + 1, sync)
-        self._defer_reductions(False)
-        self._finish_wgrad_bookkeeping()
-        self._join_side()
-        if sync and self.reducer is not None:
-            self.reducer.launch_remaining()
-            if self._opt_bucketed:  # every bucket's AdamW is queued on the optimizer stream
-                self._opt_buckets(range(len(self.reducer.buckets)))
-                torch.cuda.current_stream(self.device).wait_stream(self._opt_stream)
-                self.reducer.reset()
-            elif self._overlap_opt and not cap and self.reducer.per_bucket_waits():
-                self._reduce_pending = True
-            else:
-                with trace_range("grad_allreduce.wait"):
-                    self.reducer.finish()
+        self._finish_backward(sync, cap)
         if cap:
             # block outputs' gradients: dh of the combine that produced each resid[l]
             act_grads = [dh_caps[0].view(B, T, C)] + [dh_caps[l].view(B, T, C) for l in range(1, self.L + 1)] + \
                         [grads_cap[1], grads_cap[0]]
-            algos = [m.__class__.__name__.lower() for m in self.model.layers]
-            pairs = list(zip(acts, act_grads))
-            self._captured = (algos, pairs[:len(algos)])
+            self._set_captured(acts, act_grads)
         return loss

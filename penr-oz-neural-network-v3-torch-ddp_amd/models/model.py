@@ -10,8 +10,9 @@ delete / from_huggingface``, ``forward(input, target, skip_softmax) -> (activati
 Training engines (``PENROZ_ENGINE``, default ``auto``):
   * ``fused`` — GPT-2-pattern models on GPU lower to :class:`penroz.models.executor.GPTExecutor`,
     Gemma-pattern models to :class:`penroz.models.gemma_executor.GemmaExecutor` (hand-written HIP
-    kernels + hipBLASLt GEMMs, explicit backward, flat fp32 master/grad buffers, fused AdamW,
-    bucketed RCCL all-reduce overlapped with backward);
+    kernels + hipBLASLt GEMMs, explicit backward; their common base
+    :class:`penroz.models.flat_executor.FlatExecutor` holds the flat fp32 master/grad buffers, the
+    fused AdamW and the bucketed RCCL all-reduce overlapped with backward);
   * ``generic`` — any layer list: module forward (HIP kernels through autograd), bf16 autocast
     on GPU, our bucketed reducer for DDP;
   * ``reference`` — stock PyTorch eager + autocast + ``torch.nn.parallel.DDP`` + foreach AdamW

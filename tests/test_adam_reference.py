@@ -88,13 +88,32 @@ def _flattened(cls, model, monkeypatch, padded):
     """The executor's flat layout on the CPU; ``padded`` lays the lm_head out with its pad rows
     (up to a multiple of 128) as on the GPU, where alone the padding is on."""
     if padded:
-        monkeypatch.setattr(cls, "head_pad_rows", lambda self: (-self.spec.V) % self.HEAD_PAD)
+        monkeypatch.setattr(cls, "_head_pad_policy", lambda self: (-self.spec.V) % self.HEAD_PAD)
     ex = object.__new__(cls)
     ex.model, ex.spec, ex.device = model, cls.match(model), torch.device("cpu")
     assert ex.spec is not None
     ex.L = len(ex.spec.blocks)
     ex._flatten()
     return ex
+
+
+def test_head_pad_is_fixed_when_the_flat_buffers_are_laid_out(monkeypatch):
+    """PENROZ_HEAD_PAD is read once, by ``_flatten``: changing it afterwards must not move the
+    slices an existing executor takes out of its flat buffers."""
+    monkeypatch.delenv("PENROZ_HEAD_PAD", raising=False)
+    with monkeypatch.context() as construction:  # the padded policy holds for the layout only
+        ex = _flattened(GPTExecutor, _gpt(509), construction, True)
+    C = ex.spec.C
+    assert ex.Vp == 512 and ex.head_pad_rows() == 3
+    monkeypatch.setenv("PENROZ_HEAD_PAD", "0")
+    assert ex.Vp == 512 and ex.head_pad_rows() == 3
+    assert ex.head_w().shape == (512, C) and ex.head_grad().shape == (512, C)
+    off = ex.offsets[id(ex.spec.head.weight)]
+    pad = slice(off + 509 * C, off + 512 * C)  # the flat pad range: right after the V real rows
+    for rows, flat in ((ex.head_w()[509:], ex.shadow), (ex.head_grad()[509:], ex.flat_grad)):
+        assert rows.shape == (3, C) and rows.is_contiguous()
+        assert rows.data_ptr() == flat[pad].data_ptr() and rows.numel() == flat[pad].numel()
+    assert torch.all(ex.flat[pad] == 0) and torch.all(ex.head_w()[509:] == 0)
 
 
 @pytest.mark.parametrize("padded", [False, True])

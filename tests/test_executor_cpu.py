@@ -103,6 +103,19 @@ def test_gemma_executor_matches_heterogeneous_gemma4_layer_list():
     assert GemmaExecutor.match(NeuralNetworkModel("w", Mapper(Mapper.from_hf_config(wide), {"adamw": {}}))) is not None
 
 
+def test_executors_share_the_flat_base_and_do_not_copy_it():
+    """Both executors derive from FlatExecutor, neither from the other, and the model-independent
+    methods exist once, in the base."""
+    from penroz.models.flat_executor import FlatExecutor
+    from penroz.models.gemma_executor import GemmaExecutor
+    assert not issubclass(GemmaExecutor, GPTExecutor)
+    assert issubclass(GemmaExecutor, FlatExecutor) and issubclass(GPTExecutor, FlatExecutor)
+    for cls in (GPTExecutor, GemmaExecutor):
+        for name in ("_refresh_transposed", "_dgrad_w", "_head_logits", "eval_loss", "optimizer_step"):
+            assert name not in cls.__dict__, (cls.__name__, name)
+            assert name in FlatExecutor.__dict__, name
+
+
 def _range_exec(monkeypatch):
     """A bare executor with only the weight-gradient bookkeeping live: flat fp32 buffer, wgrad
     done eagerly on the CPU (g = dyᵀ·x or g += dyᵀ·x), no side stream."""
@@ -113,6 +126,7 @@ def _range_exec(monkeypatch):
     ex.flat_grad = torch.zeros(64)
     ex.device = types.SimpleNamespace(type="cuda", index=0)  # range learning is a GPU-path feature
     ex._side = None
+    ex._init_wgrad_state()
     ex.wait_gradients = lambda: None
 
     def wgrad(dy, x, g, acc):

@@ -217,8 +217,8 @@ def test_transposed_dgrad_weights_follow_the_main_stream():
     ex.shadow.mul_(2.0)
     ex._refresh_transposed()
     torch.cuda.synchronize()
-    for w, t in ex._tw.values():
-        assert torch.equal(t, ex.bf16(w).t()), "transpose ran before the main stream's shadow write"
+    for src, t in ex._tw.values():
+        assert torch.equal(t, src().t()), "transpose ran before the main stream's shadow write"
 
 
 def test_executors_share_one_high_priority_stream(monkeypatch):

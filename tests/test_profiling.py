@@ -31,7 +31,7 @@ def test_profile_steps_writes_trace_and_table(tmp_path):
 
 def test_executor_phases_are_instrumented():
     import inspect
-    from penroz.models import executor
-    src = inspect.getsource(executor)
+    from penroz.models import executor, flat_executor
+    src = inspect.getsource(executor) + inspect.getsource(flat_executor)  # the block loop + the shared base
     for name in ("forward", "backward.head", "backward.block", "grad_allreduce.wait", "optimizer"):
         assert name in src
