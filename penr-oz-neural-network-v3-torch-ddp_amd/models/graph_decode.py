@@ -5,11 +5,13 @@ The reference decodes one token per Python iteration through every layer module
 batch 64 on MI355X that per-token path is launch-bound: ~150 kernel launches plus Python
 dispatch per token cost ~2.9 ms while the actual work (weights + cache read once) is ~0.2 ms.
 
-Here the decode step — the model's own module forward (so numerics are the eager path's:
-same LayerNorm / GELU / decode-attention kernels, same GEMMs), KV append, sampling, and the
-feedback of the sampled token into the next step's input — is captured ONCE per
-(rows, block size, sampling settings) into a ``torch.cuda.CUDAGraph`` (a hipGraph on ROCm) and
-replayed. Everything that changes between steps lives on the device:
+Here the decode step — the model's forward, KV append, sampling, and the feedback of the sampled
+token into the next step's input — is captured ONCE per (rows, block size, sampling settings) into
+a ``torch.cuda.CUDAGraph`` (a hipGraph on ROCm) and replayed. For bf16 GPT-2-pattern and Gemma-family
+models the forward is an explicit kernel sequence (``GPTDecodeProgram``, ``GemmaDecodeProgram``:
+one loop over the blocks, the kernel of each linear chosen by the row count); any other model
+replays its own module forward, whose numerics are the eager path's. Everything that changes
+between steps lives on the device:
 
 * ``StaticKVCache.pos_t`` / ``len_t``: the slot this step writes and the cache length after it;
   the decode-attention kernel reads q in place and ``len_t`` at run time, and appends this step's
@@ -129,7 +131,6 @@ class StaticKVCache(_GraphMode, kvc.KVCache):
         _ext.kernels().kv_append(k, v, kc, vc, None, None, self.pos_t, 0)
         return attn_ops.decode_attention(q, kc, vc, kc.shape[2], seq_len_dev=self.len_t)
 
-
     def rope_attend_ok(self, B: int, H: int, Hkv: int, D: int) -> bool:
         """``attend_rope`` applies: opted in (PENROZ_DECODE_ROPE_IN_ATTN=1), graph mode with the
         fused append, the small decode kernel. Off by default: Gemma-3 1B batch 32 / 64 measured
@@ -160,24 +161,126 @@ class StaticTurboKVCache(_GraphMode, kvc.TurboQuantKVCache):
                                          seq_len_dev=self.len_t)
 
 
+def _qkv_views(qkv: Tensor, H: int, Hkv: int, D: int):
+    """q [rows, 1, H, D], k and v [rows, 1, Hkv, D] as views into the fused QKV rows."""
+    rows = qkv.shape[0]
+    q, k, v = qkv.view(rows, 1, -1).split([H * D, Hkv * D, Hkv * D], dim=2)
+    return q.reshape(rows, 1, H, D), k.view(rows, 1, Hkv, D), v.view(rows, 1, Hkv, D)
+
+
+class _PlainSteps:
+    """The GPT block's steps on separate kernels: [add-residual + bias + LN] → GEMM+bias (→ GELU),
+    8 per block (9 with the separate KV append). Owns the fp32 residual stream, as every regime
+    does: ``x`` is the sum up to the last norm; proj and fc2 leave their output and fp32 bias
+    pending in ``delta`` / ``dbias``, and the next norm's kernel adds them, writing the new sum to
+    the other buffer ``x2`` (the stream ping-pongs, no aliasing)."""
+
+    def __init__(self, prog, x: Tensor, x2: Tensor | None = None, emb=None):
+        self.prog, self.x, self.x2, self.emb = prog, x, x2, emb
+        self.delta = self.dbias = None
+        self._live = (None, None)
+        self.act = 2 if prog.spec.gelu_approx == "tanh" else 1
+
+    def _take(self):
+        """(resid_in, delta, dbias, resid_out) for the next norm's kernel; the sum it writes is the
+        residual from here on."""
+        if self.delta is None:
+            return self.x, None, None, None
+        args = (self.x, self.delta, self.dbias, self.x2)
+        self.x, self.x2, self.delta, self.dbias = self.x2, self.x, None, None
+        return args
+
+    def norm_linear(self, ln, lin, gelu: bool = False) -> Tensor:
+        x, delta, dbias, out = self._take()
+        if delta is None:
+            y, _, _ = norm_ops.ln_fwd(x, *ln)
+        else:
+            y, _, _ = norm_ops.add_ln_fwd(x, delta, out, *ln, delta_bias=dbias)
+        h = self.prog._linear(y, lin)
+        return act_ops.gelu_fwd(h, self.prog.spec.gelu_approx, out=h) if gelu else h
+
+    def _defer(self, delta: Tensor, fbias: Tensor) -> None:
+        """proj's or fc2's output and the fp32 copy of its bias (GPTDecodeProgram.out_bias), left
+        for the next norm's kernel to add. The output before it stays referenced too: each lives
+        until its successor of the next block exists, so a capture's allocator alternates two
+        buffers for proj and two for fc2 and never hands fc2 the block proj just used (buffer
+        placement shows in the replayed step's time: batch 64 ran 0.7 % slower with fc's output
+        freed one step earlier)."""
+        self.delta, self.dbias = delta, fbias
+        self._live = (self._live[1], delta)
+
+    def project(self, h: Tensor, lin, fbias: Tensor) -> None:
+        self._defer(self.prog._linear(h, lin, bias=False), fbias)
+
+    def head(self, ln, lin) -> Tensor:
+        return _PlainSteps.norm_linear(self, ln, lin)
+
+
+class _FusedSteps(_PlainSteps):
+    """Up to FUSED_MAX_ROWS rows, per block: [add + LN1 + QKV GEMM + bias] → decode attention (K/V
+    append fused) → proj GEMM → [add + proj bias + LN2 + fc GEMM + bias + GELU] → fc2 GEMM: 5 kernels
+    instead of 8. The final add + LN and the lm_head stay separate kernels."""
+
+    def norm_linear(self, ln, lin, gelu: bool = False) -> Tensor:
+        x, delta, dbias, out = self._take()
+        return gemm_ops.decode_ln_linear(x, ln, lin.weight, lin.bias, self.act if gelu else 0, delta=delta,
+                                         dbias=dbias, resid_out=out)
+
+
+class _GemvSteps(_PlainSteps):
+    """Batch 1-4, per block: [add + LN1 + QKV GEMV + bias] → decode attention (K/V append fused)
+    → proj GEMV → [add + proj bias + LN2 + fc GEMV + bias + GELU] → fc2 GEMV; then the final
+    add + LN and the lm_head GEMV — every linear one decode_gemv launch. ``emb`` = (token ids,
+    device position): the first GEMV builds the residual rows wte[tok] + wpe[pos] itself and
+    writes them to ``x`` (one kernel less per token)."""
+
+    def norm_linear(self, ln, lin, gelu: bool = False) -> Tensor:
+        act = self.act if gelu else 0
+        if self.emb is not None:
+            (idx, pos), self.emb, sp = self.emb, None, self.prog.spec
+            return gemm_ops.decode_gemv_emb(idx, pos, sp.wte.weight, sp.wpe.weight, self.x, ln, lin.weight,
+                                            lin.bias, act)
+        x, delta, dbias, out = self._take()
+        return gemm_ops.decode_gemv_ln(x, ln, lin.weight, lin.bias, act, delta=delta, dbias=dbias, resid_out=out)
+
+    def project(self, h: Tensor, lin, fbias: Tensor) -> None:
+        self._defer(gemm_ops.decode_gemv(h, lin.weight), fbias)
+
+    head = norm_linear
+
+
+class _BatchedSteps(_PlainSteps):
+    """Above FUSED_MAX_ROWS rows, per block: [LN1 + QKV GEMM + bias] → decode attention (K/V append
+    fused) → [proj GEMM + bias, added into the fp32 residual in place] → [LN2 + fc GEMM + bias +
+    GELU] → [fc2 GEMM + bias, added into the residual]: 5 kernels instead of 8. Nothing is ever
+    pending, so there is no second residual buffer and the last norm is a plain LN."""
+
+    def norm_linear(self, ln, lin, gelu: bool = False) -> Tensor:
+        return gemm_ops.decode_ln_gemm(self.x, ln, lin.weight, lin.bias, self.act if gelu else 0)
+
+    def project(self, h: Tensor, lin, fbias: Tensor) -> None:
+        _ext.kernels().decode_gemm_acc(h, lin.weight, lin.bias, self.x)
+
+
 class GPTDecodeProgram:
     """One decode step of a GPT-2-pattern bf16 model as an explicit kernel sequence.
 
     The module forward costs ~12 kernels per block at decode shapes (residual adds and dtype
     glue included) and every kernel has a fixed ~4-5 µs cost in a replayed graph at batch 64 —
-    more than most of them compute. Per block this runs 9: [add-residual + fc2 bias + LN1] →
-    QKV GEMM+bias → KV append → decode attention → proj GEMM → [add-residual + proj bias + LN2]
-    → fc GEMM+bias → GELU → fc2 GEMM, with the residual stream kept in fp32 (the training executor's
-    numerics; the module path rounds it to bf16 after every add). The embedding reads the
-    position from the device.
+    more than most of them compute. ``forward`` is one loop over the blocks: norm + QKV linear →
+    decode attention (K/V append fused) → proj into the residual → norm + fc linear + GELU → fc2
+    into the residual, then the final norm + lm_head. Which kernels run those steps depends on the
+    row count (``_GemvSteps`` / ``_FusedSteps`` / ``_BatchedSteps``: 5 per block, ``_PlainSteps``:
+    8). The residual stream is kept in fp32 (the training executor's numerics; the module path
+    rounds it to bf16 after every add). The embedding reads the position from the device.
     """
 
     def __init__(self, model, spec):
         self.spec = spec
         dev = spec.wte.weight.device
         # LayerNorm kernels take fp32 affine parameters
-        self.ln = [(b.ln1.weight.float(), b.ln1.bias.float(), b.ln1.eps, b.ln2.weight.float(), b.ln2.bias.float(),
-                    b.ln2.eps) for b in spec.blocks]
+        self.ln = [((b.ln1.weight.float(), b.ln1.bias.float(), b.ln1.eps),
+                    (b.ln2.weight.float(), b.ln2.bias.float(), b.ln2.eps)) for b in spec.blocks]
         self.lnf = (spec.lnf.weight.float(), spec.lnf.bias.float(), spec.lnf.eps)
         # proj / fc2 biases are added by the following add+LN kernel (fp32), so those two GEMMs
         # run without a bias epilogue (hipBLASLt's pick for fc2 at M = 64 has none: torch then
@@ -229,140 +332,26 @@ class GPTDecodeProgram:
             # B = 1 0.3548 / 0.3564 -> 0.3520 / 0.3544 ms; at 4 rows every workgroup's four-row
             # gather cost more than the launch it saves (0.535 -> 0.551), profiles/decode_r5.md
             x = torch.empty(rows, C, dtype=torch.float32, device=idx.device)
-            return self._forward_gemv(x, torch.empty_like(x), rows, cache, emb=(idx.reshape(-1).contiguous(), cache.pos_t))
-        x = fused_ops.embedding_fwd(idx, sp.wte.weight, sp.wpe.weight, 0, pos_dev=cache.pos_t)  # fp32 [rows, C]
-        if self._batched_ok(rows):
-            return self._forward_batched(x, rows, cache)
-        x2 = torch.empty_like(x)  # the residual stream ping-pongs between x and x2 (no aliasing)
-        if self._gemv_ok(rows):
-            return self._forward_gemv(x, x2, rows, cache)
-        if self._fused_ok(rows):
-            return self._forward_fused(x, x2, rows, cache)
-
-        def add_ln(delta, w, b, eps, dbias=None):
-            nonlocal x, x2
-            y, _, _ = norm_ops.add_ln_fwd(x, delta, x2, w, b, eps, delta_bias=dbias)
-            x, x2 = x2, x
-            return y
-
-        delta = dbias = None
-        for l, blk in enumerate(sp.blocks):
-            w1, b1, e1, w2, b2, e2 = self.ln[l]
-            pb, fb = self.out_bias[l]
-            if delta is None:
-                y, _, _ = norm_ops.ln_fwd(x, w1, b1, e1)
+            s = _GemvSteps(self, x, torch.empty_like(x), emb=(idx.reshape(-1).contiguous(), cache.pos_t))
+        else:
+            x = fused_ops.embedding_fwd(idx, sp.wte.weight, sp.wpe.weight, 0, pos_dev=cache.pos_t)  # fp32 [rows, C]
+            if self._batched_ok(rows):
+                s = _BatchedSteps(self, x)
+            elif self._gemv_ok(rows):
+                s = _GemvSteps(self, x, torch.empty_like(x))
+            elif self._fused_ok(rows):
+                s = _FusedSteps(self, x, torch.empty_like(x))
             else:
-                y = add_ln(delta, w1, b1, e1, dbias)
-            qkv = self._linear(y, blk.qkv).view(rows, 1, 3 * C)
-            q = qkv[:, :, :C].view(rows, 1, H, D)
-            k = qkv[:, :, C:2 * C].view(rows, 1, H, D)
-            v = qkv[:, :, 2 * C:].view(rows, 1, H, D)
-            o = cache._attend_graph(l, q, k, v)
-            d = self._linear(o.view(rows, C), blk.proj, bias=False)
-            y = add_ln(d, w2, b2, e2, pb)
-            h = self._linear(y, blk.fc)
-            h = act_ops.gelu_fwd(h, sp.gelu_approx, out=h)
-            delta, dbias = self._linear(h, blk.fc2, bias=False), fb
-        wf, bf, ef = self.lnf
-        return self._linear(add_ln(delta, wf, bf, ef, dbias), sp.head)
-
-    def _forward_fused(self, x: Tensor, x2: Tensor, rows: int, cache) -> Tensor:
-        """Per block: [add + LN1 + QKV GEMM + bias] → decode attention (K/V append fused) → proj
-        GEMM → [add + proj bias + LN2 + fc GEMM + bias + GELU] → fc2 GEMM: 5 kernels instead of 8."""
-        sp = self.spec
-        K = _ext.kernels()
-        C, H, D = sp.C, sp.H, sp.D
-        act = 2 if sp.gelu_approx == "tanh" else 1
-        delta = dbias = None
+                s = _PlainSteps(self, x, torch.empty_like(x))
         for l, blk in enumerate(sp.blocks):
-            w1, b1, e1, w2, b2, e2 = self.ln[l]
+            ln1, ln2 = self.ln[l]
             pb, fb = self.out_bias[l]
-            qkv = torch.empty(rows, 3 * C, dtype=torch.bfloat16, device=x.device)
-            if delta is None:
-                K.decode_ln_linear(x, None, None, None, w1, b1, e1, blk.qkv.weight, blk.qkv.bias, qkv, 0)
-            else:
-                K.decode_ln_linear(x, delta, dbias, x2, w1, b1, e1, blk.qkv.weight, blk.qkv.bias, qkv, 0)
-                x, x2 = x2, x
-            qkv = qkv.view(rows, 1, 3 * C)
-            q = qkv[:, :, :C].view(rows, 1, H, D)
-            k = qkv[:, :, C:2 * C].view(rows, 1, H, D)
-            v = qkv[:, :, 2 * C:].view(rows, 1, H, D)
+            q, k, v = _qkv_views(s.norm_linear(ln1, blk.qkv), H, H, D)
             o = cache._attend_graph(l, q, k, v)
-            d = self._linear(o.view(rows, C), blk.proj, bias=False)
-            h = torch.empty(rows, blk.fc.out_features, dtype=torch.bfloat16, device=x.device)
-            K.decode_ln_linear(x, d, pb, x2, w2, b2, e2, blk.fc.weight, blk.fc.bias, h, act)
-            x, x2 = x2, x
-            delta, dbias = self._linear(h, blk.fc2, bias=False), fb
-        wf, bf, ef = self.lnf
-        y, _, _ = norm_ops.add_ln_fwd(x, delta, x2, wf, bf, ef, delta_bias=dbias)
-        return self._linear(y, sp.head)
-
-
-    def _forward_gemv(self, x: Tensor, x2: Tensor, rows: int, cache, emb=None) -> Tensor:
-        """Batch 1-4, per block: [add + LN1 + QKV GEMV + bias] → decode attention (K/V append fused)
-        → proj GEMV → [add + proj bias + LN2 + fc GEMV + bias + GELU] → fc2 GEMV; then the final
-        add + LN and the lm_head GEMV — every linear one decode_gemv launch. ``emb`` = (token ids,
-        device position): the first GEMV builds the residual rows wte[tok] + wpe[pos] itself and
-        writes them to ``x`` (one kernel less per token)."""
-        sp = self.spec
-        K = _ext.kernels()
-        C, H, D = sp.C, sp.H, sp.D
-        act = 2 if sp.gelu_approx == "tanh" else 1
-        delta = dbias = None
-        for l, blk in enumerate(sp.blocks):
-            w1, b1, e1, w2, b2, e2 = self.ln[l]
-            pb, fb = self.out_bias[l]
-            qkv = torch.empty(rows, 3 * C, dtype=torch.bfloat16, device=x.device)
-            if delta is None and emb is not None:
-                K.decode_gemv(None, None, None, None, x, w1, b1, e1, blk.qkv.weight, blk.qkv.bias, qkv, 0,
-                              emb_idx=emb[0], emb_wte=sp.wte.weight, emb_wpe=sp.wpe.weight, emb_pos=emb[1])
-            elif delta is None:
-                K.decode_gemv(None, x, None, None, None, w1, b1, e1, blk.qkv.weight, blk.qkv.bias, qkv, 0)
-            else:
-                K.decode_gemv(None, x, delta, dbias, x2, w1, b1, e1, blk.qkv.weight, blk.qkv.bias, qkv, 0)
-                x, x2 = x2, x
-            qkv = qkv.view(rows, 1, 3 * C)
-            q = qkv[:, :, :C].view(rows, 1, H, D)
-            k = qkv[:, :, C:2 * C].view(rows, 1, H, D)
-            v = qkv[:, :, 2 * C:].view(rows, 1, H, D)
-            o = cache._attend_graph(l, q, k, v).view(rows, C)
-            d = torch.empty(rows, C, dtype=torch.bfloat16, device=x.device)
-            K.decode_gemv(o, None, None, None, None, None, None, 0.0, blk.proj.weight, None, d, 0)
-            h = torch.empty(rows, blk.fc.out_features, dtype=torch.bfloat16, device=x.device)
-            K.decode_gemv(None, x, d, pb, x2, w2, b2, e2, blk.fc.weight, blk.fc.bias, h, act)
-            x, x2 = x2, x
-            delta = torch.empty(rows, C, dtype=torch.bfloat16, device=x.device)
-            K.decode_gemv(h, None, None, None, None, None, None, 0.0, blk.fc2.weight, None, delta, 0)
-            dbias = fb
-        wf, bf, ef = self.lnf
-        logits = torch.empty(rows, sp.head.weight.shape[0], dtype=torch.bfloat16, device=x.device)
-        K.decode_gemv(None, x, delta, dbias, x2, wf, bf, ef, sp.head.weight, None, logits, 0)
-        return logits
-
-    def _forward_batched(self, x: Tensor, rows: int, cache) -> Tensor:
-        """Per block: [LN1 + QKV GEMM + bias] → decode attention (K/V append fused) → [proj GEMM +
-        bias, added into the fp32 residual in place] → [LN2 + fc GEMM + bias + GELU] → [fc2 GEMM +
-        bias, added into the residual]: 5 kernels instead of 8."""
-        sp = self.spec
-        K = _ext.kernels()
-        C, H, D = sp.C, sp.H, sp.D
-        act = 2 if sp.gelu_approx == "tanh" else 1
-        for l, blk in enumerate(sp.blocks):
-            w1, b1, e1, w2, b2, e2 = self.ln[l]
-            qkv = torch.empty(rows, 3 * C, dtype=torch.bfloat16, device=x.device)
-            K.decode_ln_gemm(x, w1, b1, e1, blk.qkv.weight, blk.qkv.bias, qkv, 0)
-            qkv = qkv.view(rows, 1, 3 * C)
-            q = qkv[:, :, :C].view(rows, 1, H, D)
-            k = qkv[:, :, C:2 * C].view(rows, 1, H, D)
-            v = qkv[:, :, 2 * C:].view(rows, 1, H, D)
-            o = cache._attend_graph(l, q, k, v)
-            K.decode_gemm_acc(o.view(rows, C), blk.proj.weight, blk.proj.bias, x)
-            h = torch.empty(rows, blk.fc.out_features, dtype=torch.bfloat16, device=x.device)
-            K.decode_ln_gemm(x, w2, b2, e2, blk.fc.weight, blk.fc.bias, h, act)
-            K.decode_gemm_acc(h, blk.fc2.weight, blk.fc2.bias, x)
-        wf, bf, ef = self.lnf
-        y, _, _ = norm_ops.ln_fwd(x, wf, bf, ef)
-        return self._linear(y, sp.head)
+            s.project(o.view(rows, C), blk.proj, pb)
+            h = s.norm_linear(ln2, blk.fc, gelu=True)  # a local: allocated until the next block's (_defer)
+            s.project(h, blk.fc2, fb)
+        return s.head(self.lnf, sp.head)
 
 
 def _packed_gate_up(mlp):
@@ -386,10 +375,13 @@ class GemmaDecodeProgram:
 
     The module forward runs ~16 kernels per block at decode shapes (four RMSNorms, two residual
     adds, separate gate and up GEMMs). Per block this runs 6 (+1 split-K combine): QKV GEMM with
-    RoPE (device-offset table) in its epilogue (``skinny_qkv_rope``) → decode attention with fused K/V append → O GEMM →
+    RoPE (device-offset table) in its epilogue → decode attention with fused K/V append → O GEMM →
     [residual add + post-attention norm + pre-MLP norm] → gate|up GEMM (one concatenated weight)
-    with the gated activation in its epilogue (``skinny_gated``) → down GEMM → [residual add +
-    post-MLP norm + the next block's input norm]. Rounding follows the module path (bf16 residual stream, torch's rounding
+    with the gated activation in its epilogue → down GEMM → [residual add + post-MLP norm + the
+    next block's input norm]. ``forward`` is one loop over those steps; ``_qkv``, ``_gate_up`` and
+    ``_lin`` pick each linear's kernel by the row count: the decode GEMVs for 1-4 rows, the skinny
+    MFMA kernels (``skinny_qkv_rope``, ``skinny_gated``) up to SKINNY_MAX_ROWS, decode_gemm /
+    hipBLASLt above. Rounding follows the module path (bf16 residual stream, torch's rounding
     points), so only the GEMM accumulation order of the fused gate|up projection can differ.
     Reference block semantics: ``neural_net_layers.py:188-225``.
     """
@@ -408,7 +400,7 @@ class GemmaDecodeProgram:
                 in_norm=in_norm, qkv=qkv.weight, attn=attn, o=o.weight, pre_mlp=pre_mlp, mode=mode,
                 post_attn=b.post_attn_norm, post_mlp=b.post_mlp_norm,
                 gu=_packed_gate_up(mlp), down=mlp.down_proj.weight,
-                kind=act_ops._GATED[mlp.act_kind], inter=mlp.gate_proj.out_features))
+                kind=act_ops._GATED[mlp.act_kind]))
 
     @staticmethod
     def build(model):
@@ -448,102 +440,68 @@ class GemmaDecodeProgram:
     def _gemv_ok(self, rows: int, C: int) -> bool:
         """Batch 1-4: every projection as one decode GEMV (decode_gemv / decode_gemv_pair:
         one wave per workgroup, one memory round trip; RoPE and the gated activation in the
-        paired-row epilogues)."""
+        paired-row epilogues). The residual adds + RMSNorms stay the rms_residual kernel: as the
+        GEMVs' prologue — every workgroup normalising the rows itself — it measured neutral
+        (Gemma-3 1B B=1 1.576 / 1.579 vs 1.571 / 1.571 ms, profiles/decode_r5.md)."""
         # decode_gemv reads K <= 8192 (decode_linear.hip); the O and down projections read K = H·D
         # and the intermediate size (12288 on Gemma-4 e2b's KV-shared double-wide MLPs)
         return (1 <= rows <= min(4, GEMV_MAX_ROWS) and C % 8 == 0 and C <= 1792 and _ext.available()
                 and all(b["o"].shape[1] <= GEMV_MAX_K and b["down"].shape[1] <= GEMV_MAX_K for b in self.blocks))
+
+    def _lin(self, x: Tensor, w: Tensor, gemv: bool) -> Tensor:
+        if gemv and w.shape[1] % 8 == 0 and w.shape[1] <= GEMV_MAX_K:
+            return gemm_ops.decode_gemv(x.contiguous(), w)
+        return _linear(x, w)
+
+    def _qkv(self, b, y: Tensor, cache, gemv: bool):
+        """This block's fused QKV rows, and the (cos, sin) the attention still has to apply to q and
+        the new key (None: already rotated, or a block without RoPE). Per block: layer lists may mix
+        head dims."""
+        a, rows = b["attn"], y.shape[0]
+        H, Hkv, D = a.num_heads, a.num_kv_heads, a.head_dim
+        if a.rope_theta is None:
+            return self._lin(y, b["qkv"], gemv), None
+        inv = a._inv_freq(D, y.device)
+        cos, sin = cache.rope_table((a.rope_theta, D), inv, 1)
+        if gemv and DECODE_EPILOGUES and D % 2 == 0:
+            return gemm_ops.decode_gemv_rope(y.contiguous(), b["qkv"], cos, sin, D, H + Hkv), None
+        if DECODE_EPILOGUES and rows <= SKINNY_MAX_ROWS and gemm_ops.skinny_qkv_rope_ok(y, b["qkv"], D):
+            return gemm_ops.skinny_qkv_rope(y, b["qkv"], cos, sin, D, H + Hkv), None
+        if getattr(cache, "rope_attend_ok", None) is not None and cache.rope_attend_ok(rows, H, Hkv, D):
+            # 17-64 rows: q and the new key rotated inside the decode attention kernel
+            return _linear(y, b["qkv"]), (cos, sin)
+        return rope_ops.apply_rope_qkv(_linear(y, b["qkv"]).view(rows, 1, -1), H, Hkv, D, inv, 0,
+                                       table=(cos, sin)), None
+
+    def _gate_up(self, b, y: Tensor, gemv: bool) -> Tensor:
+        if gemv and DECODE_EPILOGUES:
+            return gemm_ops.decode_gemv_gated(y.contiguous(), b["gu"], b["kind"])
+        return _gated(y, b["gu"], b["kind"])
 
     def forward(self, idx: Tensor, cache) -> Tensor:
         """idx [rows, 1] -> logits [rows, V] (bf16); appends this step's K/V at cache.pos_t."""
         K = _ext.kernels()
         rows = idx.shape[0]
         gemv = self._gemv_ok(rows, self.emb.embedding_dim)
-
-        def lin(x: Tensor, w: Tensor) -> Tensor:
-            if gemv and w.shape[1] % 8 == 0 and w.shape[1] <= GEMV_MAX_K:
-                out = torch.empty(rows, w.shape[0], device=x.device, dtype=torch.bfloat16)
-                K.decode_gemv(x.contiguous(), None, None, None, None, None, None, 0.0, w, None, out, 0)
-                return out
-            return _linear(x, w)
-
         x = torch.nn.functional.embedding(idx.view(rows), self.emb.weight) * self.emb.scale
         first = self.blocks[0]["in_norm"]
         y = K.rmsnorm_fwd(x, first.weight, first.eps)[0]
-        if gemv and DECODE_EPILOGUES and all(b["attn"].rope_theta is not None and b["attn"].head_dim % 2 == 0
-                                             for b in self.blocks):
-            return self._forward_gemv(K, rows, x, y, cache)
         for l, b in enumerate(self.blocks):
             a = b["attn"]
             H, Hkv, D = a.num_heads, a.num_kv_heads, a.head_dim
-            if a.rope_theta is not None:
-                inv = a._inv_freq(D, y.device)
-                cos, sin = cache.rope_table((a.rope_theta, D), inv, 1)
-                if gemv and DECODE_EPILOGUES and D % 2 == 0:
-                    qkv = torch.empty(rows, b["qkv"].shape[0], device=y.device, dtype=torch.bfloat16)
-                    K.decode_gemv_pair(y.contiguous(), b["qkv"], qkv, 2, 0, D, H + Hkv, cos, sin)
-                    qkv = qkv.view(rows, 1, -1)
-                elif DECODE_EPILOGUES and rows <= SKINNY_MAX_ROWS and gemm_ops.skinny_qkv_rope_ok(y, b["qkv"], D):
-                    qkv = gemm_ops.skinny_qkv_rope(y, b["qkv"], cos, sin, D, H + Hkv).view(rows, 1, -1)
-                elif getattr(cache, "rope_attend_ok", None) is not None and cache.rope_attend_ok(rows, H, Hkv, D):
-                    # 17-64 rows: q and the new key rotated inside the decode attention kernel
-                    qkv = _linear(y, b["qkv"]).view(rows, 1, -1)
-                    q, k, v = qkv.split([H * D, Hkv * D, Hkv * D], dim=2)
-                    att = cache.attend_rope(l, q.reshape(rows, 1, H, D), k.view(rows, 1, Hkv, D),
-                                            v.view(rows, 1, Hkv, D), cos, sin)
-                    qkv = None
-                else:
-                    qkv = rope_ops.apply_rope_qkv(_linear(y, b["qkv"]).view(rows, 1, -1), H, Hkv, D, inv, 0,
-                                                  table=(cos, sin))
-            else:
-                qkv = lin(y, b["qkv"]).view(rows, 1, -1)
-            if qkv is not None:
-                q, k, v = qkv.split([H * D, Hkv * D, Hkv * D], dim=2)
-                att = cache.attend(l, q.reshape(rows, 1, H, D), k.view(rows, 1, Hkv, D), v.view(rows, 1, Hkv, D))
-            o = lin(att.view(rows, H * D), b["o"])
+            qkv, rope = self._qkv(b, y, cache, gemv)
+            q, k, v = _qkv_views(qkv, H, Hkv, D)
+            att = cache.attend(l, q, k, v) if rope is None else cache.attend_rope(l, q, k, v, *rope)
+            o = self._lin(att.view(rows, H * D), b["o"], gemv)
             pa, pm, pre = b["post_attn"], b["post_mlp"], b["pre_mlp"]
             h, y = K.rms_residual(x, o, pa.weight if pa is not None else None, pre.weight, b["mode"],
                                   pa.eps if pa is not None else 0.0, pre.eps)
-            if gemv and DECODE_EPILOGUES:
-                g = torch.empty(rows, b["inter"], device=y.device, dtype=torch.bfloat16)
-                K.decode_gemv_pair(y.contiguous(), b["gu"], g, 1, b["kind"])
-            else:
-                g = _gated(y, b["gu"], b["kind"])
-            d = lin(g, b["down"])
+            g = self._gate_up(b, y, gemv)
+            d = self._lin(g, b["down"], gemv)
             nxt = self.blocks[l + 1]["in_norm"] if l + 1 < len(self.blocks) else self.norm_f
             x, y = K.rms_residual(h, d, pm.weight if pm is not None else None, nxt.weight, b["mode"],
                                   pm.eps if pm is not None else 0.0, nxt.eps)
-        return lin(y, self.head.weight)
-
-    def _forward_gemv(self, K, rows: int, x: Tensor, y: Tensor, cache) -> Tensor:
-        """Batch 1-4: QKV + RoPE, O, gate|up + activation, down and the lm_head as decode GEMVs (one
-        wave per workgroup, one memory round trip); the residual adds + RMSNorms stay the
-        rms_residual kernel (as the GEMVs' prologue — every workgroup normalising the rows itself —
-        it measured neutral: Gemma-3 1B B=1 1.576 / 1.579 vs 1.571 / 1.571 ms, profiles/decode_r5.md)."""
-        for l, b in enumerate(self.blocks):
-            a = b["attn"]
-            H, Hkv, D = a.num_heads, a.num_kv_heads, a.head_dim
-            cos, sin = cache.rope_table((a.rope_theta, D), a._inv_freq(D, x.device), 1)
-            qkv = torch.empty(rows, b["qkv"].shape[0], device=x.device, dtype=torch.bfloat16)
-            K.decode_gemv_pair(y.contiguous(), b["qkv"], qkv, 2, 0, D, H + Hkv, cos, sin)
-            qkv = qkv.view(rows, 1, -1)
-            q, k, v = qkv.split([H * D, Hkv * D, Hkv * D], dim=2)
-            att = cache.attend(l, q.reshape(rows, 1, H, D), k.view(rows, 1, Hkv, D), v.view(rows, 1, Hkv, D))
-            o = torch.empty(rows, b["o"].shape[0], device=x.device, dtype=torch.bfloat16)
-            K.decode_gemv(att.reshape(rows, H * D).contiguous(), None, None, None, None, None, None, 0.0, b["o"], None, o, 0)
-            pa, pm, pre = b["post_attn"], b["post_mlp"], b["pre_mlp"]
-            h, y = K.rms_residual(x, o, pa.weight if pa is not None else None, pre.weight, b["mode"],
-                                  pa.eps if pa is not None else 0.0, pre.eps)
-            g = torch.empty(rows, b["inter"], device=x.device, dtype=torch.bfloat16)
-            K.decode_gemv_pair(y, b["gu"], g, 1, b["kind"])
-            d = torch.empty(rows, b["down"].shape[0], device=x.device, dtype=torch.bfloat16)
-            K.decode_gemv(g, None, None, None, None, None, None, 0.0, b["down"], None, d, 0)
-            nxt = self.blocks[l + 1]["in_norm"] if l + 1 < len(self.blocks) else self.norm_f
-            x, y = K.rms_residual(h, d, pm.weight if pm is not None else None, nxt.weight, b["mode"],
-                                  pm.eps if pm is not None else 0.0, nxt.eps)
-        logits = torch.empty(rows, self.head.weight.shape[0], device=x.device, dtype=torch.bfloat16)
-        K.decode_gemv(y, None, None, None, None, None, None, 0.0, self.head.weight, None, logits, 0)
-        return logits
+        return self._lin(y, self.head.weight, gemv)
 
 
 # 17-32 rows: decode_linear.hip decode_gemm (16 rows × 16 columns per workgroup, K split over its
@@ -636,11 +594,13 @@ class GraphDecoder:
         self.out = torch.zeros(rows, capacity, dtype=torch.long, device=self.device)
         self.step_t = torch.zeros(1, dtype=torch.long, device=self.device)
         self.seed_t = torch.zeros(1, dtype=torch.long, device=self.device)  # per-run sampling salt
+        self.run_seed = 0  # set by begin()
         self.graph: torch.cuda.CUDAGraph | None = None
         gemm_ops.skinny_workspace(self.device)  # zeroed counters exist before any capture
         attn_ops.decode_counters(self.device)  # (the decode attention's split-merge counters too)
         gemm_ops.load_tuned_gemms()  # measured hipBLASLt solutions for the decode-shaped GEMMs too
         self.program = GPTDecodeProgram.build(model) or GemmaDecodeProgram.build(model)
+        self._done_t = torch.zeros(1, dtype=torch.int32, device=self.device)  # sample_step's arrival counter
 
     # ------------------------------------------------------------------ cache attachment
     def attach(self):
@@ -675,8 +635,6 @@ class GraphDecoder:
                 V = last.shape[-1]
                 k = 0 if self.top_k is None or self.top_k >= V else int(self.top_k)
                 if FUSED_ADVANCE:  # the sampler's last row advances the counters itself
-                    if getattr(self, "_done_t", None) is None:
-                        self._done_t = torch.zeros(1, dtype=torch.int32, device=last.device)
                     _ext.kernels().sample_step(last.contiguous(), self.temperature, k, self.seed_t, self.step_t,
                                                self.idx, self.out, self.cache.pos_t, self.cache.len_t, self._done_t)
                 else:
@@ -709,7 +667,7 @@ class GraphDecoder:
         self.run_seed = int(run_seed) & (2 ** 64 - 1)
 
     def _burst_seed(self, start: int) -> int:
-        v = (getattr(self, "run_seed", 0) + self._HASH_STEP * int(start)) & (2 ** 64 - 1)
+        v = (self.run_seed + self._HASH_STEP * int(start)) & (2 ** 64 - 1)
         return v - 2 ** 64 if v >= 2 ** 63 else v
 
     def _set_state(self, last_tok: Tensor, cache_len: int, start: int = 0):

@@ -230,6 +230,77 @@ def skinny_qkv_rope(x: Tensor, w: Tensor, cos: Tensor, sin: Tensor, D: int, nrot
     return out
 
 
+# ---- decode linears (csrc/kernels/decode_linear.hip, skinny_gemm.hip decode_ln_linear) -------
+# Keyword entry points of the decode programs' linears: each allocates its bf16 output and names
+# the prologue. ``ln`` = (gamma, beta, eps) with fp32 affine parameters; ``act`` 0 none, 1 GELU
+# (erf), 2 GELU (tanh). ``delta`` (bf16) / ``dbias`` (fp32) are added to the fp32 residual before
+# the norm and the sum is written to ``resid_out``.
+def _decode_out(x: Tensor, n: int) -> Tensor:
+    return torch.empty(x.shape[0], n, device=x.device, dtype=torch.bfloat16)
+
+
+def decode_gemv(x: Tensor, w: Tensor, bias: Tensor | None = None, act: int = 0) -> Tensor:
+    """act(x·wᵀ + bias) for 1-4 bf16 rows: one wave per workgroup, one memory round trip."""
+    out = _decode_out(x, w.shape[0])
+    kernels().decode_gemv(x=x, resid_in=None, delta=None, dbias=None, resid_out=None, gamma=None, beta=None,
+                          eps=0.0, w=w, bias=bias, out=out, act=act)
+    return out
+
+
+def decode_gemv_ln(resid: Tensor, ln, w: Tensor, bias: Tensor | None, act: int = 0, delta: Tensor | None = None,
+                   dbias: Tensor | None = None, resid_out: Tensor | None = None) -> Tensor:
+    """``decode_gemv`` with the residual add + LayerNorm as its prologue:
+    act(LN(resid + delta + dbias)·wᵀ + bias)."""
+    out = _decode_out(resid, w.shape[0])
+    kernels().decode_gemv(x=None, resid_in=resid, delta=delta, dbias=dbias, resid_out=resid_out, gamma=ln[0],
+                          beta=ln[1], eps=ln[2], w=w, bias=bias, out=out, act=act)
+    return out
+
+
+def decode_gemv_emb(idx: Tensor, pos: Tensor, wte: Tensor, wpe: Tensor, resid_out: Tensor, ln, w: Tensor,
+                    bias: Tensor | None, act: int = 0) -> Tensor:
+    """``decode_gemv`` with the embedding gather + LayerNorm as its prologue:
+    act(LN(wte[idx] + wpe[pos])·wᵀ + bias), the fp32 embedding rows written to ``resid_out``; ``pos``
+    is the device position."""
+    out = _decode_out(resid_out, w.shape[0])
+    kernels().decode_gemv(x=None, resid_in=None, delta=None, dbias=None, resid_out=resid_out, gamma=ln[0],
+                          beta=ln[1], eps=ln[2], w=w, bias=bias, out=out, act=act, emb_idx=idx, emb_wte=wte,
+                          emb_wpe=wpe, emb_pos=pos)
+    return out
+
+
+def decode_gemv_gated(x: Tensor, gu: Tensor, kind: int) -> Tensor:
+    """Paired-row decode GEMV of the packed [gate; up] weight, 1-4 rows: act(x·Wgᵀ) ⊙ (x·Wuᵀ)."""
+    out = _decode_out(x, gu.shape[0] // 2)
+    kernels().decode_gemv_pair(x=x, w=gu, out=out, mode=1, kind=kind)
+    return out
+
+
+def decode_gemv_rope(x: Tensor, w: Tensor, cos: Tensor, sin: Tensor, D: int, nrot: int) -> Tensor:
+    """Paired-row decode GEMV of the QKV weight, 1-4 rows, with RoPE (one position's cos / sin)
+    applied to the first ``nrot`` heads of size ``D`` in its epilogue."""
+    out = _decode_out(x, w.shape[0])
+    kernels().decode_gemv_pair(x=x, w=w, out=out, mode=2, kind=0, D=D, nrot=nrot, cos=cos, sin=sin)
+    return out
+
+
+def decode_ln_linear(resid: Tensor, ln, w: Tensor, bias: Tensor | None, act: int = 0, delta: Tensor | None = None,
+                     dbias: Tensor | None = None, resid_out: Tensor | None = None) -> Tensor:
+    """act(LN(resid + delta + dbias)·wᵀ + bias) for ≤ 64 rows, K ≤ 1024 on the skinny MFMA kernel:
+    every workgroup normalises all rows itself."""
+    out = _decode_out(resid, w.shape[0])
+    kernels().decode_ln_linear(resid_in=resid, delta=delta, dbias=dbias, resid_out=resid_out, gamma=ln[0],
+                               beta=ln[1], eps=ln[2], w=w, bias=bias, out=out, act=act)
+    return out
+
+
+def decode_ln_gemm(resid: Tensor, ln, w: Tensor, bias: Tensor | None, act: int = 0) -> Tensor:
+    """Batched decode: act(LN(resid)·wᵀ + bias), the LayerNorm recomputed per 16-row block."""
+    out = _decode_out(resid, w.shape[0])
+    kernels().decode_ln_gemm(resid=resid, gamma=ln[0], beta=ln[1], eps=ln[2], w=w, bias=bias, out=out, act=act)
+    return out
+
+
 class decode_gemms:
     """Context: the ``nn.Linear`` modules of ``model`` run decode-shaped inputs through the skinny
     kernel (others keep ``F.linear``). Entered by the graph decoder around the captured step of a

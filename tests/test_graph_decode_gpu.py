@@ -100,10 +100,7 @@ def test_decode_program_graph_replay_matches_eager_program(monkeypatch, rows):
     assert graphed == eager
 
 
-@pytest.mark.parametrize("rows", [1, 3, 6, 24, 64])
-def test_decode_program_step_matches_module_step(rows):
-    """One decode-program step vs the module forward: rows 1 and 3 run the decode GEMV path, 6 the
-    fused LN-linear path, 24 and 64 the batched block (decode_ln_gemm / decode_gemm_acc)."""
+def _gpt_program_step_vs_module_step(rows):
     m = _model(torch.bfloat16)
     cap = 32
     dec = gd.GraphDecoder(m, rows, cap, 0.0, None)
@@ -127,6 +124,24 @@ def test_decode_program_step_matches_module_step(rows):
             dec.detach()
     rel = (got - ref).norm() / ref.norm()
     assert rel < 2e-2, rel
+
+
+@pytest.mark.parametrize("rows", [1, 3, 6, 24, 64])
+def test_decode_program_step_matches_module_step(rows):
+    """One decode-program step vs the module forward: rows 1 and 3 run the decode GEMV path, 6 the
+    fused LN-linear path, 24 and 64 the batched block (decode_ln_gemm / decode_gemm_acc)."""
+    _gpt_program_step_vs_module_step(rows)
+
+
+@pytest.mark.parametrize("rows", [3, 6, 24])
+def test_plain_decode_program_step_matches_module_step(monkeypatch, rows):
+    """The same with the GEMV, fused and batched regimes switched off: the plain add+LN / GEMM / GELU
+    kernels (the path of any GPT with C > 1024 or C % 32 != 0), skinny GEMMs at 3 and 6 rows,
+    hipBLASLt at 24."""
+    monkeypatch.setattr(gd, "FUSED_LN_LINEAR", False)
+    monkeypatch.setattr(gd, "BATCHED_BLOCK", False)
+    monkeypatch.setattr(gd, "GEMV_MAX_ROWS", 0)
+    _gpt_program_step_vs_module_step(rows)
 
 
 def _gemma_model(head_dim, model_type="gemma3_text", intermediate_size=128):
@@ -162,6 +177,19 @@ def test_rope_model_graph_decode_matches_eager(monkeypatch, head_dim):
 # inside the decode attention kernel (the opt-in PENROZ_DECODE_ROPE_IN_ATTN=1) or by the RoPE pass
 @pytest.mark.parametrize("rows,rope_in_attn", [(1, "0"), (3, "0"), (8, "0"), (24, "0"), (24, "1"), (64, "1")])
 def test_gemma_program_step_matches_module_step(monkeypatch, model_type, rows, rope_in_attn):
+    _gemma_program_step_vs_module_step(monkeypatch, model_type, rows, rope_in_attn)
+
+
+@pytest.mark.parametrize("model_type", ["gemma", "gemma2", "gemma3_text"])
+@pytest.mark.parametrize("rows", [3, 8])
+def test_gemma_program_step_without_epilogues_matches_module_step(monkeypatch, model_type, rows):
+    """DECODE_EPILOGUES off: plain QKV linear + the RoPE pass, and gate|up GEMM + the packed gated
+    activation, around the decode GEMVs (3 rows) or the skinny GEMMs (8 rows)."""
+    monkeypatch.setattr(gd, "DECODE_EPILOGUES", False)
+    _gemma_program_step_vs_module_step(monkeypatch, model_type, rows, "0")
+
+
+def _gemma_program_step_vs_module_step(monkeypatch, model_type, rows, rope_in_attn):
     monkeypatch.setenv("PENROZ_DECODE_ROPE_IN_ATTN", rope_in_attn)
     m = _gemma_model(256, model_type)
     cap = 32
