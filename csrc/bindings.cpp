@@ -1,6 +1,7 @@
 // Python bindings for the penroz CDNA4 kernels (module ``penroz_kernels``).
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
+#include <tuple>
 #include <vector>
 
 // layernorm.hip
@@ -34,6 +35,7 @@ void gemma_combine_bwd(int64_t mode, torch::Tensor dy, c10::optional<torch::Tens
                        c10::optional<torch::Tensor> r1, torch::Tensor r2, c10::optional<torch::Tensor> w1,
                        torch::Tensor w2, torch::Tensor dx, c10::optional<torch::Tensor> da,
                        c10::optional<torch::Tensor> dw1, torch::Tensor dw2, c10::optional<torch::Tensor> dh_save);
+// elementwise.hip
 void transpose_bf16(torch::Tensor in, torch::Tensor out);
 void embedding_fwd(torch::Tensor idx, torch::Tensor wte, torch::Tensor wpe, int64_t off, torch::Tensor out,
                    c10::optional<torch::Tensor> off_dev, double dropout_p, int64_t dropout_seed);
@@ -82,8 +84,6 @@ int64_t skinny_gemm(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tenso
                     torch::Tensor ws, torch::Tensor cnt, int64_t splitk);
 void skinny_gated(torch::Tensor x, torch::Tensor gu, torch::Tensor out, int64_t kind);
 std::vector<int64_t> skinny_qkv_rope_plan(int64_t M, int64_t N, int64_t K);
-std::vector<int64_t> attn_work_plan(int64_t nblk, int64_t nvh, int64_t slots, int64_t BM, int64_t BN, int64_t T,
-                                    int64_t D, double tile_us);
 int64_t skinny_qkv_rope(torch::Tensor x, torch::Tensor w, torch::Tensor cosv, torch::Tensor sinv, int64_t D,
                         int64_t nrot, torch::Tensor out, torch::Tensor ws, torch::Tensor cnt, int64_t splitk);
 void decode_ln_linear(torch::Tensor rin, c10::optional<torch::Tensor> delta, c10::optional<torch::Tensor> dbias,
@@ -104,6 +104,8 @@ void decode_gemv_pair(torch::Tensor x, torch::Tensor w, torch::Tensor out, int64
 void decode_gemm_acc(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor resid,
                      int64_t flags);
 void decode_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor out, int64_t kind);
+std::tuple<int64_t, int64_t, int64_t, int64_t> decode_gemv_limits();
+// adamw.hip
 torch::Tensor update_moments(std::vector<torch::Tensor> ws, std::vector<torch::Tensor> ps);
 // gemm_nt.hip
 bool gemm_nt_supported(int64_t M, int64_t N, int64_t K);
@@ -125,6 +127,8 @@ void flash_attn_gen_fwd(torch::Tensor qkv, torch::Tensor out, torch::Tensor lse,
 void flash_attn_gen_bwd(torch::Tensor dout, torch::Tensor qkv, torch::Tensor out, torch::Tensor lse,
                         torch::Tensor dqkv, int64_t H, int64_t Hkv, int64_t D, double scale, double p_drop,
                         int64_t seed);
+std::vector<int64_t> attn_work_plan(int64_t nblk, int64_t nvh, int64_t slots, int64_t BM, int64_t BN, int64_t T,
+                                    int64_t D, double tile_us);
 
 // A stream whose kernels may only run on the CUs set in `mask` (32-bit words, CU i = bit i % 32
 // of word i / 32): the executor's side stream can be confined to a CU subset so the critical-path
@@ -256,6 +260,8 @@ PYBIND11_MODULE(penroz_kernels, m) {
   m.def("decode_gemm", &decode_gemm, pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("out"),
         pybind11::arg("kind") = -1,
         "batched decode (16-64 rows): out = x·wᵀ, or the gated MLP act(x·Wgᵀ)·(x·Wuᵀ) of a packed [gate; up] weight");
+  m.def("decode_gemv_limits", &decode_gemv_limits,
+        "(rows, K, LN-mode K, paired-row K) limits of decode_gemv / decode_gemv_pair (host only)");
   m.def("update_moments", &update_moments, "per-epoch weight-update diagnostics: [n, 2] (std(w - prev), std(w))");
   m.def("gemm_nt_supported", &gemm_nt_supported, "shapes the native NT GEMM takes (M % 256, N % 128, K % 32, K >= 160)");
   m.def("gemm_nt", &gemm_nt, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("bias"), pybind11::arg("out"),

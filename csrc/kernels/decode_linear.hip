@@ -24,7 +24,9 @@
 // (decode rows m): lane holds D[n = 4(lane>>4) + r][m = lane & 15], r = 0..3 — four
 // consecutive outputs of one row, stored as 8 B (bf16) or RMW'd as 16 B (fp32).
 #include "common.h"
-#include <type_traits>
+#include "host_plan.h"
+#include "launch_args.h"
+#include <tuple>
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -597,18 +599,10 @@ __global__ void __launch_bounds__(64) decode_gemv_kernel(
 
 using namespace penroz;
 
-static void dl_check_w(const torch::Tensor& w, int K, const char* who) {
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.dim() == 2 && w.is_contiguous() &&
-                  w.size(1) == K && w.size(0) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-              who, ": bf16 contiguous 16-B aligned W [N, K], N % 16 == 0");
-}
-
-static const bf16* dl_bias(const c10::optional<torch::Tensor>& bias, int N, const char* who) {
-  if (!bias.has_value() || !bias->defined()) return nullptr;
-  TORCH_CHECK(bias->scalar_type() == torch::kBFloat16 && bias->is_contiguous() && bias->numel() == N &&
-                  reinterpret_cast<uintptr_t>(bias->data_ptr()) % 8 == 0,
-              who, ": bf16 bias [N], 8-B aligned");
-  return reinterpret_cast<const bf16*>(bias->data_ptr());
+// Environment switches, read once per process and handed to the launch plans (host_plan.h)
+static bool env_starts_with(const char* name, char c) {
+  const char* e = std::getenv(name);
+  return e && e[0] == c;
 }
 
 // out[M, N] = act(LayerNorm(resid) · wᵀ + bias); act 0 none, 1 GELU (erf), 2 GELU (tanh).
@@ -616,87 +610,71 @@ static const bf16* dl_bias(const c10::optional<torch::Tensor>& bias, int N, cons
 // 4 no stores, 8 no LayerNorm (LDS image unwritten), 16 no MFMA
 void decode_ln_gemm(torch::Tensor resid, torch::Tensor gamma, torch::Tensor beta, double eps, torch::Tensor w,
                     c10::optional<torch::Tensor> bias, torch::Tensor out, int64_t act, int64_t flags) {
-  TORCH_CHECK(resid.is_cuda() && resid.scalar_type() == torch::kFloat32 && resid.dim() == 2 && resid.is_contiguous(),
-              "decode_ln_gemm: fp32 contiguous resid [M, K]");
-  const int M = resid.size(0), K = resid.size(1);
-  TORCH_CHECK(M >= 1 && K % 32 == 0 && K <= 32 * kDlMaxSteps, "decode_ln_gemm: K % 32 == 0, K <= 1024");
-  dl_check_w(w, K, "decode_ln_gemm");
-  const int N = w.size(0);
-  TORCH_CHECK(gamma.scalar_type() == torch::kFloat32 && beta.scalar_type() == torch::kFloat32 && gamma.numel() == K &&
-                  beta.numel() == K && gamma.is_contiguous() && beta.is_contiguous(),
-              "decode_ln_gemm: fp32 gamma / beta [K]");
-  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 && out.dim() == 2 && out.size(0) == M && out.size(1) == N &&
-                  out.stride(1) == 1 && out.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
-              "decode_ln_gemm: bf16 out [M, N], rows 8-B aligned");
-  TORCH_CHECK(act >= 0 && act <= 2, "decode_ln_gemm: act 0 (none), 1 (GELU erf), 2 (GELU tanh)");
-  const bf16* bp = dl_bias(bias, N, "decode_ln_gemm");
-  // K halves (KS = 2) by default: GPT-2 decode B = 16 / 32 / 64 0.567 / 0.584 / 0.636 -> 0.532 /
-  // 0.550 / 0.620 ms/step; quarters (KS = 4) lost: 0.55 / 0.74 / 0.96 — every workgroup repeats the
-  // LayerNorm of its 16 rows (profiles/decode_r5.md). PENROZ_DECODE_LN_KSPLIT=1: 64-column tiles.
-  static const int ks_env = [] {
-    const char* e = std::getenv("PENROZ_DECODE_LN_KSPLIT");
-    return e && e[0] == '1' ? 1 : 2;
-  }();
-  const int ks = ks_env == 2 && (K / 32) % 2 == 0 ? 2 : 1;
-  const int tw = 64 / ks;
-  const int grid = ((M + 15) / 16) * ((N + tw - 1) / tw);
-  hipLaunchKernelGGL(ks == 2 ? decode_ln_gemm_kernel<2> : decode_ln_gemm_kernel<1>,
-                     dim3(grid), dim3(256), 0, at::hip::getCurrentHIPStream(), resid.data_ptr<float>(), gamma.data_ptr<float>(),
-                     beta.data_ptr<float>(), (float)eps, reinterpret_cast<const bf16*>(w.data_ptr()), bp,
-                     reinterpret_cast<bf16*>(out.data_ptr()), (int64_t)out.stride(0), M, N, K, (int)act, (int)flags);
+  const char* who = "decode_ln_gemm";
+  static_assert(32 * kDlMaxSteps == kLnMaxK, "the kernel's k-step limit is the LN-mode K limit");
+  const bf16* wp = la_weight(who, w, 16);
+  const int N = w.size(0), K = w.size(1);
+  const float* rp = la_f32_mat(who, "resid", resid, -1, K);
+  const int M = resid.size(0);
+  TORCH_CHECK(M >= 1 && K % 32 == 0 && K <= kLnMaxK, who, ": K % 32 == 0, K <= ", kLnMaxK);
+  const float *gp = la_f32_vec(who, "gamma", gamma, K), *bt = la_f32_vec(who, "beta", beta, K);
+  bf16* op = la_out(who, out, M, N, 8);
+  TORCH_CHECK(act >= 0 && act <= 2, who, ": act 0 (none), 1 (GELU erf), 2 (GELU tanh)");
+  const bf16* bp = la_bias(who, bias, N, 8);
+  static const int ks_env = env_starts_with("PENROZ_DECODE_LN_KSPLIT", '1') ? 1 : 2;
+  const GridPlan p = plan_decode_ln_gemm(M, N, K, ks_env);
+  hipLaunchKernelGGL(p.v == 2 ? decode_ln_gemm_kernel<2> : decode_ln_gemm_kernel<1>, dim3(p.grid), dim3(256), 0,
+                     at::hip::getCurrentHIPStream(), rp, gp, bt, (float)eps, wp, bp, op, (int64_t)out.stride(0), M, N, K,
+                     (int)act, (int)flags);
 }
 
 // resid[M, N] += x · wᵀ + bias (fp32 residual, in place). flags: timing ablations (1 no x reads,
 // 2 no weight reads, 4 no stores)
 void decode_gemm_acc(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor resid,
                      int64_t flags) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 2 && x.stride(1) == 1 &&
-                  x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "decode_gemm_acc: bf16 x [M, K], rows 16-B aligned");
-  const int M = x.size(0), K = x.size(1);
-  TORCH_CHECK(M >= 1 && K % 32 == 0, "decode_gemm_acc: K % 32 == 0");
-  dl_check_w(w, K, "decode_gemm_acc");
-  const int N = w.size(0);
-  TORCH_CHECK(resid.scalar_type() == torch::kFloat32 && resid.is_contiguous() && resid.dim() == 2 &&
-                  resid.size(0) == M && resid.size(1) == N,
-              "decode_gemm_acc: fp32 contiguous resid [M, N]");
-  const bf16* bp = dl_bias(bias, N, "decode_gemm_acc");
+  const char* who = "decode_gemm_acc";
+  const bf16* wp = la_weight(who, w, 16);
+  const int N = w.size(0), K = w.size(1);
+  const bf16* xp = la_rows(who, x, K);
+  const int M = x.size(0);
+  TORCH_CHECK(M >= 1 && K % 32 == 0, who, ": K % 32 == 0");
+  float* rp = la_f32_mat(who, "resid", resid, M, N);
+  const bf16* bp = la_bias(who, bias, N, 8);
   const int grid = ((M + 15) / 16) * (N / 16);
-  hipLaunchKernelGGL(decode_gemm_acc_kernel, dim3(grid), dim3(256), 0, at::hip::getCurrentHIPStream(),
-                     reinterpret_cast<const bf16*>(x.data_ptr()), (int64_t)x.stride(0),
-                     reinterpret_cast<const bf16*>(w.data_ptr()), bp, resid.data_ptr<float>(), M, N, K, (int)flags);
+  hipLaunchKernelGGL(decode_gemm_acc_kernel, dim3(grid), dim3(256), 0, at::hip::getCurrentHIPStream(), xp,
+                     (int64_t)x.stride(0), wp, bp, rp, M, N, K, (int)flags);
 }
 
 // out[M, N] = x · Wᵀ (kind < 0), or with the packed [gate; up] weight [2I, K] out[M, I] =
 // act(x·Wgᵀ) ⊙ (x·Wuᵀ) (kind 0 gelu, 1 gelu_tanh, 2 silu) — decode_gemm_kernel
 void decode_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor out, int64_t kind) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 2 && x.stride(1) == 1 &&
-                  x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "decode_gemm: bf16 x [M, K], rows 16-B aligned");
-  const int M = x.size(0), K = x.size(1);
-  TORCH_CHECK(M >= 1 && K % 32 == 0, "decode_gemm: K % 32 == 0");
-  dl_check_w(w, K, "decode_gemm");
+  const char* who = "decode_gemm";
+  const bf16* wp = la_weight(who, w, 16);
+  const int K = w.size(1);
+  const bf16* xp = la_rows(who, x, K);
+  const int M = x.size(0);
+  TORCH_CHECK(M >= 1 && K % 32 == 0, who, ": K % 32 == 0");
   const bool gated = kind >= 0;
-  TORCH_CHECK(kind <= 2, "decode_gemm: kind -1 (plain), 0 gelu, 1 gelu_tanh, 2 silu");
+  TORCH_CHECK(kind <= 2, who, ": kind -1 (plain), 0 gelu, 1 gelu_tanh, 2 silu");
   const int N = gated ? w.size(0) / 2 : w.size(0);
-  TORCH_CHECK(N % 16 == 0 && (!gated || w.size(0) == 2 * N), "decode_gemm: N (gated: I) % 16 == 0");
-  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 && out.dim() == 2 && out.size(0) == M && out.size(1) == N &&
-                  out.stride(1) == 1 && out.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
-              "decode_gemm: bf16 out [M, N], rows 8-B aligned");
-  // 4 row blocks per workgroup once there are more than two and the columns alone give >= 256
-  // workgroups (weights read once); otherwise one row block per workgroup (more workgroups)
-  const int rb = (M > 32 && N / 16 >= 256) ? 4 : 1;
-  const int grid = ((M + 16 * rb - 1) / (16 * rb)) * (N / 16);
-  auto kern = gated ? (rb == 4 ? decode_gemm_kernel<true, 4> : decode_gemm_kernel<true, 1>)
-                    : (rb == 4 ? decode_gemm_kernel<false, 4> : decode_gemm_kernel<false, 1>);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, at::hip::getCurrentHIPStream(),
-                     reinterpret_cast<const bf16*>(x.data_ptr()), (int64_t)x.stride(0),
-                     reinterpret_cast<const bf16*>(w.data_ptr()), reinterpret_cast<bf16*>(out.data_ptr()),
+  TORCH_CHECK(N % 16 == 0 && (!gated || w.size(0) == 2 * N), who, ": N (gated: I) % 16 == 0");
+  bf16* op = la_out(who, out, M, N, 8);
+  const GridPlan p = plan_decode_gemm(M, N);
+  auto kern = gated ? (p.v == 4 ? decode_gemm_kernel<true, 4> : decode_gemm_kernel<true, 1>)
+                    : (p.v == 4 ? decode_gemm_kernel<false, 4> : decode_gemm_kernel<false, 1>);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), 0, at::hip::getCurrentHIPStream(), xp, (int64_t)x.stride(0), wp, op,
                      (int64_t)out.stride(0), M, N, K, (int)(gated ? kind : 0));
 }
 
+// (rows, K, LN-mode K, paired-row K) the two GEMV launchers below accept at most: the Python
+// admission checks (models/graph_decode.py) read them here instead of repeating them
+std::tuple<int64_t, int64_t, int64_t, int64_t> decode_gemv_limits() {
+  return {kGemvMaxRows, kGemvMaxK, kLnMaxK, kGemvPairMaxK};
+}
+
 // out[M, N] = act(x · Wᵀ + bias) for M <= 4 decode rows (decode_gemv_kernel). LN mode (x
-// undefined): x = LayerNorm(resid_in + delta + dbias) with γ / β, resid_out receives the sum.
+// undefined): x = LayerNorm(resid_in + delta + dbias) with γ / β, resid_out receives the sum; with
+// emb_wte, LayerNorm(wte[idx] + wpe[pos]) and resid_out receives the embedding rows.
 // act 0 none, 1 GELU (erf), 2 GELU (tanh). rows_per_wave 2, 4 or 8 (0: by N).
 void decode_gemv(c10::optional<torch::Tensor> x, c10::optional<torch::Tensor> rin, c10::optional<torch::Tensor> delta,
                  c10::optional<torch::Tensor> dbias, c10::optional<torch::Tensor> rout,
@@ -704,183 +682,76 @@ void decode_gemv(c10::optional<torch::Tensor> x, c10::optional<torch::Tensor> ri
                  c10::optional<torch::Tensor> bias, torch::Tensor out, int64_t act, int64_t rows_per_wave,
                  c10::optional<torch::Tensor> emb_idx, c10::optional<torch::Tensor> emb_wte,
                  c10::optional<torch::Tensor> emb_wpe, c10::optional<torch::Tensor> emb_pos) {
-  const bool ln = !(x.has_value() && x->defined());
-  const bool emb = emb_wte.has_value() && emb_wte->defined();
-  const int64_t* eip = nullptr;
-  const bf16 *ewp = nullptr, *epp = nullptr;
-  const int64_t* eps_p = nullptr;
-  int eV = 0, eP = 0;
+  const char* who = "decode_gemv";
+  const bool ln = !la_defined(x);
+  const bf16* wp = la_weight(who, w);
   const int N = w.size(0), K = w.size(1);
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.dim() == 2 && w.is_contiguous() &&
-                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 && K % 8 == 0,
-              "decode_gemv: bf16 contiguous 16-B aligned W [N, K], K % 8 == 0");
-  TORCH_CHECK(K <= 256 * 32, "decode_gemv: K <= 8192");
-  TORCH_CHECK(act >= 0 && act <= 2, "decode_gemv: act 0 (none), 1 (GELU erf), 2 (GELU tanh)");
+  TORCH_CHECK(K % 8 == 0 && K <= kGemvMaxK, who, ": K % 8 == 0, K <= ", kGemvMaxK);
+  TORCH_CHECK(act >= 0 && act <= 2, who, ": act 0 (none), 1 (GELU erf), 2 (GELU tanh)");
   int M;
   const bf16* xp = nullptr;
   int64_t x_rs = 0;
-  const float *rp = nullptr, *dbp = nullptr, *gp = nullptr, *bt = nullptr;
-  const bf16* dp = nullptr;
-  float* rop = nullptr;
+  ResidArgs r;
+  const float *gp = nullptr, *bt = nullptr;
+  const int64_t *eip = nullptr, *eps_p = nullptr;
+  const bf16 *ewp = nullptr, *epp = nullptr;
+  int eV = 0, eP = 0;
   if (!ln) {
-    TORCH_CHECK(x->scalar_type() == torch::kBFloat16 && x->dim() == 2 && x->size(1) == K && x->stride(1) == 1 &&
-                    x->stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x->data_ptr()) % 16 == 0,
-                "decode_gemv: bf16 x [M, K], rows 16-B aligned");
+    xp = la_rows(who, *x, K);
     M = x->size(0);
-    xp = reinterpret_cast<const bf16*>(x->data_ptr());
     x_rs = x->stride(0);
-  } else if (emb) {  // LN mode on the step's embedding rows; resid_out receives them
-    TORCH_CHECK(emb_idx.has_value() && emb_wpe.has_value() && emb_pos.has_value(), "decode_gemv: embedding mode needs idx / wpe / pos");
-    TORCH_CHECK(emb_idx->is_cuda() && emb_idx->scalar_type() == torch::kInt64 && emb_idx->is_contiguous(),
-                "decode_gemv: int64 token ids");
-    for (const torch::Tensor* t : {&*emb_wte, &*emb_wpe})
-      TORCH_CHECK(t->scalar_type() == torch::kBFloat16 && t->dim() == 2 && t->is_contiguous() && t->size(1) == K &&
-                      reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "decode_gemv: bf16 contiguous wte / wpe [*, K]");
-    TORCH_CHECK(emb_pos->is_cuda() && emb_pos->scalar_type() == torch::kInt64 && emb_pos->numel() == 1, "decode_gemv: int64 pos [1]");
-    TORCH_CHECK(K <= 1024, "decode_gemv: LN mode needs K <= 1024");
-    TORCH_CHECK(gamma.has_value() && beta.has_value() && gamma->scalar_type() == torch::kFloat32 &&
-                    beta->scalar_type() == torch::kFloat32 && gamma->numel() == K && beta->numel() == K &&
-                    gamma->is_contiguous() && beta->is_contiguous(), "decode_gemv: fp32 gamma / beta [K]");
-    M = emb_idx->numel();
-    TORCH_CHECK(rout.has_value() && rout->defined() && rout->scalar_type() == torch::kFloat32 && rout->is_contiguous() &&
-                    rout->numel() == (int64_t)M * K, "decode_gemv: fp32 resid_out [M, K] for the embedding rows");
-    rop = rout->data_ptr<float>();
-    gp = gamma->data_ptr<float>();
-    bt = beta->data_ptr<float>();
-    eip = emb_idx->data_ptr<int64_t>();
-    ewp = reinterpret_cast<const bf16*>(emb_wte->data_ptr());
-    epp = reinterpret_cast<const bf16*>(emb_wpe->data_ptr());
-    eps_p = emb_pos->data_ptr<int64_t>();
-    eV = (int)emb_wte->size(0);
-    eP = (int)emb_wpe->size(0);
   } else {
-    TORCH_CHECK(rin.has_value() && rin->defined() && rin->scalar_type() == torch::kFloat32 && rin->dim() == 2 &&
-                    rin->is_contiguous() && rin->size(1) == K, "decode_gemv: fp32 contiguous resid_in [M, K]");
-    TORCH_CHECK(K <= 1024, "decode_gemv: LN mode needs K <= 1024");
-    TORCH_CHECK(gamma.has_value() && beta.has_value() && gamma->scalar_type() == torch::kFloat32 &&
-                    beta->scalar_type() == torch::kFloat32 && gamma->numel() == K && beta->numel() == K &&
-                    gamma->is_contiguous() && beta->is_contiguous(), "decode_gemv: fp32 gamma / beta [K]");
-    M = rin->size(0);
-    rp = rin->data_ptr<float>();
-    gp = gamma->data_ptr<float>();
-    bt = beta->data_ptr<float>();
-    if (delta.has_value() && delta->defined()) {
-      TORCH_CHECK(delta->scalar_type() == torch::kBFloat16 && delta->is_contiguous() && delta->numel() == (int64_t)M * K,
-                  "decode_gemv: bf16 contiguous delta [M, K]");
-      TORCH_CHECK(rout.has_value() && rout->defined() && rout->scalar_type() == torch::kFloat32 &&
-                      rout->is_contiguous() && rout->numel() == (int64_t)M * K && rout->data_ptr() != rin->data_ptr(),
-                  "decode_gemv: fp32 resid_out [M, K] (not aliasing resid_in) with a delta");
-      dp = reinterpret_cast<const bf16*>(delta->data_ptr());
-      rop = rout->data_ptr<float>();
-      if (dbias.has_value() && dbias->defined()) {
-        TORCH_CHECK(dbias->scalar_type() == torch::kFloat32 && dbias->is_contiguous() && dbias->numel() == K,
-                    "decode_gemv: fp32 dbias [K]");
-        dbp = dbias->data_ptr<float>();
-      }
+    TORCH_CHECK(K <= kLnMaxK, who, ": LN mode needs K <= ", kLnMaxK);
+    gp = la_f32_vec(who, "gamma", gamma, K);
+    bt = la_f32_vec(who, "beta", beta, K);
+    if (la_defined(emb_wte)) {  // LN mode on the step's embedding rows; resid_out receives them
+      TORCH_CHECK(la_defined(emb_idx) && la_defined(emb_wpe) && la_defined(emb_pos), who,
+                  ": embedding mode needs idx / wpe / pos");
+      TORCH_CHECK(emb_idx->is_cuda() && emb_idx->scalar_type() == torch::kInt64 && emb_idx->is_contiguous(), who,
+                  ": int64 token ids");
+      TORCH_CHECK(emb_pos->is_cuda() && emb_pos->scalar_type() == torch::kInt64 && emb_pos->numel() == 1, who,
+                  ": int64 pos [1]");
+      ewp = la_weight(who, *emb_wte);
+      epp = la_weight(who, *emb_wpe);
+      TORCH_CHECK(emb_wte->size(1) == K && emb_wpe->size(1) == K, who, ": wte / wpe [*, K]");
+      M = emb_idx->numel();
+      TORCH_CHECK(la_defined(rout) && rout->is_cuda() && rout->scalar_type() == torch::kFloat32 && rout->is_contiguous() &&
+                      rout->numel() == (int64_t)M * K, who, ": fp32 resid_out [M, K] for the embedding rows");
+      r.rout = rout->data_ptr<float>();
+      eip = emb_idx->data_ptr<int64_t>();
+      eps_p = emb_pos->data_ptr<int64_t>();
+      eV = (int)emb_wte->size(0);
+      eP = (int)emb_wpe->size(0);
+    } else {
+      r = la_resid(who, rin, delta, dbias, rout, K, true);
+      M = r.M;
     }
   }
-  TORCH_CHECK(M >= 1 && M <= 4, "decode_gemv: 1..4 rows");
-  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 && out.dim() == 2 && out.size(0) == M && out.size(1) == N &&
-                  out.stride(1) == 1, "decode_gemv: bf16 out [M, N]");
-  const bf16* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->scalar_type() == torch::kBFloat16 && bias->is_contiguous() && bias->numel() == N,
-                "decode_gemv: bf16 bias [N]");
-    bp = reinterpret_cast<const bf16*>(bias->data_ptr());
-  }
-  const int cpl = (K / 8 + 31) / 32;
-  int rpw = (int)rows_per_wave;
-  // by shape: the vocabulary projection wants fewer, longer-lived waves (8 rows); everything else
-  // 2 rows per wave — the most workgroups in flight. In the replayed step that beat 4 rows for the
-  // wider QKV / fc outputs, which the isolated microbench preferred (GPT-2 B = 1 0.3594 / 0.3608 ->
-  // 0.3563 / 0.3547 ms, Gemma-3 1B neutral; profiles/decode_r5.md). PENROZ_DECODE_GEMV_RPW forces 2 /
-  // 4 / 8 below 16k rows (A/B).
+  TORCH_CHECK(M >= 1 && M <= kGemvMaxRows, who, ": 1..", kGemvMaxRows, " rows");
+  bf16* op = la_out(who, out, M, N);
+  const bf16* bp = la_bias(who, bias, N);
   static const int rpw_env = [] {
     const char* e = std::getenv("PENROZ_DECODE_GEMV_RPW");
     return e ? std::atoi(e) : 0;
   }();
-  if (rpw <= 0 && rpw_env > 0 && N < 16384) rpw = rpw_env;
-  if (rpw <= 0) rpw = N >= 16384 ? 8 : 2;
-  TORCH_CHECK(rpw == 2 || rpw == 4 || rpw == 8, "decode_gemv: rows_per_wave 2, 4 or 8");
-  const int RPv = rpw / 2;
-  // wave-per-row form for the bf16-x GEMVs (proj, fc2, Gemma o / down): one row per wave, the
-  // whole wave striding over K — twice the workgroups. Same box: Gemma-3 1B B = 1 1.2626 / 1.2621 ->
-  // 1.2577 / 1.2555 ms, GPT-2 B = 4 0.549 / 0.544 -> 0.544 / 0.542, GPT-2 B = 1 even
-  // (profiles/decode_r5.md). PENROZ_DECODE_GEMV_WAVE_ROW=0: the half-wave form.
-  static const bool wave_row_env = [] {
-    const char* e = std::getenv("PENROZ_DECODE_GEMV_WAVE_ROW");
-    return !(e && e[0] == '0');
-  }();
-  const bool wave_row = wave_row_env && !ln && rows_per_wave <= 0 && N < 16384;
-  const int cpl64 = (K / 8 + 63) / 64;
-  const dim3 grid(wave_row ? N : (N + rpw - 1) / rpw);
+  static const bool wave_row_env = !env_starts_with("PENROZ_DECODE_GEMV_WAVE_ROW", '0');
+  const GemvPlan p = plan_decode_gemv(M, N, K, ln, (int)rows_per_wave, rpw_env, wave_row_env);
+  TORCH_CHECK(p.rp > 0, who, ": rows_per_wave 2, 4 or 8");
   auto stream = at::hip::getCurrentHIPStream();
-  auto wp = reinterpret_cast<const bf16*>(w.data_ptr());
-  auto op = reinterpret_cast<bf16*>(out.data_ptr());
-  const int64_t o_rs = out.stride(0);
-  auto launch = [&](auto mt, auto lnt, auto rpt, auto cplt) {
-    constexpr int MM = decltype(mt)::value, RR = decltype(rpt)::value, CC = decltype(cplt)::value;
-    constexpr int LL = decltype(lnt)::value ? 1 : 0;
-    hipLaunchKernelGGL((decode_gemv_kernel<MM, LL, RR, CC>), grid, dim3(64), 0, stream, rp, dp, dbp, rop, gp, bt,
-                       (float)eps, xp, x_rs, wp, bp, op, o_rs, N, K, (int)act, 0, 0, (const float*)nullptr,
-                       (const float*)nullptr, eip, ewp, epp, eps_p, eV, eP);
+  auto launch = [&](auto m, auto pro, auto rp, auto cpl, auto epi) {  // decode_gemv_kernel's template arguments
+    hipLaunchKernelGGL((decode_gemv_kernel<decltype(m)::value, decltype(pro)::value, decltype(rp)::value,
+                                           decltype(cpl)::value, decltype(epi)::value>),
+                       dim3(p.grid), dim3(64), 0, stream, r.rin, r.delta, r.dbias, r.rout, gp, bt, (float)eps, xp, x_rs, wp,
+                       bp, op, (int64_t)out.stride(0), N, K, (int)act, 0, 0, (const float*)nullptr, (const float*)nullptr,
+                       eip, ewp, epp, eps_p, eV, eP);
   };
-  auto by_cpl = [&](auto mt, auto lnt, auto rpt) {
-    using I = std::integral_constant<int, 0>;
-    (void)sizeof(I);
-    if (cpl <= 1) launch(mt, lnt, rpt, std::integral_constant<int, 1>{});
-    else if (cpl <= 2) launch(mt, lnt, rpt, std::integral_constant<int, 2>{});
-    else if (cpl <= 3) launch(mt, lnt, rpt, std::integral_constant<int, 3>{});
-    else if (cpl <= 4) launch(mt, lnt, rpt, std::integral_constant<int, 4>{});
-    else if (cpl <= 5) launch(mt, lnt, rpt, std::integral_constant<int, 5>{});
-    else if (cpl <= 7) launch(mt, lnt, rpt, std::integral_constant<int, 7>{});
-    else if (cpl <= 12) launch(mt, lnt, rpt, std::integral_constant<int, 12>{});
-    else if (cpl <= 16) launch(mt, lnt, rpt, std::integral_constant<int, 16>{});
-    else if (cpl <= 25) launch(mt, lnt, rpt, std::integral_constant<int, 25>{});
-    else launch(mt, lnt, rpt, std::integral_constant<int, 32>{});
-  };
-  auto by_rp = [&](auto mt, auto lnt) {
-    if (RPv == 1) by_cpl(mt, lnt, std::integral_constant<int, 1>{});
-    else if (RPv == 2) by_cpl(mt, lnt, std::integral_constant<int, 2>{});
-    else by_cpl(mt, lnt, std::integral_constant<int, 4>{});
-  };
-  auto by_ln = [&](auto mt) {
-    if (wave_row) {  // one row per wave (RP = 1), chunks per lane over 64 lanes
-      auto go = [&](auto cplt) {
-        constexpr int MM = decltype(mt)::value, CC = decltype(cplt)::value;
-        hipLaunchKernelGGL((decode_gemv_kernel<MM, 0, 1, CC, 3>), grid, dim3(64), 0, stream, rp, dp, dbp, rop, gp, bt,
-                           (float)eps, xp, x_rs, wp, bp, op, o_rs, N, K, (int)act);
-      };
-      if (cpl64 <= 2) go(std::integral_constant<int, 2>{});
-      else if (cpl64 <= 4) go(std::integral_constant<int, 4>{});
-      else if (cpl64 <= 7) go(std::integral_constant<int, 7>{});
-      else if (cpl64 <= 16) go(std::integral_constant<int, 16>{});
-      else go(std::integral_constant<int, 16>{});  // K <= 8192 (checked above)
-      return;
-    }
-    if (ln) {
-      TORCH_CHECK(cpl <= 4, "decode_gemv: LN mode needs K <= 1024");
-      // LN mode instantiates only the small chunk counts (K <= 1024)
-      if (RPv == 1) {
-        if (cpl <= 3) launch(mt, std::true_type{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 3>{});
-        else launch(mt, std::true_type{}, std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
-      } else if (RPv == 2) {
-        if (cpl <= 3) launch(mt, std::true_type{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{});
-        else launch(mt, std::true_type{}, std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
-      } else {
-        if (cpl <= 3) launch(mt, std::true_type{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 3>{});
-        else launch(mt, std::true_type{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{});
-      }
-    } else {
-      by_rp(mt, std::false_type{});
-    }
-  };
-  switch (M) {
-    case 1: by_ln(std::integral_constant<int, 1>{}); break;
-    case 2: by_ln(std::integral_constant<int, 2>{}); break;
-    case 3: by_ln(std::integral_constant<int, 3>{}); break;
-    default: by_ln(std::integral_constant<int, 4>{});
-  }
+  // the instantiated (M, PRO, RP, CPL, EPI) per form; EPI 3 is the wave-per-row kernel (one row per wave)
+  const bool ok =
+      p.form == GemvForm::WaveRow
+          ? dispatch_exact(launch, GemvRows{}, p.m, IntList<0>{}, 0, IntList<1>{}, p.rp, GemvCplWave{}, p.cpl, IntList<3>{}, 3)
+      : ln ? dispatch_exact(launch, GemvRows{}, p.m, IntList<1>{}, 1, Pow2To4{}, p.rp, GemvCplLn{}, p.cpl, IntList<0>{}, 0)
+           : dispatch_exact(launch, GemvRows{}, p.m, IntList<0>{}, 0, Pow2To4{}, p.rp, GemvCplHalf{}, p.cpl, IntList<0>{}, 0);
+  TORCH_CHECK(ok, who, ": no kernel for M = ", M, ", K = ", K);
 }
 
 // Paired-row decode GEMV for 1..4 rows on a bf16 x (decode_gemv_kernel modes 1 / 2):
@@ -889,68 +760,33 @@ void decode_gemv(c10::optional<torch::Tensor> x, c10::optional<torch::Tensor> ri
 void decode_gemv_pair(torch::Tensor x, torch::Tensor w, torch::Tensor out, int64_t mode, int64_t kind, int64_t D,
                       int64_t nrot, c10::optional<torch::Tensor> cosv, c10::optional<torch::Tensor> sinv,
                       int64_t pairs_per_wave) {
+  const char* who = "decode_gemv_pair";
+  TORCH_CHECK(mode == 1 || mode == 2, who, ": mode 1 (gated) or 2 (RoPE)");
+  const bf16* wp = la_weight(who, w, 2);
   const int N = w.size(0), K = w.size(1);
-  TORCH_CHECK(mode == 1 || mode == 2, "decode_gemv_pair: mode 1 (gated) or 2 (RoPE)");
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.dim() == 2 && w.is_contiguous() &&
-                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 && K % 8 == 0 && N % 2 == 0,
-              "decode_gemv_pair: bf16 contiguous 16-B aligned W [N, K], K % 8 == 0, N even");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.dim() == 2 && x.size(1) == K && x.stride(1) == 1 &&
-                  x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "decode_gemv_pair: bf16 x [M, K], rows 16-B aligned");
+  TORCH_CHECK(K % 8 == 0 && K <= kGemvPairMaxK, who, ": K % 8 == 0, K <= ", kGemvPairMaxK);
+  const bf16* xp = la_rows(who, x, K);
   const int M = x.size(0);
-  TORCH_CHECK(M >= 1 && M <= 4, "decode_gemv_pair: 1..4 rows");
-  const int cpl = (K / 8 + 31) / 32;
-  TORCH_CHECK(cpl <= 7, "decode_gemv_pair: K <= 1792");
-  const int Nout = mode == 1 ? N / 2 : N;
-  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 && out.dim() == 2 && out.size(0) == M && out.size(1) == Nout &&
-                  out.stride(1) == 1, "decode_gemv_pair: bf16 out [M, N/2] (gated) or [M, N] (RoPE)");
+  TORCH_CHECK(M >= 1 && M <= kGemvMaxRows, who, ": 1..", kGemvMaxRows, " rows");
+  bf16* op = la_out(who, out, M, mode == 1 ? N / 2 : N);
   const float *cp = nullptr, *sp = nullptr;
   if (mode == 1) {
-    TORCH_CHECK(kind >= 0 && kind <= 2, "decode_gemv_pair: kind 0 gelu, 1 gelu_tanh, 2 silu");
-  } else if (mode == 2) {
-    TORCH_CHECK(D >= 2 && D % 2 == 0 && N % D == 0 && nrot >= 0 && nrot <= N / D, "decode_gemv_pair: RoPE geometry");
-    TORCH_CHECK(cosv.has_value() && sinv.has_value() && cosv->is_cuda() && sinv->is_cuda() &&
-                    cosv->scalar_type() == torch::kFloat32 && sinv->scalar_type() == torch::kFloat32 &&
-                    cosv->numel() >= D / 2 && sinv->numel() >= D / 2 && cosv->is_contiguous() && sinv->is_contiguous(),
-                "decode_gemv_pair: fp32 cos / sin [D/2]");
-    cp = cosv->data_ptr<float>();
-    sp = sinv->data_ptr<float>();
+    TORCH_CHECK(kind >= 0 && kind <= 2, who, ": kind 0 gelu, 1 gelu_tanh, 2 silu");
+  } else {
+    TORCH_CHECK(D >= 2 && D % 2 == 0 && N % D == 0 && nrot >= 0 && nrot <= N / D, who, ": RoPE geometry");
+    cp = la_f32_vec(who, "cos", cosv, D / 2, true);
+    sp = la_f32_vec(who, "sin", sinv, D / 2, true);
   }
-  int ppw = (int)pairs_per_wave;
-  if (ppw <= 0) ppw = N / 2 >= 16384 ? 4 : N / 2 <= 1024 ? 1 : 2;
-  TORCH_CHECK(ppw == 1 || ppw == 2 || ppw == 4, "decode_gemv_pair: pairs_per_wave 1, 2 or 4");
-  const dim3 grid((N / 2 + ppw - 1) / ppw);
+  const GemvPairPlan p = plan_decode_gemv_pair(N, K, (int)pairs_per_wave);
+  TORCH_CHECK(p.ppw > 0, who, ": pairs_per_wave 1, 2 or 4");
   auto stream = at::hip::getCurrentHIPStream();
-  auto xp = reinterpret_cast<const bf16*>(x.data_ptr());
-  auto wp = reinterpret_cast<const bf16*>(w.data_ptr());
-  auto op = reinterpret_cast<bf16*>(out.data_ptr());
-  const int64_t x_rs = x.stride(0), o_rs = out.stride(0);
-  auto launch = [&](auto mt, auto rpt, auto cplt, auto et) {
-    constexpr int MM = decltype(mt)::value, RR = decltype(rpt)::value, CC = decltype(cplt)::value;
-    constexpr int EE = decltype(et)::value;
-    hipLaunchKernelGGL((decode_gemv_kernel<MM, 0, RR, CC, EE>), grid, dim3(64), 0, stream, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, nullptr, 0.f, xp, x_rs, wp, nullptr, op, o_rs, N, K,
-                       EE == 1 ? (int)kind : 0, (int)D, (int)nrot, cp, sp);
+  auto launch = [&](auto m, auto rp, auto cpl, auto epi) {
+    constexpr int EE = decltype(epi)::value;
+    hipLaunchKernelGGL((decode_gemv_kernel<decltype(m)::value, 0, decltype(rp)::value, decltype(cpl)::value, EE>),
+                       dim3(p.grid), dim3(64), 0, stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, xp,
+                       (int64_t)x.stride(0), wp, nullptr, op, (int64_t)out.stride(0), N, K, EE == 1 ? (int)kind : 0, (int)D,
+                       (int)nrot, cp, sp);
   };
-  auto by_cpl = [&](auto mt, auto rpt, auto et) {
-    if (cpl <= 3) launch(mt, rpt, std::integral_constant<int, 3>{}, et);
-    else if (cpl <= 4) launch(mt, rpt, std::integral_constant<int, 4>{}, et);
-    else if (cpl <= 5) launch(mt, rpt, std::integral_constant<int, 5>{}, et);
-    else launch(mt, rpt, std::integral_constant<int, 7>{}, et);
-  };
-  auto by_rp = [&](auto mt, auto et) {
-    if (ppw == 1) by_cpl(mt, std::integral_constant<int, 1>{}, et);
-    else if (ppw == 2) by_cpl(mt, std::integral_constant<int, 2>{}, et);
-    else by_cpl(mt, std::integral_constant<int, 4>{}, et);
-  };
-  auto by_mode = [&](auto mt) {
-    if (mode == 1) by_rp(mt, std::integral_constant<int, 1>{});
-    else by_rp(mt, std::integral_constant<int, 2>{});
-  };
-  switch (M) {
-    case 1: by_mode(std::integral_constant<int, 1>{}); break;
-    case 2: by_mode(std::integral_constant<int, 2>{}); break;
-    case 3: by_mode(std::integral_constant<int, 3>{}); break;
-    default: by_mode(std::integral_constant<int, 4>{});
-  }
+  const bool ok = dispatch_exact(launch, GemvRows{}, M, Pow2To4{}, p.ppw, GemvCplPair{}, p.cpl, IntList<1, 2>{}, (int)mode);
+  TORCH_CHECK(ok, who, ": no kernel for M = ", M, ", K = ", K);
 }

@@ -2,6 +2,8 @@
 // the same code is also compiled into tests/native/host_plan_test.cpp and run under the host
 // AddressSanitizer / UndefinedBehaviorSanitizer (tests/test_host_sanitizers.py).
 #pragma once
+#include "dispatch.h"
+
 #include <algorithm>
 #include <cstdint>
 
@@ -88,6 +90,118 @@ inline int reduce_slices(int G) {
   int s = 1;
   while ((int64_t)s * s < G) ++s;
   return s;
+}
+
+// ---- decode GEMM / GEMV launch plans (decode_linear.hip, skinny_gemm.hip) ----
+
+// Limits the launch checks enforce; graph_decode.py reads the GEMV ones (decode_gemv_limits).
+constexpr int kGemvMaxRows = 4;      // decode_gemv / decode_gemv_pair rows
+constexpr int kGemvMaxK = 8192;      // 32 chunks of 8 per lane × 32 lanes
+constexpr int kLnMaxK = 1024;        // LN mode: the normalised row lives in registers / LDS
+constexpr int kGemvPairMaxK = 1792;  // 7 chunks per lane, the widest paired-row instantiation
+constexpr int kSkinnyMaxRows = 64;   // skinny_* / decode_ln_linear rows (4 MFMA row blocks)
+
+// Template arguments instantiated per launcher form; the chunk lists are buckets (first >= need).
+using GemvRows = IntList<1, 2, 3, 4>;
+using Pow2To4 = IntList<1, 2, 4>;  // MB, RP, pairs per wave
+using GemvCplHalf = IntList<1, 2, 3, 4, 5, 7, 12, 16, 25, 32>;
+using GemvCplLn = IntList<3, 4>;  // LN mode instantiates only the small chunk counts (K <= 1024)
+using GemvCplWave = IntList<2, 4, 7, 16>;
+using GemvCplPair = IntList<3, 4, 5, 7>;
+
+template <int... Vs>
+int bucket_of(IntList<Vs...> list, int v) {  // 0: above every bucket
+  int b = 0;
+  dispatch_bucket([&](auto c) { b = decltype(c)::value; }, list, v);
+  return b;
+}
+
+// 16-row MFMA blocks per workgroup of the skinny kernels
+inline int row_blocks(int M) { return M <= 16 ? 1 : M <= 32 ? 2 : 4; }
+
+enum class GemvForm { HalfWave, WaveRow, LN };
+struct GemvPlan {
+  GemvForm form;
+  int m;     // kernel template arguments: rows,
+  int rp;    // row pairs per wave (wave-per-row: 1 row; 0: bad rows_per_wave),
+  int cpl;   // 16-B chunks per lane (0: K has no instantiation in this form)
+  int grid;  // workgroups of one wave
+  int rows_per_wg() const { return form == GemvForm::WaveRow ? 1 : 2 * rp; }
+};
+
+// rows_per_wave 2, 4 or 8 (<= 0: chosen here); rpw_env / wave_row_env: PENROZ_DECODE_GEMV_RPW
+// (0: unset) and PENROZ_DECODE_GEMV_WAVE_ROW (true unless "0").
+inline GemvPlan plan_decode_gemv(int M, int N, int K, bool ln, int rows_per_wave, int rpw_env, bool wave_row_env) {
+  int rpw = rows_per_wave;
+  // by shape: the vocabulary projection wants fewer, longer-lived waves (8 rows); everything else
+  // 2 rows per wave — the most workgroups in flight. In the replayed step that beat 4 rows for the
+  // wider QKV / fc outputs, which the isolated microbench preferred (GPT-2 B = 1 0.3594 / 0.3608 ->
+  // 0.3563 / 0.3547 ms, Gemma-3 1B neutral; profiles/decode_r5.md). PENROZ_DECODE_GEMV_RPW forces 2 /
+  // 4 / 8 below 16k rows (A/B).
+  if (rpw <= 0 && rpw_env > 0 && N < 16384) rpw = rpw_env;
+  if (rpw <= 0) rpw = N >= 16384 ? 8 : 2;
+  const bool rpw_ok = rpw == 2 || rpw == 4 || rpw == 8;
+  // wave-per-row form for the bf16-x GEMVs (proj, fc2, Gemma o / down): one row per wave, the
+  // whole wave striding over K — twice the workgroups. Same box: Gemma-3 1B B = 1 1.2626 / 1.2621 ->
+  // 1.2577 / 1.2555 ms, GPT-2 B = 4 0.549 / 0.544 -> 0.544 / 0.542, GPT-2 B = 1 even
+  // (profiles/decode_r5.md). PENROZ_DECODE_GEMV_WAVE_ROW=0: the half-wave form.
+  const bool wave_row = wave_row_env && !ln && rows_per_wave <= 0 && N < 16384;
+  const int chunks = K / 8;
+  if (wave_row) return {GemvForm::WaveRow, M, rpw_ok ? 1 : 0, bucket_of(GemvCplWave{}, (chunks + 63) / 64), N};
+  const int cpl = (chunks + 31) / 32;
+  return {ln ? GemvForm::LN : GemvForm::HalfWave, M, rpw_ok ? rpw / 2 : 0,
+          ln ? bucket_of(GemvCplLn{}, cpl) : bucket_of(GemvCplHalf{}, cpl), (N + rpw - 1) / rpw};
+}
+
+struct GemvPairPlan {
+  int ppw;   // output pairs per wave (0: bad pairs_per_wave)
+  int cpl;   // 0: K > kGemvPairMaxK
+  int grid;
+};
+
+// N weight rows = N / 2 output pairs; pairs_per_wave 1, 2 or 4 (<= 0: by the number of pairs)
+inline GemvPairPlan plan_decode_gemv_pair(int N, int K, int pairs_per_wave) {
+  int ppw = pairs_per_wave;
+  if (ppw <= 0) ppw = N / 2 >= 16384 ? 4 : N / 2 <= 1024 ? 1 : 2;
+  const bool ppw_ok = ppw == 1 || ppw == 2 || ppw == 4;
+  return {ppw_ok ? ppw : 0, bucket_of(GemvCplPair{}, (K / 8 + 31) / 32), (N / 2 + ppw - 1) / ppw};
+}
+
+// Automatic split-K of the skinny kernels: workgroups ~ 192 when the column tiles alone (16 wide
+// for skinny_gemm, 32 for skinny_qkv_rope) are too few; every split keeps >= 4 k-steps of 32.
+inline int skinny_auto_split(int ntiles, int steps) {
+  return ntiles >= 128 ? 1 : std::max(1, std::min({(192 + ntiles - 1) / ntiles, steps / 4, 16}));
+}
+inline int skinny_gemm_auto_split(int N, int K) { return skinny_auto_split((N + 15) / 16, K / 32); }
+// The fused QKV + RoPE kernel's split and the fp32 workspace it then needs: ONE rule, used by the
+// launcher and exported (skinny_qkv_rope_plan) for the Python-side admission check (ops/gemm.py
+// skinny_qkv_rope_ok), which must refuse a shape before a graph capture rather than let the
+// launcher's workspace check throw inside it.
+inline int qkv_rope_auto_split(int N, int K) { return skinny_auto_split(N / 32, K / 32); }
+inline int64_t qkv_rope_ws_floats(int M, int N, int splitk) {
+  return splitk > 1 ? (int64_t)splitk * (N / 32) * row_blocks(M) * 512 : 0;
+}
+
+struct GridPlan {
+  int v;     // decode_gemm: row blocks per workgroup (1 / 4); decode_ln_gemm: K split (1 / 2)
+  int tw;    // output columns per workgroup
+  int grid;
+};
+
+// 4 row blocks per workgroup once there are more than two and the columns alone give >= 256
+// workgroups (weights read once); otherwise one row block per workgroup (more workgroups)
+inline GridPlan plan_decode_gemm(int M, int N) {
+  const int rb = (M > 32 && N / 16 >= 256) ? 4 : 1;
+  return {rb, 16, ((M + 16 * rb - 1) / (16 * rb)) * (N / 16)};
+}
+
+// K halves (KS = 2) by default: GPT-2 decode B = 16 / 32 / 64 0.567 / 0.584 / 0.636 -> 0.532 /
+// 0.550 / 0.620 ms/step; quarters (KS = 4) lost: 0.55 / 0.74 / 0.96 — every workgroup repeats the
+// LayerNorm of its 16 rows (profiles/decode_r5.md). ks_env 1 (PENROZ_DECODE_LN_KSPLIT=1): 64-column tiles.
+inline GridPlan plan_decode_ln_gemm(int M, int N, int K, int ks_env) {
+  const int ks = ks_env == 2 && (K / 32) % 2 == 0 ? 2 : 1;
+  const int tw = 64 / ks;
+  return {ks, tw, ((M + 15) / 16) * ((N + tw - 1) / tw)};
 }
 
 }  // namespace penroz

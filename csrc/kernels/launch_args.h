@@ -1,0 +1,104 @@
+// Operand checks of the decode GEMM / GEMV launch wrappers (decode_linear.hip, skinny_gemm.hip),
+// written once. Each checks one operand and returns its typed pointer; `who` is the entry point's
+// name for the message. Where the entry points differ, the difference is a parameter. Host only.
+#pragma once
+#include "common.h"
+#include <torch/extension.h>
+
+namespace penroz {
+
+using OptTensor = c10::optional<torch::Tensor>;
+
+inline bool la_defined(const OptTensor& t) { return t.has_value() && t->defined(); }
+inline bool la_aligned(const torch::Tensor& t, int bytes) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0; }
+
+// bf16 activation rows x [M, K]: unit column stride, rows 16-B aligned (16-B vector loads)
+inline const bf16* la_rows(const char* who, const torch::Tensor& x, int K) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 2 && x.size(1) == K &&
+                  x.stride(1) == 1 && x.stride(0) % 8 == 0 && la_aligned(x, 16),
+              who, ": bf16 x [M, K = ", K, "], unit column stride, rows 16-B aligned");
+  return reinterpret_cast<const bf16*>(x.data_ptr());
+}
+
+// bf16 weight [N, K], contiguous and 16-B aligned; N a multiple of n_mult (16 for the MFMA tiles
+// of decode_linear.hip, 2 for the packed [gate; up] and paired-row forms)
+inline const bf16* la_weight(const char* who, const torch::Tensor& w, int n_mult = 1) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.dim() == 2 && w.is_contiguous() &&
+                  la_aligned(w, 16) && w.size(0) % n_mult == 0,
+              who, ": bf16 contiguous 16-B aligned W [N, K], N % ", n_mult, " == 0");
+  return reinterpret_cast<const bf16*>(w.data_ptr());
+}
+
+// optional bf16 bias [N] (nullptr when absent); decode_linear.hip's MFMA epilogues read it in 8-B pieces
+inline const bf16* la_bias(const char* who, const OptTensor& bias, int N, int align = 2) {
+  if (!la_defined(bias)) return nullptr;
+  TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == torch::kBFloat16 && bias->is_contiguous() &&
+                  bias->numel() == N && la_aligned(*bias, align),
+              who, ": bf16 contiguous bias [N = ", N, "], ", align, "-B aligned");
+  return reinterpret_cast<const bf16*>(bias->data_ptr());
+}
+
+// fp32 contiguous vector of n entries (gamma, beta, dbias, cos, sin), or of at least n
+inline const float* la_f32_vec(const char* who, const char* what, const OptTensor& t, int64_t n, bool at_least = false) {
+  TORCH_CHECK(la_defined(t) && t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() &&
+                  (at_least ? t->numel() >= n : t->numel() == n),
+              who, ": fp32 contiguous ", what, " [", n, "]");
+  return t->data_ptr<float>();
+}
+
+// fp32 contiguous matrix [rows, cols] of the residual stream (rows < 0: any)
+inline float* la_f32_mat(const char* who, const char* what, const OptTensor& t, int64_t rows, int64_t cols) {
+  TORCH_CHECK(la_defined(t) && t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->dim() == 2 &&
+                  t->is_contiguous() && (rows < 0 || t->size(0) == rows) && t->size(1) == cols,
+              who, ": fp32 contiguous ", what, " [M, ", cols, "]");
+  return t->data_ptr<float>();
+}
+
+// bf16 output [M, N] with unit column stride; align 8: rows 8-B aligned as well (4-value stores)
+inline bf16* la_out(const char* who, const torch::Tensor& out, int M, int N, int align = 2) {
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kBFloat16 && out.dim() == 2 && out.size(0) == M &&
+                  out.size(1) == N && out.stride(1) == 1 && (align < 8 || out.stride(0) % 4 == 0) && la_aligned(out, align),
+              who, ": bf16 out [", M, ", ", N, "], unit column stride, rows ", align, "-B aligned");
+  return reinterpret_cast<bf16*>(out.data_ptr());
+}
+
+// The fused residual add in front of a LayerNorm: x = resid_in + delta + dbias, resid_out receives
+// the sum. A delta needs a resid_out that does not alias resid_in; dbias comes only with a delta.
+// lone_ignored (decode_gemv): without a delta, dbias and resid_out are not looked at. Otherwise
+// (decode_ln_linear) a lone dbias is an error and a lone resid_out is checked and written.
+struct ResidArgs {
+  const float* rin = nullptr;
+  const bf16* delta = nullptr;
+  const float* dbias = nullptr;
+  float* rout = nullptr;
+  int M = 0;
+};
+
+inline ResidArgs la_resid(const char* who, const OptTensor& rin, const OptTensor& delta, const OptTensor& dbias,
+                          const OptTensor& rout, int K, bool lone_ignored) {
+  ResidArgs r;
+  r.rin = la_f32_mat(who, "resid_in", rin, -1, K);
+  r.M = rin->size(0);
+  const bool add = la_defined(delta);
+  if (add) {
+    TORCH_CHECK(delta->is_cuda() && delta->scalar_type() == torch::kBFloat16 && delta->is_contiguous() &&
+                    delta->numel() == (int64_t)r.M * K,
+                who, ": bf16 contiguous delta [M, K]");
+    r.delta = reinterpret_cast<const bf16*>(delta->data_ptr());
+    TORCH_CHECK(la_defined(rout), who, ": a residual add (delta) needs resid_out");
+  }
+  if (!add && lone_ignored) return r;
+  if (la_defined(dbias)) {
+    TORCH_CHECK(add, who, ": dbias only with a delta");
+    r.dbias = la_f32_vec(who, "dbias", dbias, K);
+  }
+  if (la_defined(rout)) {
+    TORCH_CHECK(rout->is_cuda() && rout->scalar_type() == torch::kFloat32 && rout->is_contiguous() &&
+                    rout->numel() == (int64_t)r.M * K && rout->data_ptr() != rin->data_ptr(),
+                who, ": fp32 contiguous resid_out [M, K], not aliasing resid_in");
+    r.rout = rout->data_ptr<float>();
+  }
+  return r;
+}
+
+}  // namespace penroz

@@ -17,6 +17,8 @@
 // C/D layout of mfma_f32_16x16x32_bf16: col = lane & 15 (row m of x), row = 4·(lane >> 4) + r
 // (output column n), so each lane ends with 4 consecutive outputs of one row.
 #include "common.h"
+#include "host_plan.h"
+#include "launch_args.h"
 #include <vector>
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -479,163 +481,88 @@ using namespace penroz;
 void decode_ln_linear(torch::Tensor rin, c10::optional<torch::Tensor> delta, c10::optional<torch::Tensor> dbias,
                       c10::optional<torch::Tensor> rout, torch::Tensor gamma, torch::Tensor beta, double eps,
                       torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor out, int64_t act) {
-  TORCH_CHECK(rin.is_cuda() && rin.scalar_type() == torch::kFloat32 && rin.dim() == 2 && rin.is_contiguous(),
-              "decode_ln_linear: fp32 contiguous [M, K] residual");
-  const int M = rin.size(0), K = rin.size(1), N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64 && K % 32 == 0 && K <= 1024, "decode_ln_linear: M <= 64, K % 32 == 0, K <= 1024");
-  TORCH_CHECK(w.scalar_type() == torch::kBFloat16 && w.is_contiguous() && w.size(1) == K &&
-                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "decode_ln_linear: bf16 contiguous W [N, K]");
-  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 && out.dim() == 2 && out.size(0) == M && out.size(1) == N &&
-                  out.stride(1) == 1, "decode_ln_linear: bf16 out [M, N]");
-  TORCH_CHECK(gamma.scalar_type() == torch::kFloat32 && beta.scalar_type() == torch::kFloat32 && gamma.numel() == K &&
-                  beta.numel() == K && gamma.is_contiguous() && beta.is_contiguous(), "decode_ln_linear: fp32 gamma/beta [K]");
-  TORCH_CHECK(act >= 0 && act <= 2, "decode_ln_linear: act 0 (none), 1 (GELU erf), 2 (GELU tanh)");
-  const bf16* dp = nullptr;
-  const float* dbp = nullptr;
-  float* rop = nullptr;
-  const bf16* bp = nullptr;
-  if (delta.has_value() && delta->defined()) {
-    TORCH_CHECK(delta->scalar_type() == torch::kBFloat16 && delta->is_contiguous() && delta->numel() == (int64_t)M * K,
-                "decode_ln_linear: bf16 contiguous delta [M, K]");
-    dp = reinterpret_cast<const bf16*>(delta->data_ptr());
-    TORCH_CHECK(rout.has_value() && rout->defined(), "decode_ln_linear: a residual add needs resid_out");
-  }
-  if (dbias.has_value() && dbias->defined()) {
-    TORCH_CHECK(dp && dbias->scalar_type() == torch::kFloat32 && dbias->is_contiguous() && dbias->numel() == K,
-                "decode_ln_linear: fp32 dbias [K] (with delta)");
-    dbp = dbias->data_ptr<float>();
-  }
-  if (rout.has_value() && rout->defined()) {
-    TORCH_CHECK(rout->scalar_type() == torch::kFloat32 && rout->is_contiguous() && rout->numel() == (int64_t)M * K &&
-                    rout->data_ptr() != rin.data_ptr(), "decode_ln_linear: fp32 resid_out [M, K], not aliasing resid_in");
-    rop = rout->data_ptr<float>();
-  }
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->scalar_type() == torch::kBFloat16 && bias->is_contiguous() && bias->numel() == N,
-                "decode_ln_linear: bf16 bias [N]");
-    bp = reinterpret_cast<const bf16*>(bias->data_ptr());
-  }
-  const int MB = M <= 16 ? 1 : M <= 32 ? 2 : 4;
+  const char* who = "decode_ln_linear";
+  const bf16* wp = la_weight(who, w);
+  const int N = w.size(0), K = w.size(1);
+  const ResidArgs r = la_resid(who, rin, delta, dbias, rout, K, false);
+  const int M = r.M;
+  TORCH_CHECK(M >= 1 && M <= kSkinnyMaxRows && K % 32 == 0 && K <= kLnMaxK, who, ": M <= ", kSkinnyMaxRows,
+              ", K % 32 == 0, K <= ", kLnMaxK);
+  bf16* op = la_out(who, out, M, N);
+  const float *gp = la_f32_vec(who, "gamma", gamma, K), *bt = la_f32_vec(who, "beta", beta, K);
+  TORCH_CHECK(act >= 0 && act <= 2, who, ": act 0 (none), 1 (GELU erf), 2 (GELU tanh)");
+  const bf16* bp = la_bias(who, bias, N);
+  const int MB = row_blocks(M);
   const size_t lds = (size_t)MB * 16 * (K + 8) * 2 + (size_t)4 * MB * 64 * 16;
   static bool attr_set = false;
   if (!attr_set) {
-    const int mx = 4 * 16 * (1024 + 8) * 2 + 4 * 4 * 64 * 16;
+    const int mx = 4 * 16 * (kLnMaxK + 8) * 2 + 4 * 4 * 64 * 16;
     hipFuncSetAttribute(reinterpret_cast<const void*>(decode_ln_linear_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
     hipFuncSetAttribute(reinterpret_cast<const void*>(decode_ln_linear_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
     hipFuncSetAttribute(reinterpret_cast<const void*>(decode_ln_linear_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
     attr_set = true;
   }
   auto stream = at::hip::getCurrentHIPStream();
-  const dim3 grid((N + 15) / 16);
-  const float* rp = rin.data_ptr<float>();
-  const float* gp = gamma.data_ptr<float>();
-  const float* bt = beta.data_ptr<float>();
-  auto wp = reinterpret_cast<const bf16*>(w.data_ptr());
-  auto op = reinterpret_cast<bf16*>(out.data_ptr());
-#define PENROZ_DLL(MBV)                                                                                             \
-  hipLaunchKernelGGL(decode_ln_linear_kernel<MBV>, grid, dim3(256), lds, stream, rp, dp, dbp, rop, gp, bt, (float)eps, \
-                     wp, bp, op, (int64_t)out.stride(0), M, N, K, (int)act)
-  if (MB == 1) PENROZ_DLL(1);
-  else if (MB == 2) PENROZ_DLL(2);
-  else PENROZ_DLL(4);
-#undef PENROZ_DLL
+  dispatch_exact([&](auto mb) {
+    hipLaunchKernelGGL((decode_ln_linear_kernel<decltype(mb)::value>), dim3((N + 15) / 16), dim3(256), lds, stream, r.rin,
+                       r.delta, r.dbias, r.rout, gp, bt, (float)eps, wp, bp, op, (int64_t)out.stride(0), M, N, K, (int)act);
+  }, Pow2To4{}, MB);
 }
 
-// splitk <= 0: chosen here (workgroups ~ 192 when the 16-column slices alone are too few).
+// The operands of a split-K launch: fp32 slabs and int32 arrival counters (one per column tile)
+static void check_split_ws(const char* who, const torch::Tensor& ws, const torch::Tensor& cnt, int64_t ws_floats,
+                           int ntiles) {
+  TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == torch::kFloat32 && ws.numel() >= ws_floats, who, ": workspace too small");
+  TORCH_CHECK(cnt.is_cuda() && cnt.scalar_type() == torch::kInt32 && cnt.numel() >= ntiles, who, ": counters too small");
+}
+
+// splitk <= 0: chosen here (skinny_gemm_auto_split).
 // ws: fp32 workspace (>= splitk * ceil(N/16) * MB * 256 floats when splitk > 1); cnt: int32
 // counters (>= ceil(N/16)), zero on entry — every launch leaves them zero again.
 int64_t skinny_gemm(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor out,
                     torch::Tensor ws, torch::Tensor cnt, int64_t splitk) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16 &&
-                  out.scalar_type() == torch::kBFloat16, "skinny_gemm: bf16 x / w / out");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "skinny_gemm: 2-D operands");
-  const int M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64 && w.size(1) == K && K % 32 == 0, "skinny_gemm: M <= 64, K % 32 == 0");
-  TORCH_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "skinny_gemm: x rows 16-B aligned");
-  TORCH_CHECK(w.is_contiguous() && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "skinny_gemm: w contiguous");
-  TORCH_CHECK(out.size(0) == M && out.size(1) == N && out.stride(1) == 1, "skinny_gemm: out [M, N]");
-  const bf16* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    TORCH_CHECK(bias->scalar_type() == torch::kBFloat16 && bias->is_contiguous() && bias->numel() == N,
-                "skinny_gemm: bf16 bias [N]");
-    bp = reinterpret_cast<const bf16*>(bias->data_ptr());
-  }
-  const int ntiles = (N + 15) / 16, steps = K / 32;
-  const int MB = M <= 16 ? 1 : M <= 32 ? 2 : 4;
-  if (splitk <= 0) {
-    splitk = 1;
-    if (ntiles < 128) splitk = std::max(1, std::min({(192 + ntiles - 1) / ntiles, steps / 4, 16}));
-  }
-  TORCH_CHECK(splitk >= 1 && splitk <= steps, "skinny_gemm: bad split");
-  if (splitk > 1) {
-    TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == torch::kFloat32 &&
-                    ws.numel() >= (int64_t)splitk * ntiles * MB * 256, "skinny_gemm: workspace too small");
-    TORCH_CHECK(cnt.is_cuda() && cnt.scalar_type() == torch::kInt32 && cnt.numel() >= ntiles,
-                "skinny_gemm: counters too small");
-  }
+  const char* who = "skinny_gemm";
+  const bf16* wp = la_weight(who, w);
+  const int N = w.size(0), K = w.size(1);
+  const bf16* xp = la_rows(who, x, K);
+  const int M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= kSkinnyMaxRows && K % 32 == 0, who, ": M <= ", kSkinnyMaxRows, ", K % 32 == 0");
+  bf16* op = la_out(who, out, M, N);
+  const bf16* bp = la_bias(who, bias, N);
+  const int ntiles = (N + 15) / 16, MB = row_blocks(M);
+  if (splitk <= 0) splitk = skinny_gemm_auto_split(N, K);
+  TORCH_CHECK(splitk >= 1 && splitk <= K / 32, who, ": bad split");
+  if (splitk > 1) check_split_ws(who, ws, cnt, (int64_t)splitk * ntiles * MB * 256, ntiles);
   auto stream = at::hip::getCurrentHIPStream();
-  const dim3 grid(ntiles * splitk);
-  auto xp = reinterpret_cast<const bf16*>(x.data_ptr());
-  auto wp = reinterpret_cast<const bf16*>(w.data_ptr());
-  auto op = reinterpret_cast<bf16*>(out.data_ptr());
   float* wsp = splitk > 1 ? ws.data_ptr<float>() : nullptr;
   int* cp = splitk > 1 ? cnt.data_ptr<int>() : nullptr;
-#define PENROZ_SKINNY(MBV)                                                                                       \
-  hipLaunchKernelGGL(skinny_gemm_kernel<MBV>, grid, dim3(256), 0, stream, xp, (int64_t)x.stride(0), wp, bp, op, \
-                     (int64_t)out.stride(0), M, N, K, (int)splitk, wsp, cp)
-  if (MB == 1) PENROZ_SKINNY(1);
-  else if (MB == 2) PENROZ_SKINNY(2);
-  else PENROZ_SKINNY(4);
-#undef PENROZ_SKINNY
+  dispatch_exact([&](auto mb) {
+    hipLaunchKernelGGL((skinny_gemm_kernel<decltype(mb)::value>), dim3(ntiles * splitk), dim3(256), 0, stream, xp,
+                       (int64_t)x.stride(0), wp, bp, op, (int64_t)out.stride(0), M, N, K, (int)splitk, wsp, cp);
+  }, Pow2To4{}, MB);
   return splitk;
 }
 
 // out[M, I] = act(x · gu[:I]ᵀ) ⊙ (x · gu[I:]ᵀ) for M <= 64 decode rows (kind: 0 gelu, 1 gelu_tanh,
 // 2 silu); bit-identical to skinny_gemm(x, gu) followed by gated_act_packed.
 void skinny_gated(torch::Tensor x, torch::Tensor gu, torch::Tensor out, int64_t kind) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && gu.scalar_type() == torch::kBFloat16 &&
-                  out.scalar_type() == torch::kBFloat16, "skinny_gated: bf16 x / gu / out");
-  TORCH_CHECK(x.dim() == 2 && gu.dim() == 2 && out.dim() == 2, "skinny_gated: 2-D operands");
-  const int M = x.size(0), K = x.size(1);
-  TORCH_CHECK(gu.size(0) % 2 == 0, "skinny_gated: packed [gate; up] weight [2I, K]");
-  const int I = gu.size(0) / 2;
-  TORCH_CHECK(M >= 1 && M <= 64 && I >= 1 && gu.size(1) == K && K % 32 == 0, "skinny_gated: M <= 64, K % 32 == 0");
-  TORCH_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "skinny_gated: x rows 16-B aligned");
-  TORCH_CHECK(gu.is_contiguous() && reinterpret_cast<uintptr_t>(gu.data_ptr()) % 16 == 0, "skinny_gated: gu contiguous");
-  TORCH_CHECK(out.size(0) == M && out.size(1) == I && out.stride(1) == 1, "skinny_gated: out [M, I]");
-  TORCH_CHECK(kind >= 0 && kind <= 2, "skinny_gated: kind 0 (gelu), 1 (gelu_tanh), 2 (silu)");
-  const int MB = M <= 16 ? 1 : M <= 32 ? 2 : 4;
+  const char* who = "skinny_gated";
+  const bf16* wp = la_weight(who, gu, 2);  // packed [gate; up] weight [2I, K]
+  const int I = gu.size(0) / 2, K = gu.size(1);
+  const bf16* xp = la_rows(who, x, K);
+  const int M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= kSkinnyMaxRows && I >= 1 && K % 32 == 0, who, ": M <= ", kSkinnyMaxRows, ", K % 32 == 0");
+  bf16* op = la_out(who, out, M, I);
+  TORCH_CHECK(kind >= 0 && kind <= 2, who, ": kind 0 (gelu), 1 (gelu_tanh), 2 (silu)");
   auto stream = at::hip::getCurrentHIPStream();
-  const dim3 grid((I + 15) / 16);
-  auto xp = reinterpret_cast<const bf16*>(x.data_ptr());
-  auto wp = reinterpret_cast<const bf16*>(gu.data_ptr());
-  auto op = reinterpret_cast<bf16*>(out.data_ptr());
-#define PENROZ_SKG(MBV)                                                                                              \
-  hipLaunchKernelGGL(skinny_gated_kernel<MBV>, grid, dim3(256), 0, stream, xp, (int64_t)x.stride(0), wp, op,        \
-                     (int64_t)out.stride(0), M, I, K, (int)kind)
-  if (MB == 1) PENROZ_SKG(1);
-  else if (MB == 2) PENROZ_SKG(2);
-  else PENROZ_SKG(4);
-#undef PENROZ_SKG
-}
-
-// The fused QKV + RoPE kernel's automatic split-K (workgroups ~ 192 when the 32-column tiles alone
-// are too few) and the fp32 workspace it then needs: ONE rule, used by the launcher below and
-// exported (skinny_qkv_rope_plan) for the Python-side admission check (ops/gemm.py
-// skinny_qkv_rope_ok), which must refuse a shape before a graph capture rather than let this
-// launcher's workspace check throw inside it.
-static int qkv_rope_auto_split(int N, int K) {
-  const int ntiles = N / 32, steps = K / 32;
-  return ntiles >= 128 ? 1 : std::max(1, std::min({(192 + ntiles - 1) / ntiles, steps / 4, 16}));
-}
-static int64_t qkv_rope_ws_floats(int M, int N, int splitk) {
-  const int MB = M <= 16 ? 1 : M <= 32 ? 2 : 4;
-  return splitk > 1 ? (int64_t)splitk * (N / 32) * MB * 512 : 0;
+  dispatch_exact([&](auto mb) {
+    hipLaunchKernelGGL((skinny_gated_kernel<decltype(mb)::value>), dim3((I + 15) / 16), dim3(256), 0, stream, xp,
+                       (int64_t)x.stride(0), wp, op, (int64_t)out.stride(0), M, I, K, (int)kind);
+  }, Pow2To4{}, row_blocks(M));
 }
 
 // (split-K, fp32 workspace floats, counters) of skinny_qkv_rope at M rows, N = heads·D, K
+// (host_plan.h qkv_rope_auto_split / qkv_rope_ws_floats, the launcher's own rule)
 std::vector<int64_t> skinny_qkv_rope_plan(int64_t M, int64_t N, int64_t K) {
   const int split = qkv_rope_auto_split((int)N, (int)K);
   return {split, qkv_rope_ws_floats((int)M, (int)N, split), split > 1 ? N / 32 : 0};
@@ -645,44 +572,27 @@ std::vector<int64_t> skinny_qkv_rope_plan(int64_t M, int64_t N, int64_t K) {
 // the first nrot = H + Hkv heads; M <= 64, D % 32 == 0. Returns the split-K factor used.
 int64_t skinny_qkv_rope(torch::Tensor x, torch::Tensor w, torch::Tensor cosv, torch::Tensor sinv, int64_t D,
                         int64_t nrot, torch::Tensor out, torch::Tensor ws, torch::Tensor cnt, int64_t splitk) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16 &&
-                  out.scalar_type() == torch::kBFloat16, "skinny_qkv_rope: bf16 x / w / out");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "skinny_qkv_rope: 2-D operands");
-  const int M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64 && w.size(1) == K && K % 32 == 0, "skinny_qkv_rope: M <= 64, K % 32 == 0");
-  TORCH_CHECK(D >= 32 && D % 32 == 0 && N % D == 0 && nrot >= 0 && nrot <= N / D,
-              "skinny_qkv_rope: D % 32 == 0, whole heads, nrot <= heads");
-  TORCH_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              "skinny_qkv_rope: x rows 16-B aligned");
-  TORCH_CHECK(w.is_contiguous() && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "skinny_qkv_rope: w contiguous");
-  TORCH_CHECK(out.size(0) == M && out.size(1) == N && out.stride(1) == 1, "skinny_qkv_rope: out [M, N]");
-  TORCH_CHECK(cosv.scalar_type() == torch::kFloat32 && sinv.scalar_type() == torch::kFloat32 && cosv.is_contiguous() &&
-                  sinv.is_contiguous() && cosv.numel() == D / 2 && sinv.numel() == D / 2,
-              "skinny_qkv_rope: fp32 cos / sin [D/2]");
-  const int ntiles = N / 32, steps = K / 32;
-  const int MB = M <= 16 ? 1 : M <= 32 ? 2 : 4;
+  const char* who = "skinny_qkv_rope";
+  const bf16* wp = la_weight(who, w);
+  const int N = w.size(0), K = w.size(1);
+  const bf16* xp = la_rows(who, x, K);
+  const int M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= kSkinnyMaxRows && K % 32 == 0, who, ": M <= ", kSkinnyMaxRows, ", K % 32 == 0");
+  TORCH_CHECK(D >= 32 && D % 32 == 0 && N % D == 0 && nrot >= 0 && nrot <= N / D, who,
+              ": D % 32 == 0, whole heads, nrot <= heads");
+  bf16* op = la_out(who, out, M, N);
+  const float *cs = la_f32_vec(who, "cos", cosv, D / 2), *sn = la_f32_vec(who, "sin", sinv, D / 2);
+  const int ntiles = N / 32;
   if (splitk <= 0) splitk = qkv_rope_auto_split(N, K);
-  TORCH_CHECK(splitk >= 1 && splitk <= steps, "skinny_qkv_rope: bad split");
-  if (splitk > 1) {
-    TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == torch::kFloat32 && ws.numel() >= qkv_rope_ws_floats(M, N, (int)splitk),
-                "skinny_qkv_rope: workspace too small");
-    TORCH_CHECK(cnt.is_cuda() && cnt.scalar_type() == torch::kInt32 && cnt.numel() >= ntiles,
-                "skinny_qkv_rope: counters too small");
-  }
+  TORCH_CHECK(splitk >= 1 && splitk <= K / 32, who, ": bad split");
+  if (splitk > 1) check_split_ws(who, ws, cnt, qkv_rope_ws_floats(M, N, (int)splitk), ntiles);
   auto stream = at::hip::getCurrentHIPStream();
-  const dim3 grid(ntiles * splitk);
-  auto xp = reinterpret_cast<const bf16*>(x.data_ptr());
-  auto wp = reinterpret_cast<const bf16*>(w.data_ptr());
-  auto op = reinterpret_cast<bf16*>(out.data_ptr());
   float* wsp = splitk > 1 ? ws.data_ptr<float>() : nullptr;
   int* cp = splitk > 1 ? cnt.data_ptr<int>() : nullptr;
-#define PENROZ_SQR(MBV)                                                                                              \
-  hipLaunchKernelGGL(skinny_qkv_rope_kernel<MBV>, grid, dim3(256), 0, stream, xp, (int64_t)x.stride(0), wp, op,     \
-                     (int64_t)out.stride(0), M, K, (int)D, (int)nrot, cosv.data_ptr<float>(), sinv.data_ptr<float>(), \
-                     (int)splitk, wsp, cp)
-  if (MB == 1) PENROZ_SQR(1);
-  else if (MB == 2) PENROZ_SQR(2);
-  else PENROZ_SQR(4);
-#undef PENROZ_SQR
+  dispatch_exact([&](auto mb) {
+    hipLaunchKernelGGL((skinny_qkv_rope_kernel<decltype(mb)::value>), dim3(ntiles * splitk), dim3(256), 0, stream, xp,
+                       (int64_t)x.stride(0), wp, op, (int64_t)out.stride(0), M, K, (int)D, (int)nrot, cs, sn, (int)splitk,
+                       wsp, cp);
+  }, Pow2To4{}, row_blocks(M));
   return splitk;
 }

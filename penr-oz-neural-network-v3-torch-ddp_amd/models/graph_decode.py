@@ -85,12 +85,16 @@ BATCHED_BLOCK = os.environ.get("PENROZ_DECODE_BATCHED", "1") != "0"
 # (csrc/kernels/decode_linear.hip decode_gemv: one memory round trip, no LDS, no barrier, no
 # split-K hand-off); "0": decode_ln_linear + skinny GEMMs
 GEMV_MAX_ROWS = int(os.environ.get("PENROZ_DECODE_GEMV_MAX_ROWS", "4"))
-# decode_gemv's reduction limit (256 lanes × 32 values, decode_linear.hip); wider linears take the
-# skinny GEMM
-GEMV_MAX_K = 8192
 # the sampler's last row advances the step counters itself (sample_step with adv_a / adv_b / done:
 # one launch less per token); "0": the separate decode_advance kernel
 FUSED_ADVANCE = os.environ.get("PENROZ_DECODE_FUSED_ADVANCE", "1") != "0"
+
+
+def _gemv_limits():
+    """(rows, K, LN-mode K, paired-row K) the decode GEMV launchers accept at most: their own
+    limits (csrc/kernels/host_plan.h), read here instead of repeated; wider linears take the
+    skinny GEMM. Needs the built extension (callers ask ``_ext.available()`` first)."""
+    return _ext.kernels().decode_gemv_limits()
 
 
 class _GraphMode:
@@ -307,9 +311,12 @@ class GPTDecodeProgram:
         return torch.mm(x, lin.weight.t())
 
     def _gemv_ok(self, rows: int) -> bool:
+        if not _ext.available():
+            return False
         sp = self.spec
-        return (1 <= rows <= min(4, GEMV_MAX_ROWS) and sp.C % 8 == 0 and sp.C <= 1024
-                and sp.blocks[0].fc.out_features % 8 == 0 and sp.gelu_approx in ("none", "tanh") and _ext.available())
+        max_rows, _, max_ln_k, _ = _gemv_limits()  # the QKV / fc GEMVs run in LN mode
+        return (1 <= rows <= min(max_rows, GEMV_MAX_ROWS) and sp.C % 8 == 0 and sp.C <= max_ln_k
+                and sp.blocks[0].fc.out_features % 8 == 0 and sp.gelu_approx in ("none", "tanh"))
 
     def _fused_ok(self, rows: int) -> bool:
         sp = self.spec
@@ -443,13 +450,17 @@ class GemmaDecodeProgram:
         paired-row epilogues). The residual adds + RMSNorms stay the rms_residual kernel: as the
         GEMVs' prologue — every workgroup normalising the rows itself — it measured neutral
         (Gemma-3 1B B=1 1.576 / 1.579 vs 1.571 / 1.571 ms, profiles/decode_r5.md)."""
-        # decode_gemv reads K <= 8192 (decode_linear.hip); the O and down projections read K = H·D
-        # and the intermediate size (12288 on Gemma-4 e2b's KV-shared double-wide MLPs)
-        return (1 <= rows <= min(4, GEMV_MAX_ROWS) and C % 8 == 0 and C <= 1792 and _ext.available()
-                and all(b["o"].shape[1] <= GEMV_MAX_K and b["down"].shape[1] <= GEMV_MAX_K for b in self.blocks))
+        if not _ext.available():
+            return False
+        # the QKV and gate|up projections (K = C) are paired-row GEMVs; the O and down projections
+        # are plain ones and read K = H·D and the intermediate size (12288 on Gemma-4 e2b's
+        # KV-shared double-wide MLPs: above decode_gemv's K limit)
+        max_rows, max_k, _, max_pair_k = _gemv_limits()
+        return (1 <= rows <= min(max_rows, GEMV_MAX_ROWS) and C % 8 == 0 and C <= max_pair_k
+                and all(b["o"].shape[1] <= max_k and b["down"].shape[1] <= max_k for b in self.blocks))
 
     def _lin(self, x: Tensor, w: Tensor, gemv: bool) -> Tensor:
-        if gemv and w.shape[1] % 8 == 0 and w.shape[1] <= GEMV_MAX_K:
+        if gemv and w.shape[1] % 8 == 0 and w.shape[1] <= _gemv_limits()[1]:
             return gemm_ops.decode_gemv(x.contiguous(), w)
         return _linear(x, w)
 

@@ -16,6 +16,110 @@ static int fails = 0;
     }                                                               \
   } while (0)
 
+using namespace penroz;
+
+template <class L>
+static bool in_list(L list, int v) {
+  return dispatch_exact([](auto) {}, list, v);
+}
+
+// dispatch.h: exact match hits each listed value (once, with that value) and nothing else; the
+// bucket form picks the first V >= v
+static void test_dispatch() {
+  using L = IntList<1, 2, 3, 4, 5, 7, 12, 16, 25, 32>;
+  for (int v = -2; v <= 40; ++v) {
+    int calls = 0, got = -1;
+    const bool hit = dispatch_exact([&](auto c) { ++calls, got = decltype(c)::value; }, L{}, v);
+    const bool listed = (v >= 1 && v <= 5) || v == 7 || v == 12 || v == 16 || v == 25 || v == 32;
+    EXPECT(hit == listed && calls == (listed ? 1 : 0) && (!listed || got == v));
+    calls = 0, got = -1;
+    const bool bhit = dispatch_bucket([&](auto c) { ++calls, got = decltype(c)::value; }, L{}, v);
+    EXPECT(bhit == (v <= 32) && calls == (bhit ? 1 : 0));
+    if (bhit) EXPECT(got >= v && in_list(L{}, got));
+    for (int u = v; bhit && u < got; ++u) EXPECT(!in_list(L{}, u));  // nothing listed in [v, got)
+    EXPECT(bucket_of(L{}, v) == (bhit ? got : 0));
+  }
+  // several (list, value) pairs: one call with all constants, false when any value is unlisted
+  for (int m = 0; m <= 5; ++m)
+    for (int r = 0; r <= 5; ++r) {
+      int calls = 0, gm = 0, gr = 0;
+      const bool hit = dispatch_exact([&](auto a, auto b) { ++calls, gm = decltype(a)::value, gr = decltype(b)::value; },
+                                      GemvRows{}, m, Pow2To4{}, r);
+      const bool want = m >= 1 && m <= 4 && (r == 1 || r == 2 || r == 4);
+      EXPECT(hit == want && calls == (want ? 1 : 0) && (!want || (gm == m && gr == r)));
+    }
+  EXPECT(row_blocks(1) == 1 && row_blocks(16) == 1 && row_blocks(17) == 2 && row_blocks(32) == 2 &&
+         row_blocks(33) == 4 && row_blocks(64) == 4);
+}
+
+// Every decode_gemv / decode_gemv_pair plan names an instantiated kernel whose lanes cover K and
+// whose grid covers N
+static void test_gemv_plan_properties() {
+  const int Ns[] = {16, 33, 768, 2304, 16383, 16384, 50304, 262144};
+  for (int M = 1; M <= kGemvMaxRows; ++M)
+    for (int K = 8; K <= kGemvMaxK; K += 8)
+      for (int N : Ns)
+        for (int ln = 0; ln < 2; ++ln)
+          for (int rpw : {0, 2, 4, 8})
+            for (int env = 0; env < 4; ++env) {  // bit 0: PENROZ_DECODE_GEMV_WAVE_ROW=0, bit 1: ..._RPW=4
+              const GemvPlan p = plan_decode_gemv(M, N, K, ln != 0, rpw, env & 2 ? 4 : 0, !(env & 1));
+              EXPECT(p.m == M && in_list(Pow2To4{}, p.rp));
+              EXPECT((p.form == GemvForm::LN) == (ln != 0));
+              if (ln && K > kLnMaxK) {  // LN mode is never planned above its limit
+                EXPECT(p.cpl == 0);
+                continue;
+              }
+              const bool wr = p.form == GemvForm::WaveRow;
+              EXPECT(wr ? in_list(GemvCplWave{}, p.cpl) : ln ? in_list(GemvCplLn{}, p.cpl) : in_list(GemvCplHalf{}, p.cpl));
+              EXPECT(p.cpl * (wr ? 64 : 32) * 8 >= K);
+              EXPECT(!wr || (p.rp == 1 && rpw == 0 && N < 16384 && !(env & 1)));
+              EXPECT((long long)p.grid * p.rows_per_wg() >= N && (long long)(p.grid - 1) * p.rows_per_wg() < N);
+              if (rpw) EXPECT(!wr && p.rp == rpw / 2);
+            }
+  EXPECT(plan_decode_gemv(1, 768, 768, false, 3, 0, true).rp == 0);   // bad rows_per_wave
+  EXPECT(plan_decode_gemv(1, 768, 768, true, 0, 16, true).rp == 0);   // bad PENROZ_DECODE_GEMV_RPW
+  for (int K = 8; K <= kGemvMaxK; K += 8)
+    for (int N : {2, 66, 256, 2048, 2050, 13824, 32768, 65536})
+      for (int ppw : {0, 1, 2, 4}) {
+        const GemvPairPlan p = plan_decode_gemv_pair(N, K, ppw);
+        EXPECT(in_list(Pow2To4{}, p.ppw) && (!ppw || p.ppw == ppw));
+        EXPECT((long long)p.grid * p.ppw >= N / 2 && (long long)(p.grid - 1) * p.ppw < N / 2);
+        if (K > kGemvPairMaxK) EXPECT(p.cpl == 0);
+        else EXPECT(in_list(GemvCplPair{}, p.cpl) && p.cpl * 32 * 8 >= K);
+      }
+  EXPECT(plan_decode_gemv_pair(256, 64, 3).ppw == 0);
+}
+
+// Values worked out by hand from the launch rules (environment switches unset)
+static void test_decode_plan_goldens() {
+  struct G { int M, K, N, rpw; GemvForm form; int rp, cpl, grid; };
+  const G gemv[] = {{1, 768, 768, 0, GemvForm::WaveRow, 1, 2, 768},     {4, 768, 50304, 0, GemvForm::HalfWave, 4, 3, 6288},
+                    {2, 6912, 1152, 0, GemvForm::WaveRow, 1, 16, 1152}, {1, 8192, 16, 0, GemvForm::WaveRow, 1, 16, 16},
+                    {3, 40, 33, 0, GemvForm::WaveRow, 1, 2, 33},        {1, 3072, 768, 4, GemvForm::HalfWave, 2, 12, 192},
+                    {1, 768, 2304, 0, GemvForm::LN, 1, 3, 1152},        {4, 1024, 75, 0, GemvForm::LN, 1, 4, 38},
+                    {3, 96, 50, 0, GemvForm::LN, 1, 3, 25}};
+  for (const G& g : gemv) {
+    const GemvPlan p = plan_decode_gemv(g.M, g.N, g.K, g.form == GemvForm::LN, g.rpw, 0, true);
+    EXPECT(p.form == g.form && p.m == g.M && p.rp == g.rp && p.cpl == g.cpl && p.grid == g.grid);
+  }
+  const int pair[][5] = {{1152, 13824, 2, 5, 3456}, {1792, 66, 1, 7, 33}, {64, 256, 1, 3, 128}};  // K, N, ppw, CPL, grid
+  for (auto& g : pair) {
+    const GemvPairPlan p = plan_decode_gemv_pair(g[1], g[0], 0);
+    EXPECT(p.ppw == g[2] && p.cpl == g[3] && p.grid == g[4]);
+  }
+  EXPECT(skinny_gemm_auto_split(768, 768) == 4 && skinny_gemm_auto_split(2304, 768) == 1);
+  EXPECT(skinny_gemm_auto_split(768, 3072) == 4 && skinny_gemm_auto_split(40, 96) == 1);
+  EXPECT(qkv_rope_auto_split(512, 2048) == 12 && qkv_rope_ws_floats(64, 512, 12) == 12 * 16 * 4 * 512);
+  EXPECT(qkv_rope_auto_split(4096, 4096) == 1 && qkv_rope_ws_floats(64, 4096, 1) == 0);
+  EXPECT(plan_decode_gemm(64, 1536).v == 1 && plan_decode_gemm(64, 4096).v == 4);
+  EXPECT(plan_decode_gemm(40, 13824).v == 4 && plan_decode_gemm(17, 1152).v == 1);
+  EXPECT(plan_decode_gemm(64, 4096).grid == 256 && plan_decode_gemm(17, 1152).grid == 2 * 72);
+  const GridPlan a = plan_decode_ln_gemm(64, 2304, 768, 2), b = plan_decode_ln_gemm(9, 1040, 96, 2);
+  EXPECT(a.v == 2 && a.tw == 32 && a.grid == 288);
+  EXPECT(b.v == 1 && b.tw == 64 && b.grid == 17);
+  EXPECT(plan_decode_ln_gemm(64, 2304, 768, 1).v == 1);  // PENROZ_DECODE_LN_KSPLIT=1
+}
+
 int main() {
   // GPT-2 124M / XL weight-gradient shapes (K = tokens per step) and edge cases
   const int shapes[][3] = {{2304, 768, 65536}, {768, 768, 65536}, {3072, 768, 65536}, {768, 3072, 65536},
@@ -67,6 +171,9 @@ int main() {
     const int s = penroz::reduce_slices(g);
     EXPECT(s >= 1 && (long long)s * s >= g && (long long)(s - 1) * (s - 1) < (g > 1 ? g : 2));
   }
+  test_dispatch();
+  test_gemv_plan_properties();
+  test_decode_plan_goldens();
   std::printf("host_plan_test: %s (%d failures)\n", fails ? "FAILED" : "ok", fails);
   return fails ? 1 : 0;
 }

@@ -37,6 +37,15 @@ def test_qkv_rope_plan_admission_over_every_split():
     assert split == 12 and ws == 12 * 16 * 4 * 512
 
 
+def test_decode_gemv_limits_are_the_launchers_own():
+    """(rows, K, LN-mode K, paired-row K) of decode_gemv / decode_gemv_pair: the decode programs'
+    admission checks (models/graph_decode.py) read the constants the launch checks use."""
+    from penroz.models import graph_decode as gd
+
+    assert _ext.kernels().decode_gemv_limits() == (4, 8192, 1024, 1792)
+    assert gd._gemv_limits() == (4, 8192, 1024, 1792)
+
+
 def _tiles(qb, BM, BN, T):
     return (min(T, (qb + 1) * BM) + BN - 1) // BN
 

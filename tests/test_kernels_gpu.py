@@ -1335,6 +1335,106 @@ def test_decode_gemm_plain_and_gated(M, K, N, kind):
     assert (big[M:] == 7).all() and (big[:, N:] == 7).all()
 
 
+def _z(*shape, dtype=torch.bfloat16):
+    return torch.zeros(*shape, device=DEV, dtype=dtype)
+
+
+def _launcher_operands(M=2, K=64, N=32, wrows=None):
+    """Valid operands for any of the decode GEMM / GEMV launchers at [M, K] x [N, K]ᵀ (wrows: rows
+    of a packed [gate; up] weight); RoPE entries use one head of D = 32."""
+    f32 = torch.float32
+    return dict(M=M, K=K, N=N, x=_z(M, K), w=_z(wrows or N, K), bias=_z(N), out=_z(M, N), resid=_z(M, N, dtype=f32),
+                rin=_z(M, K, dtype=f32), delta=_z(M, K), dbias=_z(K, dtype=f32), rout=_z(M, K, dtype=f32),
+                gamma=_z(K, dtype=f32), beta=_z(K, dtype=f32), cos=_z(16, dtype=f32), sin=_z(16, dtype=f32),
+                ws=_z(8, dtype=f32), cnt=_z(8, dtype=torch.int32), per_wave=0)
+
+
+# One bad operand each, built from the valid ones. Every offending tensor is a view of a buffer
+# at least as large as the valid operand, so even a launcher that wrongly let it through would
+# read and write inside its own allocations.
+_BAD_OPERANDS = {
+    "x_fp32": lambda o: dict(x=_z(o["M"], o["K"], dtype=torch.float32)),
+    "x_base_plus_2B": lambda o: dict(x=_z(o["M"] * o["K"] + 8)[1:1 + o["M"] * o["K"]].view(o["M"], o["K"])),
+    "x_row_stride_K+4": lambda o: dict(x=_z(o["M"], o["K"] + 4)[:, :o["K"]]),
+    "w_transposed": lambda o: dict(w=_z(o["K"], o["w"].shape[0]).t()),
+    "bias_N-1": lambda o: dict(bias=_z(o["N"])[:o["N"] - 1]),
+    "out_M+1_rows": lambda o: dict(out=_z(o["M"] + 1, o["N"])),
+    "out_row_stride_N+2": lambda o: dict(out=_z(o["M"], o["N"] + 2)[:, :o["N"]]),  # rows not 8-B aligned
+    "resid_M+1_rows": lambda o: dict(resid=_z(o["M"] + 1, o["N"], dtype=torch.float32)),
+    "resid_in_bf16": lambda o: dict(rin=_z(2 * o["M"] * o["K"])[:o["M"] * o["K"]].view(o["M"], o["K"])),
+    "resid_out_is_resid_in": lambda o: dict(rout=o["rin"]),
+    "per_wave_3": lambda o: dict(per_wave=3),
+    "cos_D/2-1": lambda o: dict(cos=_z(16, dtype=torch.float32)[:15]),
+    "cos_D/2+1": lambda o: dict(cos=_z(17, dtype=torch.float32)),
+}
+_X_CASES = ["x_fp32", "x_base_plus_2B", "x_row_stride_K+4", "w_transposed", "out_M+1_rows"]
+_LN_CASES = ["resid_in_bf16", "resid_out_is_resid_in", "w_transposed", "bias_N-1", "out_M+1_rows"]
+
+
+def _kk():
+    return _ext.kernels()
+
+
+# entry point -> [(call, shape of the valid call, bad operands, bad shapes)]
+_LAUNCHER_CASES = {
+    "decode_gemv": [
+        (lambda o: _kk().decode_gemv(o["x"], None, None, None, None, None, None, 0.0, o["w"], o["bias"], o["out"], 0,
+                                     o["per_wave"]),
+         {}, _X_CASES + ["bias_N-1", "per_wave_3"], [dict(M=5), dict(K=8200)]),
+        (lambda o: _kk().decode_gemv(None, o["rin"], o["delta"], o["dbias"], o["rout"], o["gamma"], o["beta"], 1e-5,
+                                     o["w"], o["bias"], o["out"], 0, o["per_wave"]),
+         {}, _LN_CASES + ["per_wave_3"], [dict(M=5), dict(K=1032)])],
+    "decode_gemv_pair": [
+        (lambda o: _kk().decode_gemv_pair(o["x"], o["w"], o["out"], 1, 0, pairs_per_wave=o["per_wave"]),
+         dict(wrows=64), _X_CASES + ["per_wave_3"], [dict(M=5), dict(K=1800)]),
+        (lambda o: _kk().decode_gemv_pair(o["x"], o["w"], o["out"], 2, 0, 32, 1, o["cos"], o["sin"], o["per_wave"]),
+         {}, _X_CASES + ["cos_D/2-1"], [dict(M=5), dict(K=1800)])],
+    "decode_ln_gemm": [
+        (lambda o: _kk().decode_ln_gemm(o["rin"], o["gamma"], o["beta"], 1e-5, o["w"], o["bias"], o["out"], 0),
+         {}, ["resid_in_bf16", "w_transposed", "bias_N-1", "out_M+1_rows", "out_row_stride_N+2"], [dict(N=24)])],
+    "decode_gemm_acc": [
+        (lambda o: _kk().decode_gemm_acc(o["x"], o["w"], o["bias"], o["resid"]),
+         {}, _X_CASES[:4] + ["bias_N-1", "resid_M+1_rows"], [dict(N=24)])],
+    "decode_gemm": [
+        (lambda o: _kk().decode_gemm(o["x"], o["w"], o["out"], -1),
+         {}, _X_CASES + ["out_row_stride_N+2"], [dict(N=24)])],
+    "decode_ln_linear": [
+        (lambda o: _kk().decode_ln_linear(o["rin"], o["delta"], o["dbias"], o["rout"], o["gamma"], o["beta"], 1e-5,
+                                          o["w"], o["bias"], o["out"], 0),
+         {}, _LN_CASES, [dict(M=65), dict(K=1056)])],
+    "skinny_gemm": [
+        (lambda o: _kk().skinny_gemm(o["x"], o["w"], o["bias"], o["out"], o["ws"], o["cnt"]),
+         {}, _X_CASES + ["bias_N-1"], [dict(M=65)])],
+    "skinny_gated": [
+        (lambda o: _kk().skinny_gated(o["x"], o["w"], o["out"], 0), dict(wrows=64), _X_CASES, [dict(M=65)])],
+    "skinny_qkv_rope": [
+        (lambda o: _kk().skinny_qkv_rope(o["x"], o["w"], o["cos"], o["sin"], 32, 1, o["out"], o["ws"], o["cnt"]),
+         {}, _X_CASES + ["cos_D/2-1", "cos_D/2+1"], [dict(M=65)])],
+}
+
+
+@pytest.mark.parametrize("entry", sorted(_LAUNCHER_CASES))
+def test_decode_launchers_reject_bad_operands(entry):
+    """Each decode GEMM / GEMV launcher takes its valid call and refuses, on the host and before
+    any launch, one bad operand at a time: wrong dtype, misaligned base, misaligned row stride,
+    non-contiguous weight, short bias, extra output rows, aliased residuals, too many rows, a K
+    above the form's limit (LN mode 1024, paired rows 1792, GEMV 8192), N % 16 != 0 for the MFMA
+    tiles, a cos / sin table of the wrong length. The message names the entry point."""
+    for call, base, cases, shapes in _LAUNCHER_CASES[entry]:
+        call(_launcher_operands(**base))
+        for case in cases:
+            print(entry, base, case)  # shown when the call below does not raise
+            o = _launcher_operands(**base)
+            o.update(_BAD_OPERANDS[case](o))
+            with pytest.raises(RuntimeError, match=f"^{entry}: "):
+                call(o)
+        for shape in shapes:
+            print(entry, base, shape)
+            with pytest.raises(RuntimeError, match=f"^{entry}: "):
+                call(_launcher_operands(**{**base, **shape}))
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_update_moments_matches_torch_std(dtype):
     """Per-epoch weight-update diagnostics: the chunked fp64 moments kernel == torch's per-tensor
