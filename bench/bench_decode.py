@@ -2,6 +2,7 @@
 or a Gemma-3 1B shaped model (RoPE, GQA 4:1, head_dim 256, 262k vocab; HF config builder).
 
 python bench/bench_decode.py [--model gpt2|gemma3-1b] [--batch 64] [--prompt 64] [--new 128] [--turbo]
+                             [--top-k 50] [--top-p P] [--min-p P]      (--top-k 0: no top-k)
 Prints one JSON line: generated tokens/s over all rows (BASELINE config 4: batch 64 /generate).
 """
 import argparse, json, os, sys, time
@@ -23,6 +24,9 @@ ap.add_argument("--model", default="gpt2", choices=["gpt2", "gemma3-1b"])
 # the generation window (block_size): a context longer than it is cropped and re-prefilled every
 # token, so long-context rows need --block >= prompt + new
 ap.add_argument("--block", type=int, default=1024)
+ap.add_argument("--top-k", type=int, default=50, help="0: no top-k")
+ap.add_argument("--top-p", type=float, default=None)
+ap.add_argument("--min-p", type=float, default=None)
 a = ap.parse_args()
 if a.turbo:
     M.create_kv_cache = lambda n, cap=None: KV.TurboQuantKVCache(n, cap)
@@ -41,12 +45,14 @@ m = NeuralNetworkModel("dec", Mapper(layers, {"adamw": {"lr": 6e-4}})).to("cuda"
 if a.dtype == "bf16":
     m.to(dtype=torch.bfloat16)
 ctx = torch.randint(0, V, (a.batch, a.prompt)).tolist()
-m.generate_batch(ctx, a.block, 4, temperature=1.0, top_k=50)  # warmup
+samp = dict(temperature=1.0, top_k=a.top_k or None, top_p=a.top_p, min_p=a.min_p)
+m.generate_batch(ctx, a.block, 4, **samp)  # warmup
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-out = m.generate_batch(ctx, a.block, a.new, temperature=1.0, top_k=50)
+out = m.generate_batch(ctx, a.block, a.new, **samp)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 print(json.dumps({"metric": "decode tokens/sec (all rows)", "value": a.batch * a.new / dt, "batch": a.batch,
                   "prompt": a.prompt, "new_tokens": a.new, "block": a.block, "ms_per_step": dt / a.new * 1e3, "dtype": a.dtype,
+                  "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p,
                   "kv_cache": "int8-turboquant" if a.turbo else a.dtype, "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))

@@ -61,10 +61,10 @@ void adam_rows_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Te
                     double b2, double eps, double wd, int64_t step, double grad_scale, bool maximize, bool decoupled);
 // sampling.hip
 torch::Tensor sample_tokens(torch::Tensor logits, c10::optional<torch::Tensor> uniform, double temperature,
-                            int64_t top_k);
+                            int64_t top_k, double top_p, double min_p);
 void sample_step(torch::Tensor logits, double temperature, int64_t top_k, torch::Tensor seed, torch::Tensor step,
                  torch::Tensor idx_out, torch::Tensor out_buf, c10::optional<torch::Tensor> adv_a,
-                 c10::optional<torch::Tensor> adv_b, c10::optional<torch::Tensor> done);
+                 c10::optional<torch::Tensor> adv_b, c10::optional<torch::Tensor> done, double top_p, double min_p);
 void decode_advance(torch::Tensor a, torch::Tensor b, torch::Tensor c);
 // decode_attn.hip
 torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c10::optional<torch::Tensor> k_scale,
@@ -201,12 +201,16 @@ PYBIND11_MODULE(penroz_kernels, m) {
   m.def("adam_step", &adam_step);
   m.def("adam_rows_step", &adam_rows_step, "row-split Adam/AdamW step of an embedding table (mode 0: untouched rows, 1: touched rows)");
   m.def("multi_tensor_adam", &multi_tensor_adam);
-  m.def("sample_tokens", &sample_tokens);
+  m.def("sample_tokens", &sample_tokens, "one token per row of logits [B, V]; top_p / min_p: nucleus and min-p filters "
+        "applied after top-k (1.0 / 0.0: off)",
+        pybind11::arg("logits"), pybind11::arg("uniform"), pybind11::arg("temperature"), pybind11::arg("top_k"),
+        pybind11::arg("top_p") = 1.0, pybind11::arg("min_p") = 0.0);
   m.def("sample_step", &sample_step, "decode-step sampler: device-hashed uniforms, writes idx_out and out_buf[:, *step]; "
         "with adv_a / adv_b / done the last row's writer also advances the counters",
         pybind11::arg("logits"), pybind11::arg("temperature"), pybind11::arg("top_k"), pybind11::arg("seed"),
         pybind11::arg("step"), pybind11::arg("idx_out"), pybind11::arg("out_buf"), pybind11::arg("adv_a") = pybind11::none(),
-        pybind11::arg("adv_b") = pybind11::none(), pybind11::arg("done") = pybind11::none());
+        pybind11::arg("adv_b") = pybind11::none(), pybind11::arg("done") = pybind11::none(), pybind11::arg("top_p") = 1.0,
+        pybind11::arg("min_p") = 0.0);
   m.def("decode_advance", &decode_advance, "+1 on three device int64 scalars");
   m.def("decode_attn", &decode_attn, pybind11::arg("q"), pybind11::arg("kc"), pybind11::arg("vc"), pybind11::arg("k_scale"),
         pybind11::arg("v_scale"), pybind11::arg("S"), pybind11::arg("q_offset"), pybind11::arg("scale"),

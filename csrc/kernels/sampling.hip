@@ -2,6 +2,11 @@
 //   temperature == 0  -> argmax (first index on ties, like torch.argmax);
 //   top_k > 0         -> radix-select the k-th largest (4 × 8-bit passes, LDS histograms) and
 //                        keep logits >= it;
+//   top_p < 1         -> the same radix select with fixed-point MASS bins and the target
+//                        top_p·Z: keep a logit iff the mass of the strictly larger ones is
+//                        < top_p·Z (ties stay or go together, the maximum always stays);
+//   min_p > 0         -> keep logits >= max + T·ln(min_p);
+//   (both are template switches: with neither, the kernels compile to what they were without)
 //   then softmax of (logit / T) over the kept set and an inverse-CDF draw with the row's
 //   uniform u: thread-major order (thread t owns elements t, t+1024, …), one block scan of
 //   the per-thread sums finds the owning thread, which walks its own elements.
@@ -98,9 +103,88 @@ __device__ __forceinline__ void pick_digit(const uint32_t* bins, uint32_t* wtot,
   }
 }
 
-template <typename T>
+// ---- nucleus (top-p) / min-p. Both filters only raise the order-key threshold the top-k stage
+// produced (or cut a prefix where the candidates are already ranked). With S the top-k
+// survivors, w_i = exp((x_i - max)/T), Z = Σ_S w_i:  top-p keeps i iff the mass of the strictly
+// larger logits is < top_p·Z (ties kept or dropped together, the maximum always kept); min-p
+// keeps i iff x_i >= max + T·ln(min_p).
+// Determinism: mass is accumulated as 64-bit FIXED-POINT INTEGERS (w·2^40, so w <= 1 is <= 2^40 and a
+// 2^22-logit row still sums below 2^63). Integer adds commute, so the LDS-atomic histograms,
+// the block sums and the cut do not depend on arrival order; the quantum costs at most
+// V·2^-40 <= 2.4e-7 of Z (Z >= 1) at V = 256 Ki, well inside the ~1e-5 error of the fp32 weights.
+constexpr float kMassScale = 1099511627776.f;  // 2^40
+__device__ __forceinline__ uint64_t mass_q(float w) { return (uint64_t)(w * kMassScale); }
+
+__device__ __forceinline__ float key_value(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int o) {
+  return (uint64_t)__shfl_up((unsigned long long)v, o, 64);
+}
+
+// Σ over the block of v (NW waves); red: NW LDS words. Every thread calls it and gets the sum.
+template <int NW>
+__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  uint64_t s = 0;
+  for (int i = 0; i < NW; ++i) s += red[i];
+  __syncthreads();
+  return s;
+}
+
+// smallest integer P with (above < top_p·Z) <=> (above < P) for integer masses; 1 <= P <= Z
+__device__ __forceinline__ uint64_t nucleus_target(float top_p, uint64_t z) {
+  const double p = ceil((double)top_p * (double)z);
+  uint64_t P = p >= 9.2e18 ? z : (uint64_t)p;
+  if (P > z) P = z;
+  return P < 1 ? 1 : P;
+}
+
+// order key of the min-p logit bound max + T·ln(min_p) (<= max, so the maximum survives); -0 so
+// that both zeros pass a bound of zero
+__device__ __forceinline__ uint32_t minp_key(float gmax, float temperature, float min_p) {
+  float xt = gmax + temperature * __logf(min_p);
+  if (xt == 0.f) xt = -0.f;
+  return order_key(xt);
+}
+
+// pick_digit over MASS bins: the digit d with M(d+1) < target <= M(d), M(d) = Σ_{b>=d} bins[b];
+// the remaining target (target - M(d+1)) goes to the next pass. Integer masses: exact.
+__device__ __forceinline__ void pick_digit_mass(const uint64_t* bins, uint64_t* wtot, int shift, uint32_t pre,
+                                                uint32_t msk, uint64_t target, uint32_t* sel_prefix,
+                                                uint32_t* sel_mask, uint64_t* sel_m) {
+  const int t = threadIdx.x, lane = t & 63;
+  uint64_t c = 0, incl = 0;
+  if (t < 256) {
+    c = bins[255 - t];
+    incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint64_t n = shfl_up_u64(incl, o);
+      if (lane >= o) incl += n;
+    }
+    if (lane == 63) wtot[t >> 6] = incl;
+  }
+  __syncthreads();
+  if (t < 256) {
+    for (int i = 0; i < (t >> 6); ++i) incl += wtot[i];
+    const int d = 255 - t;
+    const uint64_t above = incl - c;
+    if (above < target && (incl >= target || d == 0)) {
+      *sel_m = target - above;
+      *sel_prefix = pre | ((uint32_t)d << shift);
+      *sel_mask = msk | (255u << shift);
+    }
+  }
+}
+
+template <typename T, bool NUC = false>
 __global__ void __launch_bounds__(kST) sample_kernel(const T* __restrict__ logits, const SampleIO io, int V,
-                                                     float temperature, int top_k) {
+                                                     float temperature, int top_k, float top_p, float min_p) {
   __shared__ float fred[kST / 64];
   __shared__ int ired[kST / 64];
   __shared__ uint32_t hist[256];
@@ -109,6 +193,9 @@ __global__ void __launch_bounds__(kST) sample_kernel(const T* __restrict__ logit
   __shared__ uint32_t sel_prefix, sel_mask;
   __shared__ int sel_k;
   __shared__ int64_t result;
+  __shared__ uint64_t mhist[NUC ? 256 : 1];  // nucleus: mass bins
+  __shared__ uint64_t mred[NUC ? kST / 64 : 1];
+  __shared__ uint64_t sel_m;
   const int row = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
   const T* lp = logits + (size_t)row * V;
 
@@ -119,6 +206,7 @@ __global__ void __launch_bounds__(kST) sample_kernel(const T* __restrict__ logit
     const float v = to_f(lp[i]);
     if (v > bm || (v == bm && i < bi)) { bm = v; bi = i; }
   }
+  const float tmax = bm;  // this thread's maximum (nucleus: first-level select)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float om = __shfl_xor(bm, o, 64);
@@ -162,9 +250,49 @@ __global__ void __launch_bounds__(kST) sample_kernel(const T* __restrict__ logit
     thr = sel_prefix;
   }
 
-  // ---- softmax weights (unnormalised) and per-thread sums
   const float invT = 1.f / temperature;
   const float m = gmax * invT;
+  // ---- nucleus: mass-weighted radix select over the same keys (bins hold fixed-point mass, the
+  // target is top_p·Z), first over the 1024 per-thread maxima — a subset of the row, so its
+  // result L is a lower bound of the cut — then over re-reads of the row, elements >= L only
+  if constexpr (NUC) {
+    if (top_p < 1.f) {
+      uint64_t zq = 0;
+      for (int i = t; i < V; i += kST) {
+        const float v = to_f(lp[i]);
+        if (thr == 0 || order_key(v) >= thr) zq += mass_q(__expf(v * invT - m));
+      }
+      const uint64_t target = nucleus_target(top_p, block_sum_u64<kST / 64>(zq, mred));
+      uint32_t lo = thr;
+      for (int level = 0; level < 2; ++level) {
+        if (t == 0) { sel_prefix = 0; sel_mask = 0; sel_m = target; }
+        for (int shift = 24; shift >= 0; shift -= 8) {
+          if (t < 256) mhist[t] = 0;
+          __syncthreads();
+          const uint32_t pre = sel_prefix, msk = sel_mask;
+          const uint64_t mm = sel_m;
+          auto add = [&](float v) {
+            const uint32_t k = order_key(v);
+            if (k < lo || (k & msk) != pre) return;
+            const uint64_t q = mass_q(__expf(v * invT - m));
+            if (q) atomicAdd(reinterpret_cast<unsigned long long*>(&mhist[(k >> shift) & 255u]), (unsigned long long)q);
+          };
+          if (level == 0) add(tmax);
+          else
+            for (int i = t; i < V; i += kST) add(to_f(lp[i]));
+          __syncthreads();
+          pick_digit_mass(mhist, mred, shift, pre, msk, mm, &sel_prefix, &sel_mask, &sel_m);
+          __syncthreads();
+        }
+        lo = max(lo, sel_prefix);
+        __syncthreads();
+      }
+      thr = lo;
+    }
+    if (min_p > 0.f) thr = max(thr, minp_key(gmax, temperature, min_p));
+  }
+
+  // ---- softmax weights (unnormalised) and per-thread sums
   float s = 0.f;
   for (int i = t; i < V; i += kST) {
     const float v = to_f(lp[i]);
@@ -206,10 +334,13 @@ __global__ void __launch_bounds__(kST) sample_kernel(const T* __restrict__ logit
 // histogram then serialises tens of thousands of LDS atomics on one address.
 constexpr int kRT = 512;  // 256 VGPRs per thread: room for a 104-logit slice
 
-template <int CPT, typename T>
+template <int CPT, typename T, bool NUC = false>
 __global__ void __launch_bounds__(kRT) sample_reg_kernel(const T* __restrict__ logits, const SampleIO io, int V,
-                                                         float temperature, int top_k) {
-  __shared__ uint32_t hist[256 * 32];
+                                                         float temperature, int top_k, float top_p, float min_p) {
+  __shared__ __attribute__((aligned(16))) uint32_t hist[256 * 32];
+  __shared__ uint64_t mbins[NUC ? 256 : 1];  // nucleus: mass bins, wave partials, remaining target
+  __shared__ uint64_t mred[NUC ? kRT / 64 : 1];
+  __shared__ uint64_t sel_m, mtarget;
   __shared__ uint32_t bins[256];
   __shared__ uint32_t wtot[4];
   __shared__ float fred[kRT / 64];
@@ -300,6 +431,7 @@ __global__ void __launch_bounds__(kRT) sample_reg_kernel(const T* __restrict__ l
     int* ci = reinterpret_cast<int*>(hist + kRT);              // [512] candidate indices
     float* pr = reinterpret_cast<float*>(hist + 2 * kRT);      // [512] weights in rank order
     int* pix = reinterpret_cast<int*>(hist + 3 * kRT);         // [512] indices in rank order
+    uint32_t* pk = hist + 4 * kRT;                             // [512] keys in rank order (nucleus)
     ck[t] = tkey;
     __syncthreads();
     int rk = 0;  // 16-B broadcast reads, 8 in flight (a serial 4-B loop waits out the LDS latency)
@@ -380,6 +512,7 @@ __global__ void __launch_bounds__(kRT) sample_reg_kernel(const T* __restrict__ l
           const uint32_t bits = (mk & 0x80000000u) ? (mk & 0x7fffffffu) : ~mk;  // order_key⁻¹
           pr[r] = __expf(__uint_as_float(bits) * invT - m);
           pix[r] = mi;
+          if constexpr (NUC) pk[r] = mk;
         }
       }
       __syncthreads();
@@ -403,6 +536,41 @@ __global__ void __launch_bounds__(kRT) sample_reg_kernel(const T* __restrict__ l
       }
       __syncthreads();
       const float cum = wsum[w] + inc;
+      if constexpr (NUC) {
+        // the candidates are ranked, so both filters cut a prefix: an integer scan of the
+        // fixed-point masses finds the last rank whose exclusive prefix is < top_p·Z, and the
+        // cut extends over the ranks that tie with it (same key)
+        const uint64_t q = t < top_k ? mass_q(pv) : 0;
+        uint64_t qi = q;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const uint64_t n = shfl_up_u64(qi, o);
+          if (lane >= o) qi += n;
+        }
+        if (lane == 63) mred[w] = qi;
+        __syncthreads();
+        uint64_t off = 0, zq = 0;
+        for (int i = 0; i < kRT / 64; ++i) {
+          if (i < w) off += mred[i];
+          zq += mred[i];
+        }
+        const uint64_t excl = off + qi - q;
+        uint32_t kcut = min_p > 0.f ? minp_key(gmax, temperature, min_p) : 0u;
+        if (top_p < 1.f) {
+          const uint64_t P = nucleus_target(top_p, zq);
+          if (t < top_k && excl < P && (t == top_k - 1 || excl + q >= P)) sel_prefix = pk[t];
+          __syncthreads();
+          kcut = max(kcut, sel_prefix);
+        }
+        const bool keep = t < top_k && pk[t] >= kcut;
+        if (keep && (t == top_k - 1 || pk[t + 1] < kcut)) total_s = cum;  // the last kept rank
+        __syncthreads();
+        const float target = io.uniform(row) * total_s;
+        if (keep && pv > 0.f && cum > target && cum - pv <= target) result = pix[t];
+        __syncthreads();
+        if (t == 0) io.write(row, result);
+        return;
+      }
       const float target = io.uniform(row) * total_s;
       if (t < top_k && pv > 0.f && cum > target && cum - pv <= target) result = pix[t];
       __syncthreads();
@@ -452,9 +620,82 @@ __global__ void __launch_bounds__(kRT) sample_reg_kernel(const T* __restrict__ l
         }
     }, top_k);
   }
-  // ---- unnormalised softmax weights of the kept set; block scan of per-thread sums
   const float invT = 1.f / temperature;
   const float m = gmax * invT;
+  // ---- nucleus: the same four 8-bit passes with MASS bins (fixed-point, see mass_q) and the
+  // target top_p·Z instead of k. Lane-private copies as above ([bin][16] 64-bit words in the
+  // same 32 KB; lanes l, l+16, l+32, l+48 share one), and the same two levels: (1) over the 512
+  // per-thread maxima — a subset of the row, so the key L it selects has at least the target
+  // mass at or above it and the row's cut is >= L — then (2) over the elements >= L only.
+  if constexpr (NUC) {
+    if (top_p < 1.f) {
+      // chunk by chunk: the barrier keeps the compiler from widening / exponentiating the whole
+      // slice ahead of the adds (register pressure)
+      auto opaque_chunk = [&](int k) {
+#pragma unroll
+        for (int h = 0; h < H; ++h) asm volatile("" : "+v"(raw[k][h].x), "+v"(raw[k][h].y), "+v"(raw[k][h].z), "+v"(raw[k][h].w));
+      };
+      uint64_t zq = 0;
+#pragma unroll
+      for (int k = 0; k < CPT; ++k) {
+        opaque_chunk(k);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float x = val(k, j);
+          if (8 * (t + kRT * k) + j < V && (thr == 0 || order_key(x) >= thr)) zq += mass_q(__expf(x * invT - m));
+        }
+      }
+      zq = block_sum_u64<kRT / 64>(zq, mred);
+      if (t == 0) mtarget = nucleus_target(top_p, zq);  // (kept in LDS: only thread 0 reads it back)
+      uint64_t* mh = reinterpret_cast<uint64_t*>(hist);
+      auto mass_select = [&](auto&& visit) -> uint32_t {
+        if (t == 0) { sel_prefix = 0; sel_mask = 0; sel_m = mtarget; }
+        for (int shift = 24; shift >= 0; shift -= 8) {
+          for (int i = t; i < 256 * 16; i += kRT) mh[i] = 0;
+          __syncthreads();
+          const uint32_t pre = sel_prefix, msk = sel_mask;
+          const uint64_t mm = sel_m;
+          opaque();
+          visit([&](uint32_t key, float x) {
+            if ((key & msk) != pre) return;
+            const uint64_t q = mass_q(__expf(x * invT - m));
+            if (q)
+              atomicAdd(reinterpret_cast<unsigned long long*>(&mh[((key >> shift) & 255u) * 16 + (lane & 15)]),
+                        (unsigned long long)q);
+          });
+          __syncthreads();
+          if (t < 256) {  // rotated reads, as for the counts
+            uint64_t c = 0;
+            for (int i = 0; i < 16; ++i) c += mh[t * 16 + ((i + t) & 15)];
+            mbins[t] = c;
+          }
+          __syncthreads();
+          pick_digit_mass(mbins, mred, shift, pre, msk, mm, &sel_prefix, &sel_mask, &sel_m);
+          __syncthreads();
+        }
+        const uint32_t sel = sel_prefix;
+        __syncthreads();  // every thread has read the selection before the next select resets it
+        return sel;
+      };
+      const uint32_t lo = max(thr, mass_select([&](auto&& add) {
+        if (tkey >= thr) add(tkey, key_value(tkey));
+      }));
+      thr = max(lo, mass_select([&](auto&& add) {
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+          opaque_chunk(k);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float x = val(k, j);
+            const uint32_t key = order_key(x);
+            if (8 * (t + kRT * k) + j < V && key >= lo) add(key, x);
+          }
+        }
+      }));
+    }
+    if (min_p > 0.f) thr = max(thr, minp_key(gmax, temperature, min_p));
+  }
+  // ---- unnormalised softmax weights of the kept set; block scan of per-thread sums
   float s = 0.f;
   opaque();
 #pragma unroll
@@ -523,10 +764,6 @@ __global__ void __launch_bounds__(kRT) sample_reg_kernel(const T* __restrict__ l
 constexpr int kMergeBatch = 8;  // sample_merge_kernel: candidate slots per thread loaded together
 constexpr int kPartN = 4096, kPartK = 64, kPartC = 128, kPartKeep = 1024, kPartMaxP = 64,
               kPartLds = kPartMaxP * kPartC;  // every part's candidates fit: none dropped in the merge
-
-__device__ __forceinline__ float key_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 template <typename T>
 __global__ void __launch_bounds__(256) sample_part_kernel(const T* __restrict__ logits, int V, int P, int top_k,
@@ -616,7 +853,9 @@ __global__ void __launch_bounds__(256) sample_part_kernel(const T* __restrict__ 
   if (t == 0) cnt[(size_t)row * P + part] = min(ncand, kPartC);
 }
 
+template <bool NUC>
 __global__ void __launch_bounds__(256) sample_merge_kernel(const SampleIO io, int P, float temperature, int top_k,
+                                                           float top_p, float min_p,
                                                            const float* __restrict__ pval, const int* __restrict__ pidx,
                                                            const uint32_t* __restrict__ ckey,
                                                            const int* __restrict__ cidx, const int* __restrict__ cnt) {
@@ -630,6 +869,8 @@ __global__ void __launch_bounds__(256) sample_merge_kernel(const SampleIO io, in
   __shared__ int kidx[kPartKeep];
   __shared__ float sval[kPartKeep];
   __shared__ int sidx[kPartKeep];
+  __shared__ uint64_t mq[NUC ? kPartKeep : 1];  // nucleus: fixed-point masses of the kept entries
+  __shared__ uint64_t mred[NUC ? 4 : 1];
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn_lds[];  // kPartLds keys + indices (64 KB)
   uint32_t* lkey = dyn_lds;
   int* lidx = reinterpret_cast<int*>(dyn_lds + kPartLds);
@@ -735,12 +976,34 @@ __global__ void __launch_bounds__(256) sample_merge_kernel(const SampleIO io, in
   }
   const int n = min(nkeep, kPartKeep);
   const float invT = 1.f / temperature;
+  // nucleus: the kept set is small and in LDS, so the definition is applied directly — entry e
+  // stays iff the fixed-point mass of the strictly larger entries is < top_p·Z (and its value
+  // passes the min-p bound). A dropped entry keeps its slot with weight 0: the draw skips it.
+  uint32_t drop = 0;  // bit i: this thread's i-th entry (e = t + 256·i) is cut
+  if constexpr (NUC) {
+    uint64_t zq = 0;
+    for (int e = t; e < n; e += 256) {
+      const uint64_t q = mass_q(__expf((kval[e] - gmax) * invT));
+      mq[e] = q;
+      zq += q;
+    }
+    const uint64_t target = nucleus_target(top_p, block_sum_u64<4>(zq, mred));  // (syncs: mq complete)
+    const float xmin = min_p > 0.f ? key_value(minp_key(gmax, temperature, min_p)) : -INFINITY;
+    for (int e = t, i = 0; e < n; e += 256, ++i) {
+      const float x = kval[e];
+      uint64_t above = 0;
+      if (top_p < 1.f)
+        for (int j = 0; j < n; ++j) above += kval[j] > x ? mq[j] : 0;
+      if (above >= target || x < xmin) drop |= 1u << i;
+    }
+  }
   float part_sum = 0.f;
-  for (int e = t; e < n; e += 256) {  // rank by token index: the draw walks the kept set in index order
+  for (int e = t, i = 0; e < n; e += 256, ++i) {  // rank by token index: the draw walks the kept set in index order
     const int ix = kidx[e];
     int r = 0;
     for (int j = 0; j < n; ++j) r += kidx[j] < ix;
-    const float wgt = __expf((kval[e] - gmax) * invT);
+    float wgt = __expf((kval[e] - gmax) * invT);
+    if constexpr (NUC) wgt = (drop >> i) & 1u ? 0.f : wgt;
     sval[r] = wgt;
     sidx[r] = ix;
     part_sum += wgt;
@@ -752,7 +1015,7 @@ __global__ void __launch_bounds__(256) sample_merge_kernel(const SampleIO io, in
   const float total = (fred[0] + fred[1]) + (fred[2] + fred[3]);
   const float target = io.uniform(row) * total;
   float carry = 0.f;
-  int pick = n > 0 ? sidx[n - 1] : gidx;
+  int pick = (n > 0 && !NUC) ? sidx[n - 1] : gidx;  // (nucleus: the last slot may be a cut entry)
   for (int b0 = 0; b0 < n; b0 += 64) {
     const int e = b0 + lane;
     float incl = e < n ? sval[e] : 0.f;
@@ -774,14 +1037,22 @@ __global__ void __launch_bounds__(256) sample_merge_kernel(const SampleIO io, in
 
 using namespace penroz;
 
-static void launch_sample(const torch::Tensor& logits, const SampleIO& io, double temperature, int64_t top_k) {
+static void launch_sample(const torch::Tensor& logits, const SampleIO& io, double temperature, int64_t top_k,
+                          double top_p, double min_p) {
   TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2);
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "top_p must be in (0, 1], got ", top_p);
+  TORCH_CHECK(min_p >= 0.0 && min_p < 1.0, "min_p must be in [0, 1), got ", min_p);
+  // the nucleus instantiations run only when a filter is on: the defaults launch today's kernels
+  const bool nuc = temperature != 0.0 && (top_p < 1.0 || min_p > 0.0);
+  const float pp = nuc ? (float)top_p : 1.f, mp = nuc ? (float)min_p : 0.f;
   const int B = logits.size(0), V = logits.size(1);
   auto stream = at::hip::getCurrentHIPStream();
   int chunks = (V / 8 + kRT - 1) / kRT;
   for (int c : {1, 2, 3, 4, 6, 8, 10, 13, 16})  // instantiated slice sizes
     if (chunks <= c) { chunks = c; break; }
-  const bool fits = chunks <= (logits.scalar_type() == torch::kBFloat16 ? 16 : 8);
+  // nucleus: the 13- and 16-chunk slices already sit at 256 VGPRs and the nucleus code does not
+  // fit beside them without more scratch, so rows above 40 960 logits take the streaming kernel
+  const bool fits = chunks <= (logits.scalar_type() == torch::kBFloat16 ? (nuc ? 10 : 16) : 8);
   const float tt = (float)temperature;
   const int kk = (int)top_k;
   // the two-stage form for rows too wide for registers, and for any number of rows from
@@ -818,47 +1089,63 @@ static void launch_sample(const torch::Tensor& logits, const SampleIO& io, doubl
       hipLaunchKernelGGL(sample_part_kernel<float>, dim3(P, B), dim3(256), 0, stream, logits.data_ptr<float>(), V, P,
                          kpart, pval.data_ptr<float>(), pidx.data_ptr<int>(), ckp, cip, cnp);
     static bool lds_set = [] {  // > 64 KB of LDS per workgroup must be requested
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(sample_merge_kernel),
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(sample_merge_kernel<false>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPartLds * 8) == hipSuccess &&
+             hipFuncSetAttribute(reinterpret_cast<const void*>(sample_merge_kernel<true>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, kPartLds * 8) == hipSuccess;
     }();
     TORCH_CHECK(lds_set, "sample_merge_kernel: LDS request refused");
-    hipLaunchKernelGGL(sample_merge_kernel, dim3(B), dim3(256), kPartLds * 8, stream, io, P, tt, kpart, pval.data_ptr<float>(),
-                       pidx.data_ptr<int>(), ckp, cip, cnp);
+    if (nuc)
+      hipLaunchKernelGGL(sample_merge_kernel<true>, dim3(B), dim3(256), kPartLds * 8, stream, io, P, tt, kpart, pp, mp,
+                         pval.data_ptr<float>(), pidx.data_ptr<int>(), ckp, cip, cnp);
+    else
+      hipLaunchKernelGGL(sample_merge_kernel<false>, dim3(B), dim3(256), kPartLds * 8, stream, io, P, tt, kpart, pp, mp,
+                         pval.data_ptr<float>(), pidx.data_ptr<int>(), ckp, cip, cnp);
     return;
   }
   if (V % 8 == 0 && fits && logits.scalar_type() != torch::kFloat16) {
     auto launch = [&](auto tag) {
       using T = decltype(tag);
       const T* lp = reinterpret_cast<const T*>(logits.data_ptr());
-#define PENROZ_SAMPLE_REG(C) \
-  case C: hipLaunchKernelGGL((sample_reg_kernel<C, T>), dim3(B), dim3(kRT), 0, stream, lp, io, V, tt, kk); break;
+#define PENROZ_SAMPLE_REG_N(C, N) \
+  hipLaunchKernelGGL((sample_reg_kernel<C, T, N>), dim3(B), dim3(kRT), 0, stream, lp, io, V, tt, kk, pp, mp)
+#define PENROZ_SAMPLE_REG(C)                      \
+  case C:                                         \
+    if (nuc) PENROZ_SAMPLE_REG_N(C, true);        \
+    else PENROZ_SAMPLE_REG_N(C, false);           \
+    break;
+#define PENROZ_SAMPLE_REG_WIDE(C) \
+  case C: PENROZ_SAMPLE_REG_N(C, false); break;  // (never reached with a nucleus filter: fits)
       switch (chunks) {
         PENROZ_SAMPLE_REG(1) PENROZ_SAMPLE_REG(2) PENROZ_SAMPLE_REG(3) PENROZ_SAMPLE_REG(4) PENROZ_SAMPLE_REG(6)
         PENROZ_SAMPLE_REG(8)
         default:
           if constexpr (sizeof(T) == 2) {
-            switch (chunks) { PENROZ_SAMPLE_REG(10) PENROZ_SAMPLE_REG(13) PENROZ_SAMPLE_REG(16) }
+            switch (chunks) { PENROZ_SAMPLE_REG(10) PENROZ_SAMPLE_REG_WIDE(13) PENROZ_SAMPLE_REG_WIDE(16) }
           }
       }
+#undef PENROZ_SAMPLE_REG_WIDE
 #undef PENROZ_SAMPLE_REG
+#undef PENROZ_SAMPLE_REG_N
     };
     if (logits.scalar_type() == torch::kBFloat16) launch(bf16{});
     else launch(float{});
     return;
   }
-  if (logits.scalar_type() == torch::kBFloat16)
-    hipLaunchKernelGGL(sample_kernel<bf16>, dim3(B), dim3(kST), 0, stream,
-                       reinterpret_cast<const bf16*>(logits.data_ptr()), io, V, tt, kk);
-  else if (logits.scalar_type() == torch::kFloat32)
-    hipLaunchKernelGGL(sample_kernel<float>, dim3(B), dim3(kST), 0, stream, logits.data_ptr<float>(), io, V, tt, kk);
-  else if (logits.scalar_type() == torch::kFloat16)
-    hipLaunchKernelGGL(sample_kernel<__half>, dim3(B), dim3(kST), 0, stream,
-                       reinterpret_cast<const __half*>(logits.data_ptr()), io, V, tt, kk);
+  auto stream_launch = [&](auto tag) {
+    using T = decltype(tag);
+    const T* lp = reinterpret_cast<const T*>(logits.data_ptr());
+    if (nuc) hipLaunchKernelGGL((sample_kernel<T, true>), dim3(B), dim3(kST), 0, stream, lp, io, V, tt, kk, pp, mp);
+    else hipLaunchKernelGGL((sample_kernel<T, false>), dim3(B), dim3(kST), 0, stream, lp, io, V, tt, kk, pp, mp);
+  };
+  if (logits.scalar_type() == torch::kBFloat16) stream_launch(bf16{});
+  else if (logits.scalar_type() == torch::kFloat32) stream_launch(float{});
+  else if (logits.scalar_type() == torch::kFloat16) stream_launch(__half{});
   else TORCH_CHECK(false, "unsupported logits dtype");
 }
 
 torch::Tensor sample_tokens(torch::Tensor logits, c10::optional<torch::Tensor> uniform, double temperature,
-                            int64_t top_k) {
+                            int64_t top_k, double top_p, double min_p) {
   TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2);
   const int B = logits.size(0);
   auto out = torch::empty({B, 1}, logits.options().dtype(torch::kInt64));
@@ -867,7 +1154,7 @@ torch::Tensor sample_tokens(torch::Tensor logits, c10::optional<torch::Tensor> u
   else u = torch::zeros({B}, logits.options().dtype(torch::kFloat32));
   TORCH_CHECK(u.numel() == B && u.is_cuda());
   launch_sample(logits, SampleIO{u.data_ptr<float>(), nullptr, nullptr, out.data_ptr<int64_t>(), nullptr, 0}, temperature,
-                top_k);
+                top_k, top_p, min_p);
   return out;
 }
 
@@ -875,7 +1162,7 @@ torch::Tensor sample_tokens(torch::Tensor logits, c10::optional<torch::Tensor> u
 // from (seed, *step, r) on the device. Then one tiny kernel advances the step counters.
 void sample_step(torch::Tensor logits, double temperature, int64_t top_k, torch::Tensor seed, torch::Tensor step,
                  torch::Tensor idx_out, torch::Tensor out_buf, c10::optional<torch::Tensor> adv_a,
-                 c10::optional<torch::Tensor> adv_b, c10::optional<torch::Tensor> done) {
+                 c10::optional<torch::Tensor> adv_b, c10::optional<torch::Tensor> done, double top_p, double min_p) {
   TORCH_CHECK(logits.dim() == 2 && step.is_cuda() && step.scalar_type() == torch::kInt64 && step.numel() == 1);
   TORCH_CHECK(seed.is_cuda() && seed.scalar_type() == torch::kInt64 && seed.numel() == 1, "seed: device int64 [1]");
   const int B = logits.size(0);
@@ -894,7 +1181,7 @@ void sample_step(torch::Tensor logits, double temperature, int64_t top_k, torch:
     io.done = reinterpret_cast<unsigned*>(done->data_ptr<int>());
     io.nrows = B;
   }
-  launch_sample(logits, io, temperature, top_k);
+  launch_sample(logits, io, temperature, top_k, top_p, min_p);
 }
 
 __global__ void decode_advance_kernel(int64_t* a, int64_t* b, int64_t* c) {

@@ -588,7 +588,8 @@ def applicable(model) -> bool:
 class GraphDecoder:
     """Static decode state + the captured step graph for ``rows`` sequences."""
 
-    def __init__(self, model, rows: int, capacity: int, temperature: float, top_k: int | None):
+    def __init__(self, model, rows: int, capacity: int, temperature: float, top_k: int | None,
+                 top_p: float | None = None, min_p: float | None = None):
         # weak: the model caches its decoders (model.__dict__), so a strong reference would make a
         # cycle that only the cyclic GC frees — and a collection that runs while ANOTHER graph is
         # being captured destroys this one's graph mid-capture (a hard abort)
@@ -601,6 +602,7 @@ class GraphDecoder:
         self.cache.init_graph_state(self.device)
         self.rows, self.capacity = rows, capacity
         self.temperature, self.top_k = float(temperature), top_k
+        self.top_p, self.min_p = _normalise_filters(temperature, top_p, min_p)
         self.idx = torch.zeros(rows, 1, dtype=torch.long, device=self.device)
         self.out = torch.zeros(rows, capacity, dtype=torch.long, device=self.device)
         self.step_t = torch.zeros(1, dtype=torch.long, device=self.device)
@@ -645,15 +647,19 @@ class GraphDecoder:
                 # buffer (uniforms hashed on the device), one kernel advances the counters
                 V = last.shape[-1]
                 k = 0 if self.top_k is None or self.top_k >= V else int(self.top_k)
+                # the nucleus / min-p cut is made by the sampler inside the captured graph
+                nuc = () if self.top_p is None and self.min_p is None else (self.top_p or 1.0, self.min_p or 0.0)
                 if FUSED_ADVANCE:  # the sampler's last row advances the counters itself
                     _ext.kernels().sample_step(last.contiguous(), self.temperature, k, self.seed_t, self.step_t,
-                                               self.idx, self.out, self.cache.pos_t, self.cache.len_t, self._done_t)
+                                               self.idx, self.out, self.cache.pos_t, self.cache.len_t, self._done_t,
+                                               *nuc)
                 else:
                     _ext.kernels().sample_step(last.contiguous(), self.temperature, k, self.seed_t, self.step_t,
-                                               self.idx, self.out)
+                                               self.idx, self.out, None, None, None, *nuc)
                     _ext.kernels().decode_advance(self.cache.pos_t, self.cache.len_t, self.step_t)
             else:
-                nxt = samp_ops.sample(last, self.temperature, self.top_k, device_rng=True)
+                nxt = samp_ops.sample(last, self.temperature, self.top_k, device_rng=True, top_p=self.top_p,
+                                      min_p=self.min_p)
                 torch.add(nxt, 0, out=self.idx)  # a kernel, not a memcpy node
                 self.out.index_copy_(1, self.step_t, nxt)
                 self.cache.pos_t.add_(1)
@@ -714,7 +720,7 @@ class GraphDecoder:
         self.graph = g
         self._set_state(last_tok, cache_len, start)  # capture does not execute; state is as before
         log.info(f"captured decode graph: rows={self.rows} block={self.capacity} "
-                 f"temperature={self.temperature} top_k={self.top_k}")
+                 f"temperature={self.temperature} top_k={self.top_k} top_p={self.top_p} min_p={self.min_p}")
 
     @torch.inference_mode()
     def run(self, last_tok: Tensor, n_steps: int, start: int = 0) -> Tensor:
@@ -733,7 +739,17 @@ class GraphDecoder:
         return self.out[:, :n_steps]
 
 
-def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: int | None) -> GraphDecoder | None:
+def _normalise_filters(temperature: float, top_p: float | None, min_p: float | None):
+    """(top_p, min_p) with the values that mean "no filter" — and both at temperature 0, which
+    ignores them — folded to None, so equal behaviour shares one captured graph."""
+    tp, mp = samp_ops._check_filters(top_p, min_p)
+    if not temperature:
+        return None, None
+    return (tp if tp < 1.0 else None), (mp if mp > 0.0 else None)
+
+
+def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: int | None,
+                top_p: float | None = None, min_p: float | None = None) -> GraphDecoder | None:
     """Cached per model and (rows, block size, sampling settings, weights identity); None when the
     model does not qualify (CPU, no attention, RoPE head_dim without a decode kernel) or ``PENROZ_GRAPH_DECODE=0``."""
     if not applicable(model):
@@ -742,13 +758,13 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
     # weights identity AND version: in-place updates (training) re-capture, so nothing captured
     # (e.g. LayerNorm's cached fp32 weight copies for bf16 models) can go stale
     version = sum(q._version for q in model.parameters())
-    key = (rows, block_size, float(temperature), top_k if temperature else None, kvc.TURBO_QUANT_ENABLED,
-           p.data_ptr(), p.dtype, version)
+    key = (rows, block_size, float(temperature), top_k if temperature else None,
+           *_normalise_filters(temperature, top_p, min_p), kvc.TURBO_QUANT_ENABLED, p.data_ptr(), p.dtype, version)
     cache = model.__dict__.setdefault("_graph_decoders", {})
     dec = cache.get(key)
     if dec is None:
         while len(cache) >= 2:  # bounded: each holds a KV cache and a graph memory pool
             cache.pop(next(iter(cache)))
-        dec = GraphDecoder(model, rows, block_size, temperature, top_k)
+        dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p)
         cache[key] = dec
     return dec

@@ -374,13 +374,17 @@ class NeuralNetworkModel(nn.Module):
         for p in (pos_embeddings or self._find_position_embeddings()):
             p.position_offset = 0
 
-    def _prepare_generation(self, input_context: list, max_new_tokens: int, temperature: float, top_k: int | None):
+    def _prepare_generation(self, input_context: list, max_new_tokens: int, temperature: float, top_k: int | None,
+                            top_p: float | None = None, min_p: float | None = None):
+        samp_ops._check_filters(top_p, min_p)  # a bad range fails before any forward pass
         self.eval()
         device = next(self.parameters()).device
         context = torch.tensor(input_context, dtype=torch.long, device=device)
         if context.ndim == 1:
             context = context.unsqueeze(0)
         top_k_msg = "" if top_k is None else f" top {top_k}"
+        top_k_msg += "" if top_p is None else f" top_p {top_p}"
+        top_k_msg += "" if min_p is None else f" min_p {min_p}"
         log.info(f"Generating at most {max_new_tokens}{top_k_msg} tokens with {temperature} temperature "
                  f"using device {device}")
         softmax_layer = self.layers[-1] if self._is_softmax_last else SoftmaxOnLast(dim=-1)
@@ -389,7 +393,8 @@ class NeuralNetworkModel(nn.Module):
     @torch.inference_mode()
     def _generate_next_token(self, context: Tensor, block_size: int, temperature: float, top_k: int | None,
                              softmax_layer=None, kv_cache: KVCache | None = None,
-                             pos_embeddings: list[PositionEmbedding] | None = None) -> Tensor:
+                             pos_embeddings: list[PositionEmbedding] | None = None, *,
+                             top_p: float | None = None, min_p: float | None = None) -> Tensor:
         if kv_cache is not None and kv_cache.seq_len() > 0:
             if kv_cache.seq_len() >= block_size:
                 # sliding window: clear and re-prefill the last block_size tokens
@@ -406,31 +411,33 @@ class NeuralNetworkModel(nn.Module):
         activations, _ = self(model_input, skip_softmax=True)
         logits = activations[-1]
         last = logits[:, -1, :] if logits.ndim == 3 else logits
-        return samp_ops.sample(last, temperature, top_k)
+        return samp_ops.sample(last, temperature, top_k, top_p=top_p, min_p=min_p)
 
     @torch.inference_mode()
     def generate_tokens(self, input_context: list, block_size: int, max_new_tokens: int,
-                        temperature=1.0, top_k: int | None = None, stop_token: int | None = None) -> list:
+                        temperature=1.0, top_k: int | None = None, stop_token: int | None = None, *,
+                        top_p: float | None = None, min_p: float | None = None) -> list:
         return [t for t in self._generate(input_context, block_size, max_new_tokens, temperature, top_k,
-                                          stop_token, full_context=True)][-1]
+                                          stop_token, full_context=True, top_p=top_p, min_p=min_p)][-1]
 
     @torch.inference_mode()
     def generate_tokens_stream(self, input_context: list, block_size: int, max_new_tokens: int,
-                               temperature=1.0, top_k: int | None = None, stop_token: int | None = None):
+                               temperature=1.0, top_k: int | None = None, stop_token: int | None = None, *,
+                               top_p: float | None = None, min_p: float | None = None):
         log.info("Streaming token generation started")
         for tok in self._generate(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
-                                  full_context=False):
+                                  full_context=False, top_p=top_p, min_p=min_p):
             yield tok
         log.info("Streaming token generation completed")
 
     def _token_bursts(self, context: Tensor, block_size: int, max_new_tokens: int, temperature, top_k,
-                      softmax_layer, burst: int):
+                      softmax_layer, burst: int, *, top_p: float | None = None, min_p: float | None = None):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
         (cache full) run eagerly, exactly as the per-token path."""
         from penroz.models import graph_decode
         rows = context.shape[0]
-        dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k)
+        dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k, top_p, min_p)
         if dec is None:
             cache, pos = self._attach_kv_cache(capacity=block_size)
         else:
@@ -448,7 +455,7 @@ class NeuralNetworkModel(nn.Module):
                 n = cache.seq_len() if cache is not None else 0
                 if dec is None or n == 0 or n >= block_size:
                     new = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache,
-                                                    pos)
+                                                    pos, top_p=top_p, min_p=min_p)
                     for p in pos:
                         p.position_offset = 0
                 else:
@@ -467,8 +474,10 @@ class NeuralNetworkModel(nn.Module):
             else:
                 dec.detach()
 
-    def _generate(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token, full_context):
-        context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k)
+    def _generate(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token, full_context, *,
+                  top_p: float | None = None, min_p: float | None = None):
+        context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k,
+                                                          top_p, min_p)
         rows = context.shape[0]
         generated = []
         done = torch.zeros(rows, dtype=torch.bool)
@@ -476,7 +485,7 @@ class NeuralNetworkModel(nn.Module):
         stopped = False
         with torch.inference_mode():
             for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, softmax_layer,
-                                          burst):
+                                          burst, top_p=top_p, min_p=min_p):
                 toks = new.tolist()
                 for j in range(new.shape[1]):
                     col = [r[j] for r in toks]
@@ -495,9 +504,10 @@ class NeuralNetworkModel(nn.Module):
             yield context[0].tolist()
 
     def _generate_eager(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
-                        full_context):
+                        full_context, *, top_p: float | None = None, min_p: float | None = None):
         """Per-token path (kept for A/B and as the reference-shaped loop)."""
-        context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k)
+        context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k,
+                                                          top_p, min_p)
         cache, pos = self._attach_kv_cache(capacity=block_size)
         rows = context.shape[0]
         generated = []
@@ -505,7 +515,8 @@ class NeuralNetworkModel(nn.Module):
         try:
             with torch.inference_mode():
                 for _ in range(max_new_tokens):
-                    nxt = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache, pos)
+                    nxt = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache, pos,
+                                                    top_p=top_p, min_p=min_p)
                     context = torch.cat((context, nxt.to(context.device)), dim=1)
                     toks = nxt.view(-1).tolist()
                     generated.append(toks[0])
@@ -524,11 +535,13 @@ class NeuralNetworkModel(nn.Module):
 
     @torch.inference_mode()
     def generate_batch(self, input_context: list, block_size: int, max_new_tokens: int, temperature=1.0,
-                       top_k: int | None = None, stop_token: int | None = None) -> list[list[int]]:
+                       top_k: int | None = None, stop_token: int | None = None, *,
+                       top_p: float | None = None, min_p: float | None = None) -> list[list[int]]:
         """All rows' contexts (the reference returns row 0 only — bug 5)."""
-        context, sm = self._prepare_generation(input_context, max_new_tokens, temperature, top_k)
+        context, sm = self._prepare_generation(input_context, max_new_tokens, temperature, top_k, top_p, min_p)
         burst = 32 if stop_token is not None else max_new_tokens
-        for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, sm, burst):
+        for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, sm, burst,
+                                      top_p=top_p, min_p=min_p):
             if stop_token is not None:
                 hit = (new == stop_token).all(dim=0).nonzero()
                 if hit.numel():

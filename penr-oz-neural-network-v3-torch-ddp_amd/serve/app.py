@@ -131,6 +131,10 @@ class GenerateRequest(ModelRequest):
     max_new_tokens: int = Field(..., examples=[10])
     temperature: float = Field(1.0, examples=[1.0])
     top_k: int | None = Field(None, examples=[None])
+    top_p: float | None = Field(None, gt=0, le=1, examples=[None],
+                                description="Nucleus sampling: keep the most likely tokens up to this probability mass")
+    min_p: float | None = Field(None, ge=0, lt=1, examples=[None],
+                                description="Keep tokens at least this likely relative to the most likely one")
     stop_token: int | None = Field(None, examples=[None], description="Token id that halts generation")
     stream: bool = Field(False, examples=[False], description="Stream tokens as text/plain lines")
 
@@ -404,11 +408,12 @@ def model_generate(body: GenerateRequest = Body(...)):
         # chunks) and released by the background task even when the client goes away mid-stream
         from starlette.background import BackgroundTask
         st = _LockedStream(model, model.generate_tokens_stream(body.input, body.block_size, body.max_new_tokens,
-                                                              body.temperature, body.top_k, body.stop_token))
+                                                              body.temperature, body.top_k, body.stop_token,
+                                                              top_p=body.top_p, min_p=body.min_p))
         return StreamingResponse(st.gen, media_type="text/plain", background=BackgroundTask(st.close))
     with _Held(model):
         tokens = model.generate_tokens(body.input, body.block_size, body.max_new_tokens, body.temperature,
-                                       body.top_k, body.stop_token)
+                                       body.top_k, body.stop_token, top_p=body.top_p, min_p=body.min_p)
     return {"tokens": tokens}
 
 
