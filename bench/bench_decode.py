@@ -3,7 +3,12 @@ or a Gemma-3 1B shaped model (RoPE, GQA 4:1, head_dim 256, 262k vocab; HF config
 
 python bench/bench_decode.py [--model gpt2|gemma3-1b] [--batch 64] [--prompt 64] [--new 128] [--turbo]
                              [--top-k 50] [--top-p P] [--min-p P]      (--top-k 0: no top-k)
+                             [--weights bf16|int8] [--ab ROUNDS]
 Prints one JSON line: generated tokens/s over all rows (BASELINE config 4: batch 64 /generate).
+--weights int8: the batch 1-4 decode steps read int8 weight copies (ops/weight_quant.py). --ab ROUNDS:
+both weight formats on one model in this one process, alternating, ROUNDS timed runs each; the line
+then holds both arms (ms/step of every run, median, min, the linears' weight bytes per token and the
+rate they were read at) and the int8 / bf16 ratio of the medians.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,6 +32,8 @@ ap.add_argument("--block", type=int, default=1024)
 ap.add_argument("--top-k", type=int, default=50, help="0: no top-k")
 ap.add_argument("--top-p", type=float, default=None)
 ap.add_argument("--min-p", type=float, default=None)
+ap.add_argument("--weights", default="bf16", choices=["bf16", "int8"], help="decode weight format")
+ap.add_argument("--ab", type=int, default=0, metavar="ROUNDS", help="alternate bf16 and int8 weights, ROUNDS runs each")
 a = ap.parse_args()
 if a.turbo:
     M.create_kv_cache = lambda n, cap=None: KV.TurboQuantKVCache(n, cap)
@@ -46,13 +53,56 @@ if a.dtype == "bf16":
     m.to(dtype=torch.bfloat16)
 ctx = torch.randint(0, V, (a.batch, a.prompt)).tolist()
 samp = dict(temperature=1.0, top_k=a.top_k or None, top_p=a.top_p, min_p=a.min_p)
-m.generate_batch(ctx, a.block, 4, **samp)  # warmup
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-out = m.generate_batch(ctx, a.block, a.new, **samp)
-torch.cuda.synchronize()
-dt = time.perf_counter() - t0
+
+
+def timed(weights: str, new: int) -> float:
+    """Seconds of one generate_batch of ``new`` tokens with this weight format ("" selects bf16
+    whatever PENROZ_DECODE_WEIGHTS says)."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    m.generate_batch(ctx, a.block, new, weight_quant="int8" if weights == "int8" else "", **samp)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def weight_bytes(weights: str) -> int:
+    """Bytes of linear weights one decode step reads: every nn.Linear once (bf16: 2 per weight;
+    int8: 1 per weight + one fp32 scale per row)."""
+    lins = [mod.weight for mod in m.modules() if isinstance(mod, torch.nn.Linear)]
+    if weights == "int8":
+        return sum(w.numel() + 4 * w.shape[0] for w in lins)
+    return sum(w.numel() * w.element_size() for w in lins)
+
+
+def in_effect() -> list:
+    return sorted({d.weight_quant or "bf16" for d in m.__dict__.get("_graph_decoders", {}).values()})
+
+
+if a.ab:
+    arms = {"bf16": [], "int8": []}
+    for w in arms:
+        timed(w, 4)  # warmup: quantised copies, graph capture
+    effect = in_effect()
+    for _ in range(a.ab):
+        for w in arms:  # alternating: both arms see the same drift of clocks and neighbours
+            arms[w].append(timed(w, a.new) / a.new * 1e3)
+    res = {}
+    for w, ms in arms.items():
+        med = sorted(ms)[len(ms) // 2]
+        res[w] = {"ms_per_step": [round(v, 4) for v in ms], "median": round(med, 4), "min": round(min(ms), 4),
+                  "weight_bytes_per_token": weight_bytes(w),
+                  "weight_tb_per_s_at_median": round(weight_bytes(w) / (med * 1e-3) / 1e12, 3)}
+    print(json.dumps({"metric": "decode ms/step, bf16 vs int8 weights, alternating in one process", "arms": res,
+                      "int8_over_bf16_median": round(res["int8"]["median"] / res["bf16"]["median"], 4),
+                      "weights_in_effect": effect, "batch": a.batch, "prompt": a.prompt, "new_tokens": a.new,
+                      "block": a.block, "rounds": a.ab, "top_k": a.top_k or None,
+                      "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
+                      "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
+    sys.exit(0)
+timed(a.weights, 4)  # warmup
+dt = timed(a.weights, a.new)
 print(json.dumps({"metric": "decode tokens/sec (all rows)", "value": a.batch * a.new / dt, "batch": a.batch,
                   "prompt": a.prompt, "new_tokens": a.new, "block": a.block, "ms_per_step": dt / a.new * 1e3, "dtype": a.dtype,
                   "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p,
+                  "weights": a.weights, "weights_in_effect": in_effect(),
                   "kv_cache": "int8-turboquant" if a.turbo else a.dtype, "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))

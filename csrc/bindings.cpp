@@ -105,6 +105,19 @@ void decode_gemm_acc(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tens
                      int64_t flags);
 void decode_gemm(torch::Tensor x, torch::Tensor w, torch::Tensor out, int64_t kind);
 std::tuple<int64_t, int64_t, int64_t, int64_t> decode_gemv_limits();
+// decode_gemv_q8.hip
+void decode_gemv_q8(c10::optional<torch::Tensor> x, c10::optional<torch::Tensor> rin, c10::optional<torch::Tensor> delta,
+                    c10::optional<torch::Tensor> dbias, c10::optional<torch::Tensor> rout,
+                    c10::optional<torch::Tensor> gamma, c10::optional<torch::Tensor> beta, double eps, torch::Tensor q,
+                    torch::Tensor scale, c10::optional<torch::Tensor> bias, torch::Tensor out, int64_t act,
+                    int64_t rows_per_wave);
+void decode_gemv_q8_pair(torch::Tensor x, torch::Tensor q, torch::Tensor scale, torch::Tensor out, int64_t mode,
+                         int64_t kind, int64_t D, int64_t nrot, c10::optional<torch::Tensor> cosv,
+                         c10::optional<torch::Tensor> sinv, int64_t pairs_per_wave);
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t> decode_gemv_q8_limits();
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t> decode_gemv_q8_plan(int64_t M, int64_t N, int64_t K, bool ln,
+                                                                            int64_t rows_per_wave);
+std::tuple<int64_t, int64_t, int64_t> decode_gemv_q8_pair_plan(int64_t N, int64_t K, int64_t pairs_per_wave);
 // adamw.hip
 torch::Tensor update_moments(std::vector<torch::Tensor> ws, std::vector<torch::Tensor> ps);
 // gemm_nt.hip
@@ -266,6 +279,26 @@ PYBIND11_MODULE(penroz_kernels, m) {
         "batched decode (16-64 rows): out = x·wᵀ, or the gated MLP act(x·Wgᵀ)·(x·Wuᵀ) of a packed [gate; up] weight");
   m.def("decode_gemv_limits", &decode_gemv_limits,
         "(rows, K, LN-mode K, paired-row K) limits of decode_gemv / decode_gemv_pair (host only)");
+  m.def("decode_gemv_q8", &decode_gemv_q8, pybind11::arg("x"), pybind11::arg("resid_in"), pybind11::arg("delta"),
+        pybind11::arg("dbias"), pybind11::arg("resid_out"), pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("eps"), pybind11::arg("q"), pybind11::arg("scale"), pybind11::arg("bias"), pybind11::arg("out"),
+        pybind11::arg("act") = 0, pybind11::arg("rows_per_wave") = 0,
+        "int8-weight decode GEMV for 1..4 rows: act(scale ⊙ (x · qᵀ) + bias), or the same on "
+        "LN(resid_in + delta + dbias); q int8 [N, K], scale fp32 [N]");
+  m.def("decode_gemv_q8_pair", &decode_gemv_q8_pair, pybind11::arg("x"), pybind11::arg("q"), pybind11::arg("scale"),
+        pybind11::arg("out"), pybind11::arg("mode"), pybind11::arg("kind") = 0, pybind11::arg("D") = 0,
+        pybind11::arg("nrot") = 0, pybind11::arg("cos") = pybind11::none(), pybind11::arg("sin") = pybind11::none(),
+        pybind11::arg("pairs_per_wave") = 0,
+        "paired-row int8-weight decode GEMV for 1..4 rows: gated MLP (mode 1) or RoPE QKV (mode 2) epilogue");
+  m.def("decode_gemv_q8_limits", &decode_gemv_q8_limits,
+        "(rows, K, LN-mode K, paired-row K, K multiple) limits of decode_gemv_q8 / decode_gemv_q8_pair (host only)");
+  m.def("decode_gemv_q8_plan", &decode_gemv_q8_plan, pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("K"),
+        pybind11::arg("ln") = false, pybind11::arg("rows_per_wave") = 0,
+        "decode_gemv_q8's launch plan: (form 0 half-wave / 1 wave-per-row / 2 LN, rows, row pairs per wave, "
+        "chunks per lane, grid) (host only)");
+  m.def("decode_gemv_q8_pair_plan", &decode_gemv_q8_pair_plan, pybind11::arg("N"), pybind11::arg("K"),
+        pybind11::arg("pairs_per_wave") = 0,
+        "decode_gemv_q8_pair's launch plan: (pairs per wave, chunks per lane, grid) (host only)");
   m.def("update_moments", &update_moments, "per-epoch weight-update diagnostics: [n, 2] (std(w - prev), std(w))");
   m.def("gemm_nt_supported", &gemm_nt_supported, "shapes the native NT GEMM takes (M % 256, N % 128, K % 32, K >= 160)");
   m.def("gemm_nt", &gemm_nt, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("bias"), pybind11::arg("out"),

@@ -167,6 +167,50 @@ inline GemvPairPlan plan_decode_gemv_pair(int N, int K, int pairs_per_wave) {
   return {ppw_ok ? ppw : 0, bucket_of(GemvCplPair{}, (K / 8 + 31) / 32), (N / 2 + ppw - 1) / ppw};
 }
 
+// ---- int8-weight decode GEMV (decode_gemv_q8.hip): W = int8 rows [N, K] + one fp32 scale per row ----
+// A 16-B weight chunk holds 16 weights and pairs with two 16-B x chunks, so K % 16 == 0 and a lane
+// holds half the chunks of the bf16 kernel for the same K. The K limits are the bf16 kernel's.
+constexpr int kGemvQ8KMult = 16;
+using GemvQ8CplHalf = IntList<1, 2, 3, 4, 8, 16>;  // 32 lanes × 16 weights: 512 of K per chunk
+using GemvQ8CplWave = IntList<1, 2, 3, 4, 7, 8>;   // 64 lanes × 16 weights: 1024 of K per chunk
+using GemvQ8CplLn = IntList<1, 2>;                 // K <= kLnMaxK
+using GemvQ8CplPair = IntList<2, 3, 4>;            // K <= kGemvPairMaxK
+static_assert(16 * 512 >= kGemvMaxK && 8 * 1024 >= kGemvMaxK && 2 * 512 >= kLnMaxK && 4 * 512 >= kGemvPairMaxK,
+              "the widest chunk bucket of every form covers its K limit");
+
+// Every load of a wave is in flight before the first use, so a lane holds all its chunks at once:
+// 4 VGPRs per weight chunk and row (pair) of the wave, 8 per chunk and x row. Combinations above
+// this budget (of the 512 VGPRs a one-wave workgroup can have) are not instantiated: they would
+// spill to scratch. The plan below never picks one.
+constexpr int kGemvQ8RegBudget = 416;
+constexpr bool gemv_q8_fits(int m, int rp, int cpl) { return cpl * (4 * rp + 8 * m) <= kGemvQ8RegBudget; }
+
+// plan_decode_gemv's shape rule (8 rows per wave for the vocabulary projection, else 2; the
+// wave-per-row form for the bf16-x GEMVs below 16k rows), without its A/B environment switches.
+// rows_per_wave 2, 4 or 8 is an upper bound here: it is halved until the wave's registers fit, and a
+// shape whose single row pair does not fit takes the wave-per-row form (half the chunks per lane).
+inline GemvPlan plan_decode_gemv_q8(int M, int N, int K, bool ln, int rows_per_wave) {
+  int rpw = rows_per_wave > 0 ? rows_per_wave : (N >= 16384 ? 8 : 2);
+  const bool rpw_ok = rpw == 2 || rpw == 4 || rpw == 8;
+  const int chunks = K / kGemvQ8KMult;
+  bool wave_row = !ln && rows_per_wave <= 0 && N < 16384;
+  const int cpl = (chunks + 31) / 32;
+  const int cb = ln ? bucket_of(GemvQ8CplLn{}, cpl) : bucket_of(GemvQ8CplHalf{}, cpl);
+  if (!ln && !wave_row && rpw_ok && cb > 0) {
+    while (rpw > 2 && !gemv_q8_fits(M, rpw / 2, cb)) rpw /= 2;
+    wave_row = !gemv_q8_fits(M, rpw / 2, cb);
+  }
+  if (wave_row) return {GemvForm::WaveRow, M, rpw_ok ? 1 : 0, bucket_of(GemvQ8CplWave{}, (chunks + 63) / 64), N};
+  return {ln ? GemvForm::LN : GemvForm::HalfWave, M, rpw_ok ? rpw / 2 : 0, cb, (N + rpw - 1) / rpw};
+}
+
+inline GemvPairPlan plan_decode_gemv_q8_pair(int N, int K, int pairs_per_wave) {
+  int ppw = pairs_per_wave;
+  if (ppw <= 0) ppw = N / 2 >= 16384 ? 4 : N / 2 <= 1024 ? 1 : 2;
+  const bool ppw_ok = ppw == 1 || ppw == 2 || ppw == 4;
+  return {ppw_ok ? ppw : 0, bucket_of(GemvQ8CplPair{}, (K / kGemvQ8KMult + 31) / 32), (N / 2 + ppw - 1) / ppw};
+}
+
 // Automatic split-K of the skinny kernels: workgroups ~ 192 when the column tiles alone (16 wide
 // for skinny_gemm, 32 for skinny_qkv_rope) are too few; every split keeps >= 4 k-steps of 32.
 inline int skinny_auto_split(int ntiles, int steps) {

@@ -29,6 +29,24 @@ inline const bf16* la_weight(const char* who, const torch::Tensor& w, int n_mult
   return reinterpret_cast<const bf16*>(w.data_ptr());
 }
 
+// int8 weight rows [N, K] + one fp32 scale per row [N] (weight-only quantisation, decode_gemv_q8.hip):
+// contiguous, rows 16-B aligned (K % 16 == 0: a 16-B chunk is 16 weights), N a multiple of n_mult
+struct Q8Weight {
+  const int8_t* q = nullptr;
+  const float* scale = nullptr;
+  int N = 0, K = 0;
+};
+
+inline Q8Weight la_weight_q8(const char* who, const torch::Tensor& q, const torch::Tensor& scale, int n_mult = 1) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kInt8 && q.dim() == 2 && q.is_contiguous() && la_aligned(q, 16) &&
+                  q.size(0) >= 1 && q.size(1) >= 16 && q.size(1) % 16 == 0 && q.size(0) % n_mult == 0,
+              who, ": int8 contiguous 16-B aligned W [N, K], K % 16 == 0, N % ", n_mult, " == 0");
+  TORCH_CHECK(scale.is_cuda() && scale.device() == q.device() && scale.scalar_type() == torch::kFloat32 &&
+                  scale.is_contiguous() && scale.numel() == q.size(0),
+              who, ": fp32 contiguous row scales [N = ", q.size(0), "] on W's device");
+  return {q.data_ptr<int8_t>(), scale.data_ptr<float>(), (int)q.size(0), (int)q.size(1)};
+}
+
 // optional bf16 bias [N] (nullptr when absent); decode_linear.hip's MFMA epilogues read it in 8-B pieces
 inline const bf16* la_bias(const char* who, const OptTensor& bias, int N, int align = 2) {
   if (!la_defined(bias)) return nullptr;

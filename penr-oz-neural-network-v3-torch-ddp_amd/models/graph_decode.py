@@ -26,6 +26,9 @@ between steps lives on the device:
   (``csrc/kernels/skinny_gemm.hip``): called explicitly by the decode programs, or — for the
   module-forward fallback — through ``ops/gemm.py: decode_gemms(model)``, which re-routes only
   that model's own ``nn.Linear`` instances for the capture.
+* with ``weight_quant="int8"`` the decode programs' batch 1-4 step reads int8 copies of every
+  linear's weight (``ops/weight_quant.py``, ``csrc/kernels/decode_gemv_q8.hip``), built per weight
+  version before the warm-up step; ``GraphDecoder.weight_quant`` records whether that is in effect.
 
 The host only tracks the cache length (one per replay) to switch to the reference's
 sliding-window re-prefill when the window is full, and copies each burst of tokens back once
@@ -52,6 +55,7 @@ from penroz.ops import gemm as gemm_ops
 from penroz.ops import norms as norm_ops
 from penroz.ops import rope as rope_ops
 from penroz.ops import sampling as samp_ops
+from penroz.ops import weight_quant as wq_ops
 
 log = logging.getLogger(__name__)
 
@@ -95,6 +99,12 @@ def _gemv_limits():
     limits (csrc/kernels/host_plan.h), read here instead of repeated; wider linears take the
     skinny GEMM. Needs the built extension (callers ask ``_ext.available()`` first)."""
     return _ext.kernels().decode_gemv_limits()
+
+
+def _gemv_q8_limits():
+    """(rows, K, LN-mode K, paired-row K, K multiple) of the int8-weight decode GEMV launchers
+    (decode_gemv_q8 / decode_gemv_q8_pair), their own constants as well."""
+    return _ext.kernels().decode_gemv_q8_limits()
 
 
 class _GraphMode:
@@ -253,6 +263,22 @@ class _GemvSteps(_PlainSteps):
     head = norm_linear
 
 
+class _GemvQ8Steps(_PlainSteps):
+    """``_GemvSteps`` on the int8 weight copies (``GPTDecodeProgram.q8``): the same five launches per
+    block, each reading half the weight bytes. The embedding stays its own kernel (the int8 GEMV has
+    no gather prologue)."""
+
+    def norm_linear(self, ln, lin, gelu: bool = False) -> Tensor:
+        x, delta, dbias, out = self._take()
+        return gemm_ops.decode_gemv_q8_ln(x, ln, self.prog.q8[id(lin)], lin.bias, self.act if gelu else 0,
+                                          delta=delta, dbias=dbias, resid_out=out)
+
+    def project(self, h: Tensor, lin, fbias: Tensor) -> None:
+        self._defer(gemm_ops.decode_gemv_q8(h, self.prog.q8[id(lin)]), fbias)
+
+    head = norm_linear
+
+
 class _BatchedSteps(_PlainSteps):
     """Above FUSED_MAX_ROWS rows, per block: [LN1 + QKV GEMM + bias] → decode attention (K/V append
     fused) → [proj GEMM + bias, added into the fp32 residual in place] → [LN2 + fc GEMM + bias +
@@ -291,6 +317,7 @@ class GPTDecodeProgram:
         # launches an extra bias-broadcast copy per call)
         self.out_bias = [(b.proj.bias.float(), b.fc2.bias.float()) for b in spec.blocks]
         self.device = dev
+        self.q8: dict | None = None  # id(linear) -> (q, scale) once enable_q8 admitted the step
 
     @staticmethod
     def build(model):
@@ -318,6 +345,27 @@ class GPTDecodeProgram:
         return (1 <= rows <= min(max_rows, GEMV_MAX_ROWS) and sp.C % 8 == 0 and sp.C <= max_ln_k
                 and sp.blocks[0].fc.out_features % 8 == 0 and sp.gelu_approx in ("none", "tanh"))
 
+    def _linears(self):
+        sp = self.spec
+        return [lin for b in sp.blocks for lin in (b.qkv, b.proj, b.fc, b.fc2)] + [sp.head]
+
+    def enable_q8(self, rows: int) -> bool:
+        """Int8 weights for this row count: admitted when the step runs the decode GEMVs and every
+        linear's K fits the int8 kernel (a multiple of its chunk, within its limits) — all of the
+        step or none of it. Builds (or finds) the quantised copies now, outside any capture."""
+        if not self._gemv_ok(rows):
+            return False
+        max_rows, max_k, max_ln_k, _, k_mult = _gemv_q8_limits()
+        sp = self.spec
+        for b in sp.blocks:  # qkv / fc (and the head) in LN mode on K = C; proj / fc2 plain
+            if (b.qkv.in_features != sp.C or b.fc.in_features != sp.C or b.proj.in_features > max_k
+                    or b.fc2.in_features > max_k or b.proj.in_features % k_mult or b.fc2.in_features % k_mult):
+                return False
+        if rows > max_rows or sp.C % k_mult or sp.C > max_ln_k or sp.head.in_features != sp.C:
+            return False
+        self.q8 = {id(lin): wq_ops.linear_q8(lin) for lin in self._linears()}
+        return True
+
     def _fused_ok(self, rows: int) -> bool:
         sp = self.spec
         return (FUSED_LN_LINEAR and 1 <= rows <= min(64, FUSED_MAX_ROWS) and sp.C % 32 == 0 and sp.C <= 1024
@@ -333,7 +381,10 @@ class GPTDecodeProgram:
         """idx [rows, 1] -> logits [rows, V] (bf16); appends this step's K/V at cache.pos_t."""
         sp = self.spec
         rows, C, H, D = idx.shape[0], sp.C, sp.H, sp.D
-        if (rows == 1 and self._gemv_ok(rows) and sp.wte.weight.dtype == torch.bfloat16
+        if self.q8 is not None:
+            x = fused_ops.embedding_fwd(idx, sp.wte.weight, sp.wpe.weight, 0, pos_dev=cache.pos_t)  # fp32 [rows, C]
+            s = _GemvQ8Steps(self, x, torch.empty_like(x))
+        elif (rows == 1 and self._gemv_ok(rows) and sp.wte.weight.dtype == torch.bfloat16
                 and sp.wpe.weight.dtype == torch.bfloat16):
             # the first block's LN + QKV GEMV reads the embedding row itself (no embedding kernel):
             # B = 1 0.3548 / 0.3564 -> 0.3520 / 0.3544 ms; at 4 rows every workgroup's four-row
@@ -407,7 +458,9 @@ class GemmaDecodeProgram:
                 in_norm=in_norm, qkv=qkv.weight, attn=attn, o=o.weight, pre_mlp=pre_mlp, mode=mode,
                 post_attn=b.post_attn_norm, post_mlp=b.post_mlp_norm,
                 gu=_packed_gate_up(mlp), down=mlp.down_proj.weight,
-                kind=act_ops._GATED[mlp.act_kind]))
+                kind=act_ops._GATED[mlp.act_kind], mods=(qkv, o, mlp)))
+        self.q8 = False  # enable_q8: the blocks then carry int8 copies (qkv_q8, o_q8, gu_q8, down_q8)
+        self.head_q8 = None
 
     @staticmethod
     def build(model):
@@ -459,7 +512,36 @@ class GemmaDecodeProgram:
         return (1 <= rows <= min(max_rows, GEMV_MAX_ROWS) and C % 8 == 0 and C <= max_pair_k
                 and all(b["o"].shape[1] <= max_k and b["down"].shape[1] <= max_k for b in self.blocks))
 
-    def _lin(self, x: Tensor, w: Tensor, gemv: bool) -> Tensor:
+    def enable_q8(self, rows: int) -> bool:
+        """Int8 weights for this row count: admitted when the step runs the decode GEMVs with their
+        RoPE / gated epilogues and every linear's K fits the int8 kernel — all of the step or none
+        of it. Builds (or finds) the quantised copies now, outside any capture; the gate|up pair is
+        quantised after packing (one [2I, K] operand, one [2I] scale)."""
+        C = self.emb.embedding_dim
+        if not (DECODE_EPILOGUES and self._gemv_ok(rows, C)):
+            return False
+        max_rows, max_k, _, max_pair_k, k_mult = _gemv_q8_limits()
+        if rows > max_rows or C % k_mult or C > max_pair_k or self.head.weight.shape[1] != C:
+            return False
+        for b in self.blocks:
+            a = b["attn"]
+            if (b["qkv"].shape[1] != C or b["gu"].shape[1] != C or b["gu"].shape[0] % 2
+                    or any(b[k].shape[1] % k_mult or b[k].shape[1] > max_k for k in ("o", "down"))
+                    or (a.rope_theta is not None and (a.head_dim % 2 or b["qkv"].shape[0] % a.head_dim))):
+                return False
+        for b in self.blocks:
+            qkv, o, mlp = b["mods"]
+            b["qkv_q8"], b["o_q8"] = wq_ops.linear_q8(qkv), wq_ops.linear_q8(o)
+            b["down_q8"] = wq_ops.linear_q8(mlp.down_proj)
+            b["gu_q8"] = wq_ops.cached_q8(mlp, "_packed_gu_q8", (mlp.gate_proj.weight, mlp.up_proj.weight),
+                                          lambda mlp=mlp: _packed_gate_up(mlp))
+        self.head_q8 = wq_ops.linear_q8(self.head)
+        self.q8 = True
+        return True
+
+    def _lin(self, x: Tensor, w: Tensor, gemv: bool, q8=None) -> Tensor:
+        if q8 is not None:
+            return gemm_ops.decode_gemv_q8(x.contiguous(), q8)
         if gemv and w.shape[1] % 8 == 0 and w.shape[1] <= _gemv_limits()[1]:
             return gemm_ops.decode_gemv(x.contiguous(), w)
         return _linear(x, w)
@@ -471,9 +553,11 @@ class GemmaDecodeProgram:
         a, rows = b["attn"], y.shape[0]
         H, Hkv, D = a.num_heads, a.num_kv_heads, a.head_dim
         if a.rope_theta is None:
-            return self._lin(y, b["qkv"], gemv), None
+            return self._lin(y, b["qkv"], gemv, b["qkv_q8"] if self.q8 else None), None
         inv = a._inv_freq(D, y.device)
         cos, sin = cache.rope_table((a.rope_theta, D), inv, 1)
+        if self.q8:
+            return gemm_ops.decode_gemv_q8_rope(y.contiguous(), b["qkv_q8"], cos, sin, D, H + Hkv), None
         if gemv and DECODE_EPILOGUES and D % 2 == 0:
             return gemm_ops.decode_gemv_rope(y.contiguous(), b["qkv"], cos, sin, D, H + Hkv), None
         if DECODE_EPILOGUES and rows <= SKINNY_MAX_ROWS and gemm_ops.skinny_qkv_rope_ok(y, b["qkv"], D):
@@ -485,6 +569,8 @@ class GemmaDecodeProgram:
                                        table=(cos, sin)), None
 
     def _gate_up(self, b, y: Tensor, gemv: bool) -> Tensor:
+        if self.q8:
+            return gemm_ops.decode_gemv_q8_gated(y.contiguous(), b["gu_q8"], b["kind"])
         if gemv and DECODE_EPILOGUES:
             return gemm_ops.decode_gemv_gated(y.contiguous(), b["gu"], b["kind"])
         return _gated(y, b["gu"], b["kind"])
@@ -503,16 +589,16 @@ class GemmaDecodeProgram:
             qkv, rope = self._qkv(b, y, cache, gemv)
             q, k, v = _qkv_views(qkv, H, Hkv, D)
             att = cache.attend(l, q, k, v) if rope is None else cache.attend_rope(l, q, k, v, *rope)
-            o = self._lin(att.view(rows, H * D), b["o"], gemv)
+            o = self._lin(att.view(rows, H * D), b["o"], gemv, b["o_q8"] if self.q8 else None)
             pa, pm, pre = b["post_attn"], b["post_mlp"], b["pre_mlp"]
             h, y = K.rms_residual(x, o, pa.weight if pa is not None else None, pre.weight, b["mode"],
                                   pa.eps if pa is not None else 0.0, pre.eps)
             g = self._gate_up(b, y, gemv)
-            d = self._lin(g, b["down"], gemv)
+            d = self._lin(g, b["down"], gemv, b["down_q8"] if self.q8 else None)
             nxt = self.blocks[l + 1]["in_norm"] if l + 1 < len(self.blocks) else self.norm_f
             x, y = K.rms_residual(h, d, pm.weight if pm is not None else None, nxt.weight, b["mode"],
                                   pm.eps if pm is not None else 0.0, nxt.eps)
-        return self._lin(y, self.head.weight, gemv)
+        return self._lin(y, self.head.weight, gemv, self.head_q8 if self.q8 else None)
 
 
 # 17-32 rows: decode_linear.hip decode_gemm (16 rows × 16 columns per workgroup, K split over its
@@ -589,7 +675,7 @@ class GraphDecoder:
     """Static decode state + the captured step graph for ``rows`` sequences."""
 
     def __init__(self, model, rows: int, capacity: int, temperature: float, top_k: int | None,
-                 top_p: float | None = None, min_p: float | None = None):
+                 top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None):
         # weak: the model caches its decoders (model.__dict__), so a strong reference would make a
         # cycle that only the cyclic GC frees — and a collection that runs while ANOTHER graph is
         # being captured destroys this one's graph mid-capture (a hard abort)
@@ -613,6 +699,15 @@ class GraphDecoder:
         attn_ops.decode_counters(self.device)  # (the decode attention's split-merge counters too)
         gemm_ops.load_tuned_gemms()  # measured hipBLASLt solutions for the decode-shaped GEMMs too
         self.program = GPTDecodeProgram.build(model) or GemmaDecodeProgram.build(model)
+        # the weight format in effect: "int8" when asked for AND this decoder's step qualifies (a
+        # decode program at 1-4 rows whose linears all fit the int8 GEMV); the quantised copies exist
+        # from here on, before the warm-up step and the capture
+        self.weight_quant = None
+        if wq_ops.resolve(weight_quant or "") == "int8":
+            if self.program is not None and self.program.enable_q8(rows):
+                self.weight_quant = "int8"
+            else:
+                _log_q8_unused(rows, self.program)
         self._done_t = torch.zeros(1, dtype=torch.int32, device=self.device)  # sample_step's arrival counter
 
     # ------------------------------------------------------------------ cache attachment
@@ -739,6 +834,20 @@ class GraphDecoder:
         return self.out[:, :n_steps]
 
 
+_q8_unused_logged = False
+
+
+def _log_q8_unused(rows: int, program) -> None:
+    """Once per process: int8 decode weights were asked for and this step keeps bf16 weights."""
+    global _q8_unused_logged
+    if _q8_unused_logged:
+        return
+    _q8_unused_logged = True
+    why = ("the model has no decode program (bf16 GPT-2-pattern or Gemma-family)" if program is None
+           else f"{rows} rows or a linear's K is outside the int8 decode GEMV's limits")
+    log.info(f"int8 decode weights requested, but the step keeps bf16 weights: {why}")
+
+
 def _normalise_filters(temperature: float, top_p: float | None, min_p: float | None):
     """(top_p, min_p) with the values that mean "no filter" — and both at temperature 0, which
     ignores them — folded to None, so equal behaviour shares one captured graph."""
@@ -749,8 +858,10 @@ def _normalise_filters(temperature: float, top_p: float | None, min_p: float | N
 
 
 def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: int | None,
-                top_p: float | None = None, min_p: float | None = None) -> GraphDecoder | None:
-    """Cached per model and (rows, block size, sampling settings, weights identity); None when the
+                top_p: float | None = None, min_p: float | None = None,
+                weight_quant: str | None = None) -> GraphDecoder | None:
+    """Cached per model and (rows, block size, sampling settings, weights identity, weight format in
+    effect for ``weight_quant`` — as ``ops.weight_quant.resolve`` returned it); None when the
     model does not qualify (CPU, no attention, RoPE head_dim without a decode kernel) or ``PENROZ_GRAPH_DECODE=0``."""
     if not applicable(model):
         return None
@@ -758,13 +869,26 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
     # weights identity AND version: in-place updates (training) re-capture, so nothing captured
     # (e.g. LayerNorm's cached fp32 weight copies for bf16 models) can go stale
     version = sum(q._version for q in model.parameters())
-    key = (rows, block_size, float(temperature), top_k if temperature else None,
-           *_normalise_filters(temperature, top_p, min_p), kvc.TURBO_QUANT_ENABLED, p.data_ptr(), p.dtype, version)
+    base = (rows, block_size, float(temperature), top_k if temperature else None,
+            *_normalise_filters(temperature, top_p, min_p), kvc.TURBO_QUANT_ENABLED, p.data_ptr(), p.dtype, version)
     cache = model.__dict__.setdefault("_graph_decoders", {})
-    dec = cache.get(key)
+    # the key holds the weight format IN EFFECT: a request for int8 that this step cannot honour
+    # (more than 4 rows, no decode program, a K that does not fit) shares the bf16 decoder instead of
+    # building a second identical one; which (rows, ...) settings those are is remembered per model
+    unused = model.__dict__.setdefault("_q8_no_effect", set())
+    if weight_quant is not None and base in unused:
+        weight_quant = None
+    dec = cache.get(base + (weight_quant,))
     if dec is None:
+        dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p, weight_quant)
+        if dec.weight_quant != weight_quant:  # asked for int8, runs bf16
+            if len(unused) >= 64:
+                unused.clear()
+            unused.add(base)
+            twin = cache.get(base + (dec.weight_quant,))
+            if twin is not None:
+                return twin
         while len(cache) >= 2:  # bounded: each holds a KV cache and a graph memory pool
             cache.pop(next(iter(cache)))
-        dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p)
-        cache[key] = dec
+        cache[base + (dec.weight_quant,)] = dec
     return dec

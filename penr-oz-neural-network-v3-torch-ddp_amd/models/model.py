@@ -45,6 +45,7 @@ from penroz.models.layers import CausalSelfAttention, PositionEmbedding, Softmax
 from penroz.models.mapper import Mapper
 from penroz.ops import sampling as samp_ops
 from penroz.ops import fused as fused_ops
+from penroz.ops import weight_quant as wq_ops
 from penroz.parallel import dist as ddp
 from penroz.parallel.launcher import maybe_inject_fault
 from penroz.utils import checkpoint as ckpt
@@ -375,8 +376,10 @@ class NeuralNetworkModel(nn.Module):
             p.position_offset = 0
 
     def _prepare_generation(self, input_context: list, max_new_tokens: int, temperature: float, top_k: int | None,
-                            top_p: float | None = None, min_p: float | None = None):
+                            top_p: float | None = None, min_p: float | None = None,
+                            weight_quant: str | None = None):
         samp_ops._check_filters(top_p, min_p)  # a bad range fails before any forward pass
+        wq_ops.resolve(weight_quant)  # (and an unknown decode weight format)
         self.eval()
         device = next(self.parameters()).device
         context = torch.tensor(input_context, dtype=torch.long, device=device)
@@ -416,28 +419,35 @@ class NeuralNetworkModel(nn.Module):
     @torch.inference_mode()
     def generate_tokens(self, input_context: list, block_size: int, max_new_tokens: int,
                         temperature=1.0, top_k: int | None = None, stop_token: int | None = None, *,
-                        top_p: float | None = None, min_p: float | None = None) -> list:
+                        top_p: float | None = None, min_p: float | None = None,
+                        weight_quant: str | None = None) -> list:
+        """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
+        "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS."""
         return [t for t in self._generate(input_context, block_size, max_new_tokens, temperature, top_k,
-                                          stop_token, full_context=True, top_p=top_p, min_p=min_p)][-1]
+                                          stop_token, full_context=True, top_p=top_p, min_p=min_p,
+                                          weight_quant=weight_quant)][-1]
 
     @torch.inference_mode()
     def generate_tokens_stream(self, input_context: list, block_size: int, max_new_tokens: int,
                                temperature=1.0, top_k: int | None = None, stop_token: int | None = None, *,
-                               top_p: float | None = None, min_p: float | None = None):
+                               top_p: float | None = None, min_p: float | None = None,
+                               weight_quant: str | None = None):
         log.info("Streaming token generation started")
         for tok in self._generate(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
-                                  full_context=False, top_p=top_p, min_p=min_p):
+                                  full_context=False, top_p=top_p, min_p=min_p, weight_quant=weight_quant):
             yield tok
         log.info("Streaming token generation completed")
 
     def _token_bursts(self, context: Tensor, block_size: int, max_new_tokens: int, temperature, top_k,
-                      softmax_layer, burst: int, *, top_p: float | None = None, min_p: float | None = None):
+                      softmax_layer, burst: int, *, top_p: float | None = None, min_p: float | None = None,
+                      weight_quant: str | None = None):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
         (cache full) run eagerly, exactly as the per-token path."""
         from penroz.models import graph_decode
         rows = context.shape[0]
-        dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k, top_p, min_p)
+        dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k, top_p, min_p,
+                                       wq_ops.resolve(weight_quant))
         if dec is None:
             cache, pos = self._attach_kv_cache(capacity=block_size)
         else:
@@ -475,9 +485,9 @@ class NeuralNetworkModel(nn.Module):
                 dec.detach()
 
     def _generate(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token, full_context, *,
-                  top_p: float | None = None, min_p: float | None = None):
+                  top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None):
         context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k,
-                                                          top_p, min_p)
+                                                          top_p, min_p, weight_quant)
         rows = context.shape[0]
         generated = []
         done = torch.zeros(rows, dtype=torch.bool)
@@ -485,7 +495,7 @@ class NeuralNetworkModel(nn.Module):
         stopped = False
         with torch.inference_mode():
             for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, softmax_layer,
-                                          burst, top_p=top_p, min_p=min_p):
+                                          burst, top_p=top_p, min_p=min_p, weight_quant=weight_quant):
                 toks = new.tolist()
                 for j in range(new.shape[1]):
                     col = [r[j] for r in toks]
@@ -536,12 +546,14 @@ class NeuralNetworkModel(nn.Module):
     @torch.inference_mode()
     def generate_batch(self, input_context: list, block_size: int, max_new_tokens: int, temperature=1.0,
                        top_k: int | None = None, stop_token: int | None = None, *,
-                       top_p: float | None = None, min_p: float | None = None) -> list[list[int]]:
+                       top_p: float | None = None, min_p: float | None = None,
+                       weight_quant: str | None = None) -> list[list[int]]:
         """All rows' contexts (the reference returns row 0 only — bug 5)."""
-        context, sm = self._prepare_generation(input_context, max_new_tokens, temperature, top_k, top_p, min_p)
+        context, sm = self._prepare_generation(input_context, max_new_tokens, temperature, top_k, top_p, min_p,
+                                               weight_quant)
         burst = 32 if stop_token is not None else max_new_tokens
         for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, sm, burst,
-                                      top_p=top_p, min_p=min_p):
+                                      top_p=top_p, min_p=min_p, weight_quant=weight_quant):
             if stop_token is not None:
                 hit = (new == stop_token).all(dim=0).nonzero()
                 if hit.numel():

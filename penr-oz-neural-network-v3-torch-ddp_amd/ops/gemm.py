@@ -284,6 +284,41 @@ def decode_gemv_rope(x: Tensor, w: Tensor, cos: Tensor, sin: Tensor, D: int, nro
     return out
 
 
+# The same four on an int8 weight operand ``qw`` = (q int8 [N, K], scale fp32 [N])
+# (csrc/kernels/decode_gemv_q8.hip, ops/weight_quant.py): half the weight bytes per token.
+def decode_gemv_q8(x: Tensor, qw, bias: Tensor | None = None, act: int = 0) -> Tensor:
+    """act(scale ⊙ (x·qᵀ) + bias) for 1-4 bf16 rows."""
+    out = _decode_out(x, qw[0].shape[0])
+    kernels().decode_gemv_q8(x=x, resid_in=None, delta=None, dbias=None, resid_out=None, gamma=None, beta=None,
+                             eps=0.0, q=qw[0], scale=qw[1], bias=bias, out=out, act=act)
+    return out
+
+
+def decode_gemv_q8_ln(resid: Tensor, ln, qw, bias: Tensor | None, act: int = 0, delta: Tensor | None = None,
+                      dbias: Tensor | None = None, resid_out: Tensor | None = None) -> Tensor:
+    """``decode_gemv_q8`` with the residual add + LayerNorm as its prologue."""
+    out = _decode_out(resid, qw[0].shape[0])
+    kernels().decode_gemv_q8(x=None, resid_in=resid, delta=delta, dbias=dbias, resid_out=resid_out, gamma=ln[0],
+                             beta=ln[1], eps=ln[2], q=qw[0], scale=qw[1], bias=bias, out=out, act=act)
+    return out
+
+
+def decode_gemv_q8_gated(x: Tensor, qw, kind: int) -> Tensor:
+    """Paired-row int8-weight GEMV of the packed [gate; up] operand, 1-4 rows: act(x·Wgᵀ) ⊙ (x·Wuᵀ)."""
+    out = _decode_out(x, qw[0].shape[0] // 2)
+    kernels().decode_gemv_q8_pair(x=x, q=qw[0], scale=qw[1], out=out, mode=1, kind=kind)
+    return out
+
+
+def decode_gemv_q8_rope(x: Tensor, qw, cos: Tensor, sin: Tensor, D: int, nrot: int) -> Tensor:
+    """Paired-row int8-weight GEMV of the QKV operand, 1-4 rows, with RoPE (one position's cos / sin)
+    applied to the first ``nrot`` heads of size ``D`` in its epilogue."""
+    out = _decode_out(x, qw[0].shape[0])
+    kernels().decode_gemv_q8_pair(x=x, q=qw[0], scale=qw[1], out=out, mode=2, kind=0, D=D, nrot=nrot, cos=cos,
+                                  sin=sin)
+    return out
+
+
 def decode_ln_linear(resid: Tensor, ln, w: Tensor, bias: Tensor | None, act: int = 0, delta: Tensor | None = None,
                      dbias: Tensor | None = None, resid_out: Tensor | None = None) -> Tensor:
     """act(LN(resid + delta + dbias)·wᵀ + bias) for ≤ 64 rows, K ≤ 1024 on the skinny MFMA kernel:

@@ -35,6 +35,7 @@ from pydantic import BaseModel, Field
 
 from penroz.models.mapper import Mapper
 from penroz.models.model import NeuralNetworkModel
+from penroz.ops import weight_quant as wq_ops
 from penroz.parallel import launcher
 from penroz.utils.loaders import Downloader, Loader
 from penroz.utils.tokenizers import Tokenizer
@@ -136,6 +137,9 @@ class GenerateRequest(ModelRequest):
     min_p: float | None = Field(None, ge=0, lt=1, examples=[None],
                                 description="Keep tokens at least this likely relative to the most likely one")
     stop_token: int | None = Field(None, examples=[None], description="Token id that halts generation")
+    weight_quant: str | None = Field(None, examples=[None],
+                                     description="Decode weight format: \"int8\" (weight-only int8 for batch 1-4 "
+                                                 "decode steps), \"\" (bf16), null: PENROZ_DECODE_WEIGHTS")
     stream: bool = Field(False, examples=[False], description="Stream tokens as text/plain lines")
 
 
@@ -169,6 +173,11 @@ async def gzip_decompression_middleware(request: Request, call_next):
             return {"type": "http.request", "body": body, "more_body": False}
         request._receive = receive
     return await call_next(request)
+
+
+# the process default of /generate's weight_quant is checked once, here: a mistyped
+# PENROZ_DECODE_WEIGHTS stops the server at start-up instead of failing every request with a 400
+wq_ops.resolve(None)
 
 
 @app.exception_handler(Exception)
@@ -402,6 +411,8 @@ def evaluate_model(body: EvaluateRequest = Body(...)):
 
 @app.post("/generate/")
 def model_generate(body: GenerateRequest = Body(...)):
+    if body.weight_quant is not None:  # an unknown format is a 400 before the model is touched (streams too)
+        wq_ops.resolve(body.weight_quant)
     model = load_for_serving(body.model_id)
     if body.stream:
         # the lock is held for the stream's whole lifetime (the KV cache stays attached between
@@ -409,11 +420,13 @@ def model_generate(body: GenerateRequest = Body(...)):
         from starlette.background import BackgroundTask
         st = _LockedStream(model, model.generate_tokens_stream(body.input, body.block_size, body.max_new_tokens,
                                                               body.temperature, body.top_k, body.stop_token,
-                                                              top_p=body.top_p, min_p=body.min_p))
+                                                              top_p=body.top_p, min_p=body.min_p,
+                                                              weight_quant=body.weight_quant))
         return StreamingResponse(st.gen, media_type="text/plain", background=BackgroundTask(st.close))
     with _Held(model):
         tokens = model.generate_tokens(body.input, body.block_size, body.max_new_tokens, body.temperature,
-                                       body.top_k, body.stop_token, top_p=body.top_p, min_p=body.min_p)
+                                       body.top_k, body.stop_token, top_p=body.top_p, min_p=body.min_p,
+                                       weight_quant=body.weight_quant)
     return {"tokens": tokens}
 
 
