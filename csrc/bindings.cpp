@@ -66,6 +66,8 @@ void sample_step(torch::Tensor logits, double temperature, int64_t top_k, torch:
                  torch::Tensor idx_out, torch::Tensor out_buf, c10::optional<torch::Tensor> adv_a,
                  c10::optional<torch::Tensor> adv_b, c10::optional<torch::Tensor> done, double top_p, double min_p);
 void decode_advance(torch::Tensor a, torch::Tensor b, torch::Tensor c);
+std::tuple<int64_t, int64_t, int64_t, int64_t> sample_plan(at::ScalarType dtype, int64_t B, int64_t V, double temperature,
+                                                           int64_t top_k, bool filtered, c10::optional<int64_t> min_rows);
 // decode_attn.hip
 torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c10::optional<torch::Tensor> k_scale,
                           c10::optional<torch::Tensor> v_scale, int64_t S, int64_t q_offset, double scale,
@@ -74,6 +76,8 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c
                           c10::optional<torch::Tensor> counters, c10::optional<torch::Tensor> rope_cos,
                           c10::optional<torch::Tensor> rope_sin);
 bool decode_small_applies(int64_t B, int64_t Tq, int64_t H, int64_t Hkv, int64_t D, int64_t S);
+std::tuple<bool, int64_t, int64_t, bool> decode_attn_plan(int64_t B, int64_t Tq, int64_t H, int64_t Hkv, int64_t D,
+                                                          int64_t S, bool bf16_plain, int64_t counters);
 // elementwise.hip (deferred.h)
 void set_deferred_reduce_stream(int64_t stream, int64_t device);
 // decode_attn.hip
@@ -225,12 +229,19 @@ PYBIND11_MODULE(penroz_kernels, m) {
         pybind11::arg("adv_b") = pybind11::none(), pybind11::arg("done") = pybind11::none(), pybind11::arg("top_p") = 1.0,
         pybind11::arg("min_p") = 0.0);
   m.def("decode_advance", &decode_advance, "+1 on three device int64 scalars");
+  m.def("sample_plan", &sample_plan, pybind11::arg("dtype"), pybind11::arg("B"), pybind11::arg("V"),
+        pybind11::arg("temperature"), pybind11::arg("top_k"), pybind11::arg("filtered") = false,
+        pybind11::arg("two_stage_min_rows") = pybind11::none(),
+        "the sampler's launch plan: (path 0 two-stage / 1 register / 2 streaming, slice, parts, part top_k) (host only)");
   m.def("decode_attn", &decode_attn, pybind11::arg("q"), pybind11::arg("kc"), pybind11::arg("vc"), pybind11::arg("k_scale"),
         pybind11::arg("v_scale"), pybind11::arg("S"), pybind11::arg("q_offset"), pybind11::arg("scale"),
         pybind11::arg("seq_len_dev") = pybind11::none(), pybind11::arg("k_new") = pybind11::none(),
         pybind11::arg("v_new") = pybind11::none(), pybind11::arg("counters") = pybind11::none(),
         pybind11::arg("rope_cos") = pybind11::none(), pybind11::arg("rope_sin") = pybind11::none());
   m.def("decode_small_applies", &decode_small_applies, "decode_attn takes the one-workgroup-per-item kernel");
+  m.def("decode_attn_plan", &decode_attn_plan, pybind11::arg("B"), pybind11::arg("Tq"), pybind11::arg("H"),
+        pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("S"), pybind11::arg("bf16_plain") = true,
+        pybind11::arg("counters") = 0, "decode_attn's plan: (small kernel, splits, keys per split, merge) (host only)");
   m.def("set_deferred_reduce_stream", &set_deferred_reduce_stream);
   m.def("kv_append", &kv_append, pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("kc"), pybind11::arg("vc"),
         pybind11::arg("ks") = pybind11::none(), pybind11::arg("vs") = pybind11::none(),

@@ -18,16 +18,14 @@
 // counters, a second kernel). Enough splits are used to put ≥ 512 workgroups in
 // flight (256 CUs) even at batch 1.
 #include "common.h"
-#include <cstdlib>
+#include "launch_args.h"
 #include <type_traits>
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 namespace penroz {
 
-constexpr int kMaxGroup = 16;
-constexpr int kMaxMergeSplits = 16;
-constexpr int64_t kMergeMaxKeys = 8192;
+constexpr int kMaxGroup = 16;  // (kMaxMergeSplits = 16: host_plan.h)
 
 template <typename TK> struct KRow;
 template <> struct KRow<bf16> {
@@ -687,35 +685,27 @@ __global__ void __launch_bounds__(256) kv_append_kernel(const T* __restrict__ k,
 
 using namespace penroz;
 
-// Whether decode_attn takes the one-workgroup-per-(batch, KV head) kernel (decode_small_kernel) for
-// a bf16 cache of S slots (the capacity under graph capture). Callers fusing RoPE into the decode
-// step ask this first: only that kernel rotates in place.
+// The A/B switches of plan_decode_attn (host_plan.h), read once per process
+static const DecodeAttnEnv& decode_env() {
+  static const DecodeAttnEnv env = [] {
+    const char* any = std::getenv("PENROZ_DECODE_SMALL_ANY");
+    const int keys = la_env_int("PENROZ_DECODE_SPLIT_KEYS", 0);
+    return DecodeAttnEnv{la_env_int("PENROZ_DECODE_SMALL_ITEMS", 64), any && any[0] == '1', keys >= 64 ? keys : 0};
+  }();
+  return env;
+}
+
+// Whether decode_attn takes decode_small_kernel for a bf16 cache of S slots (the capacity under graph
+// capture). Callers fusing RoPE into the decode step ask this first: only that kernel rotates in place.
 bool decode_small_applies(int64_t B, int64_t Tq, int64_t H, int64_t Hkv, int64_t D, int64_t S) {
-  // PENROZ_DECODE_SMALL_ITEMS: the largest B·Hkv it takes (0 disables)
-  static const int small_items = [] {
-    const char* e = std::getenv("PENROZ_DECODE_SMALL_ITEMS");
-    return e ? std::atoi(e) : 64;
-  }();
-  static const bool small_any = [] {  // (A/B switch: also MHA head_dim 64 — GPT-2)
-    const char* e = std::getenv("PENROZ_DECODE_SMALL_ANY");
-    return e && e[0] == '1';
-  }();
-  static const int split_keys_env = [] {
-    const char* e = std::getenv("PENROZ_DECODE_SPLIT_KEYS");
-    const int v = e ? std::atoi(e) : 0;
-    return v >= 64 ? v : 0;
-  }();
-  if (Hkv <= 0 || H % Hkv) return false;
-  const int64_t G0 = H / Hkv;
-  // the one-workgroup-per-item kernel takes contexts up to 1024 keys (GQA batch 1: Gemma-3 1B
-  // 1.57 -> 1.26 ms/token at a 1024-slot cache, profiles/decode_r5.md); GQA or wide heads only: at
-  // G = 1, D = 64 (GPT-2 batch 1) the general kernel is ~1 µs faster per layer. It runs ONE
-  // workgroup per (batch, KV head) over the whole cache, so longer contexts keep the key-split
-  // grid
-  const int64_t small_keys = split_keys_env ? split_keys_env : 1024;
-  return Tq == 1 && B * Hkv <= small_items && S <= small_keys && (G0 >= 2 || D >= 128 || small_any) &&
-         (G0 == 1 || G0 == 2 || G0 == 4 || G0 == 8 || G0 == 16) && (D == 64 || D == 128 || D == 256 || D == 512) &&
-         G0 * D <= 4096;
+  return plan_decode_attn(B, Tq, H, Hkv, D, S, true, 0, decode_env()).small;
+}
+
+// The launch plan (host_plan.h), for tests: (small kernel, splits, keys per split, merge in launch)
+std::tuple<bool, int64_t, int64_t, bool> decode_attn_plan(int64_t B, int64_t Tq, int64_t H, int64_t Hkv, int64_t D,
+                                                          int64_t S, bool bf16_plain, int64_t counters) {
+  const DecodeAttnPlan p = plan_decode_attn(B, Tq, H, Hkv, D, S, bf16_plain, counters, decode_env());
+  return {p.small, p.splits, p.split_keys, p.merge};
 }
 
 // seq_len_dev (optional int64 [1] on the device): the cache length is read by the kernel at run
@@ -728,212 +718,133 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c
                           c10::optional<torch::Tensor> seq_len_dev, c10::optional<torch::Tensor> k_new,
                           c10::optional<torch::Tensor> v_new, c10::optional<torch::Tensor> counters,
                           c10::optional<torch::Tensor> rope_cos, c10::optional<torch::Tensor> rope_sin) {
-  TORCH_CHECK(q.is_cuda() && q.dim() == 4, "q must be [B, Tq, H, D]");
+  const char* who = "decode_attn";
+  la_one_device(who, q, {kc, vc, k_scale, v_scale, seq_len_dev, k_new, v_new, counters, rope_cos, rope_sin});
   // q may be a view into the fused QKV rows: unit dim stride, packed heads, uniform row stride
   // (a size-1 Tq dim may carry any stride: the row stride is then stride(0))
-  TORCH_CHECK(q.stride(3) == 1 && q.stride(2) == q.size(3) && (q.size(1) == 1 || q.stride(0) == q.size(1) * q.stride(1)),
-              "q must have packed heads and a uniform row stride");
-  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous() && kc.dim() == 4 && kc.sizes() == vc.sizes());
+  TORCH_CHECK(q.dim() == 4 && q.stride(3) == 1 && q.stride(2) == q.size(3) &&
+                  (q.size(1) == 1 || q.stride(0) == q.size(1) * q.stride(1)),
+              who, ": q must be [B, Tq, H, D] with packed heads and a uniform row stride");
   const int B = q.size(0), Tq = q.size(1), H = q.size(2), D = q.size(3);
-  const int Hkv = kc.size(1), cap = kc.size(2);
-  TORCH_CHECK(kc.size(0) == B && kc.size(3) == D && H % Hkv == 0 && H / Hkv <= kMaxGroup);
-  TORCH_CHECK(S <= cap && q_offset >= 0 && q_offset + Tq <= S, "bad cache extent");
-  TORCH_CHECK(D == 32 || D == 64 || D == 128 || D == 256 || D == 512,
-              "decode attention supports head_dim 32/64/128/256/512");
   const bool quant = kc.scalar_type() == torch::kInt8;
-  TORCH_CHECK(!quant || (k_scale.has_value() && v_scale.has_value()), "int8 cache needs scales");
-  TORCH_CHECK(quant || kc.scalar_type() == q.scalar_type(), "cache dtype must match q");
-  auto out = torch::empty({B, Tq, H * D}, q.options());
-  const int64_t q_rs = Tq == 1 ? q.stride(0) : q.stride(1);
-  const int items = B * Hkv * Tq;
-  // keys per split (each workgroup sweeps its keys in chunks of 256; a graph captures S = the cache
-  // capacity and the kernel stops at the device-side length). With zeroed arrival counters
-  // (`counters`, int32 >= items) the last split workgroup of an item merges the partials itself,
-  // so a split costs no second launch and contexts beyond 256 keys are split; without them a split
-  // costs the combine launch (~4.6 µs in a replayed step) and only contexts beyond 1024 keys are.
-  // GPT-2 B = 1 at a 1024-key context: 0.489 ms/token unsplit vs 0.418 split four ways
-  // (profiles/decode_longctx_r6.log). PENROZ_DECODE_SPLIT_KEYS overrides both.
-  static const int split_keys_env = [] {
-    const char* e = std::getenv("PENROZ_DECODE_SPLIT_KEYS");
-    const int v = e ? std::atoi(e) : 0;
-    return v >= 64 ? v : 0;
-  }();
-  int* cnt = nullptr;
-  if (counters.has_value() && counters->defined()) {
-    TORCH_CHECK(counters->is_cuda() && counters->scalar_type() == torch::kInt32 && counters->is_contiguous(),
-                "counters: contiguous int32 on the device");
-    // beyond 8192 keys the combine launch wins again: every merging item costs its split
-    // workgroups a device-scope release (Gemma-3 1B batch 1 at 16k keys, 16 splits either way:
-    // 10.89-10.91 ms/token merged in launch vs 10.54-10.56 with the combine kernel)
-    if (counters->numel() >= items && S <= kMergeMaxKeys) cnt = counters->data_ptr<int>();
-  }
-  const int split_keys = split_keys_env ? split_keys_env : (cnt ? 256 : 1024);
-  int splits = std::max(1, std::min<int>((512 + items - 1) / items, (int)((S + split_keys - 1) / split_keys)));
-  // the merging workgroup reads every split's partials: at most 16
-  if (cnt) splits = std::min(splits, kMaxMergeSplits);
-  const int64_t* sdev = nullptr;
-  if (seq_len_dev.has_value() && seq_len_dev->defined()) {
-    TORCH_CHECK(seq_len_dev->is_cuda() && seq_len_dev->scalar_type() == torch::kInt64 && seq_len_dev->numel() == 1,
-                "seq_len_dev must be a device int64 [1]");
-    sdev = seq_len_dev->data_ptr<int64_t>();
-  }
-  const bool fuse = k_new.has_value() && k_new->defined();
+  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous() && kc.dim() == 4 && kc.sizes() == vc.sizes() && kc.size(0) == B &&
+                  kc.size(3) == D && vc.scalar_type() == kc.scalar_type() && (quant || kc.scalar_type() == q.scalar_type()),
+              who, ": contiguous caches [B, Hkv, cap, D] of q's dtype or int8");
+  const int Hkv = kc.size(1), cap = kc.size(2);
+  TORCH_CHECK(Hkv >= 1 && H % Hkv == 0 && H / Hkv <= kMaxGroup, who, ": H % Hkv == 0, H / Hkv <= ", kMaxGroup);
+  TORCH_CHECK(S <= cap && q_offset >= 0 && q_offset + Tq <= S, who, ": bad cache extent");
+  const float* ksp = quant ? la_f32_shape(who, "k_scale", k_scale, {B, Hkv, cap}) : nullptr;
+  const float* vsp = quant ? la_f32_shape(who, "v_scale", v_scale, {B, Hkv, cap}) : nullptr;
+  const int64_t* sdev = la_defined(seq_len_dev) ? la_i64_scalar(who, "seq_len_dev", *seq_len_dev) : nullptr;
+  const bool fuse = la_defined(k_new);
   int64_t kv_rs = 0;
   if (fuse) {
-    TORCH_CHECK(v_new.has_value() && v_new->defined() && Tq == 1, "fused append: k_new and v_new, Tq == 1");
-    for (const auto* t : {&*k_new, &*v_new}) {
+    TORCH_CHECK(la_defined(v_new) && Tq == 1, who, ": fused append: k_new and v_new, Tq == 1");
+    for (const auto* t : {&*k_new, &*v_new})
       TORCH_CHECK(t->scalar_type() == q.scalar_type() && t->dim() == 4 && t->size(0) == B && t->size(1) == 1 &&
-                      t->size(2) == Hkv && t->size(3) == D && t->stride(3) == 1 && t->stride(2) == D &&
-                      reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
-                  "k_new / v_new must be [B, 1, Hkv, D] with packed heads");
-    }
-    TORCH_CHECK(k_new->stride(0) == v_new->stride(0) && k_new->stride(0) % 8 == 0, "k_new / v_new row stride");
+                      t->size(2) == Hkv && t->size(3) == D && t->stride(3) == 1 && t->stride(2) == D && la_aligned(*t, 16),
+                  who, ": k_new / v_new must be [B, 1, Hkv, D] with packed heads");
+    TORCH_CHECK(k_new->stride(0) == v_new->stride(0) && k_new->stride(0) % 8 == 0, who, ": k_new / v_new row stride");
     kv_rs = k_new->stride(0);
   }
-  const float* ksp = quant ? k_scale->data_ptr<float>() : nullptr;
-  const float* vsp = quant ? v_scale->data_ptr<float>() : nullptr;
-  auto stream = at::hip::getCurrentHIPStream();
-  // small batches, bf16, one query row: the wave-parallel MFMA kernel (decode_small_kernel)
-  const bool small = !quant && q.scalar_type() == torch::kBFloat16 && decode_small_applies(B, Tq, H, Hkv, D, S) &&
-                     (!fuse || kv_rs % 8 == 0);
-  const bool rope = rope_cos.has_value() && rope_cos->defined();
-  if (rope) {
-    TORCH_CHECK(small && fuse && D <= 256, "in-kernel RoPE: the small decode kernel with the fused append, "
-                "head_dim <= 256 only (check decode_small_applies first)");
-    for (const auto* t : {&*rope_cos, &*rope_sin})
-      TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->numel() == D / 2,
-                  "rope cos / sin: contiguous fp32 [D/2] (one position)");
-  }
-  const float* rcp = rope ? rope_cos->data_ptr<float>() : nullptr;
-  const float* rsp = rope ? rope_sin->data_ptr<float>() : nullptr;
-  if (small) {
-    const int G0 = H / Hkv;
-    const bf16* qp = reinterpret_cast<const bf16*>(q.data_ptr());
-    bf16* kp = reinterpret_cast<bf16*>(kc.data_ptr());
-    bf16* vp = reinterpret_cast<bf16*>(vc.data_ptr());
-    bf16* op = reinterpret_cast<bf16*>(out.data_ptr());
-    const bf16* knp = fuse ? reinterpret_cast<const bf16*>(k_new->data_ptr()) : nullptr;
-    const bf16* vnp = fuse ? reinterpret_cast<const bf16*>(v_new->data_ptr()) : nullptr;
-#define PENROZ_DSMALL(DD, GG)                                                                                   \
-  do {                                                                                                            \
-  if (rope && DD <= 256)                                                                                          \
-    hipLaunchKernelGGL((decode_small_kernel<DD, GG, true>), dim3(B * Hkv), dim3(256), 0, stream, qp, kp, vp, op, H, \
-                       Hkv, cap, (int)S, (float)scale, sdev, q_rs, knp, vnp, kv_rs, rcp, rsp);                       \
-  else                                                                                                            \
-    hipLaunchKernelGGL((decode_small_kernel<DD, GG, false>), dim3(B * Hkv), dim3(256), 0, stream, qp, kp, vp, op, H, \
-                       Hkv, cap, (int)S, (float)scale, sdev, q_rs, knp, vnp, kv_rs, nullptr, nullptr);                \
-  } while (0)
-#define PENROZ_DSMALL_G(DD)                      \
-  switch (G0) {                                   \
-    case 1: PENROZ_DSMALL(DD, 1); break;          \
-    case 2: PENROZ_DSMALL(DD, 2); break;          \
-    case 4: PENROZ_DSMALL(DD, 4); break;          \
-    case 8: PENROZ_DSMALL(DD, 8); break;          \
-    default: PENROZ_DSMALL(DD, 16);               \
-  }
-    if (D == 64) PENROZ_DSMALL_G(64)
-    else if (D == 128) PENROZ_DSMALL_G(128)
-    else if (D == 256) PENROZ_DSMALL_G(256)
-    else if (G0 == 1) PENROZ_DSMALL(512, 1);
-    else if (G0 == 2) PENROZ_DSMALL(512, 2);
-    else if (G0 == 4) PENROZ_DSMALL(512, 4);
-    else PENROZ_DSMALL(512, 8);
-#undef PENROZ_DSMALL_G
-#undef PENROZ_DSMALL
-    return out;
-  }
-  torch::Tensor ws_o, ws_ml;
-  float* wo = nullptr;
-  float* wm = nullptr;
+  TORCH_CHECK(!la_defined(counters) || (counters->scalar_type() == torch::kInt32 && counters->is_contiguous()), who,
+              ": counters must be contiguous int32");
+  const DecodeAttnPlan p = plan_decode_attn(B, Tq, H, Hkv, D, S, !quant && q.scalar_type() == torch::kBFloat16,
+                                            la_defined(counters) ? counters->numel() : 0, decode_env());
+  const bool rope = la_defined(rope_cos);
+  TORCH_CHECK(!rope || (p.small && fuse && D <= 256), who, ": in-kernel RoPE: the small decode kernel with the fused "
+              "append, head_dim <= 256 only (check decode_small_applies first)");
+  const float* rcp = rope ? la_f32_vec(who, "rope cos (one position)", rope_cos, D / 2) : nullptr;
+  const float* rsp = rope ? la_f32_vec(who, "rope sin (one position)", rope_sin, D / 2) : nullptr;
+  auto out = torch::empty({B, Tq, H * D}, q.options());
+  const int64_t q_rs = Tq == 1 ? q.stride(0) : q.stride(1);
+  const int G = H / Hkv, splits = p.splits;
+  torch::Tensor ws_o, ws_ml;  // the splits' partial (O, m, l)
   if (splits > 1) {
     ws_o = torch::empty({(int64_t)splits * B * Tq * H * D}, q.options().dtype(torch::kFloat32));
     ws_ml = torch::empty({(int64_t)splits * B * Tq * H * 2}, q.options().dtype(torch::kFloat32));
-    wo = ws_o.data_ptr<float>();
-    wm = ws_ml.data_ptr<float>();
   }
-  dim3 grid(items * splits);
-  auto launch = [&](auto qtag, auto ktag) {
+  float* wo = splits > 1 ? ws_o.data_ptr<float>() : nullptr;
+  float* wm = splits > 1 ? ws_ml.data_ptr<float>() : nullptr;
+  int* cnt = p.merge ? counters->data_ptr<int>() : nullptr;
+  auto stream = at::hip::getCurrentHIPStream();
+  bool ok = true;
+  la_by_elem(who, q.scalar_type(), [&](auto qtag) {
     using TQ = decltype(qtag);
-    using TK = decltype(ktag);
     const TQ* qp = reinterpret_cast<const TQ*>(q.data_ptr());
-    const TK* kp = reinterpret_cast<const TK*>(kc.data_ptr());
-    const TK* vp = reinterpret_cast<const TK*>(vc.data_ptr());
     TQ* op = reinterpret_cast<TQ*>(out.data_ptr());
     const TQ* knp = fuse ? reinterpret_cast<const TQ*>(k_new->data_ptr()) : nullptr;
     const TQ* vnp = fuse ? reinterpret_cast<const TQ*>(v_new->data_ptr()) : nullptr;
-    const int G = H / Hkv;
-#define PENROZ_DECODE(DD, GC)                                                                                   \
-  hipLaunchKernelGGL((decode_kernel<DD, GC, TQ, TK>), grid, dim3(256), 0, stream, qp, kp, vp, ksp, vsp, op, wo, wm, \
-                     B, Tq, H, Hkv, cap, (int)S, (int)q_offset, splits, (float)scale, sdev, q_rs, knp, vnp, kv_rs, cnt, \
-                     split_keys)
-#define PENROZ_DECODE_G(DD)              \
-  switch (G) {                           \
-    case 1: PENROZ_DECODE(DD, 1); break; \
-    case 4: PENROZ_DECODE(DD, 4); break; \
-    case 8: PENROZ_DECODE(DD, 8); break; \
-    default: PENROZ_DECODE(DD, 0);       \
-  }
-    if (D == 64) PENROZ_DECODE_G(64)
-    else if (D == 128) PENROZ_DECODE_G(128)
-    else if (D == 256) PENROZ_DECODE_G(256)  // Gemma
-    else if (D == 32) PENROZ_DECODE(32, 0);  // small GPT-style models (any group size)
-    else PENROZ_DECODE(512, 0);              // Gemma-4 full-attention layers (global_head_dim)
-#undef PENROZ_DECODE_G
-#undef PENROZ_DECODE
-    if (splits > 1 && cnt == nullptr) {
-      const int rows = B * Tq * H;
-      hipLaunchKernelGGL(decode_combine_kernel<TQ>, dim3(std::min(2048, (rows * D + 255) / 256)), dim3(256), 0, stream,
-                         wo, wm, op, rows, D, splits);
-    }
-  };
-  auto with_k = [&](auto qtag) {
-    if (quant) launch(qtag, int8_t{});
-    else launch(qtag, qtag);
-  };
-  if (q.scalar_type() == torch::kBFloat16) with_k(bf16{});
-  else if (q.scalar_type() == torch::kFloat32) with_k(float{});
-  else if (q.scalar_type() == torch::kFloat16) with_k(__half{});
-  else TORCH_CHECK(false, "unsupported q dtype");
+    auto small = [&](auto d, auto g, auto r) {  // decode_small_kernel's D, G and ROPE: bf16 only
+      constexpr int DD = decltype(d)::value, GG = decltype(g)::value;
+      constexpr bool RR = decltype(r)::value != 0;
+      if constexpr (std::is_same<TQ, bf16>::value && decode_small_has(DD, GG, RR))
+        hipLaunchKernelGGL((decode_small_kernel<DD, GG, RR>), dim3(B * Hkv), dim3(256), 0, stream, qp,
+                           reinterpret_cast<bf16*>(kc.data_ptr()), reinterpret_cast<bf16*>(vc.data_ptr()), op, H, Hkv, cap,
+                           (int)S, (float)scale, sdev, q_rs, knp, vnp, kv_rs, rcp, rsp);
+      else ok = false;
+    };
+    auto general = [&](auto ktag) {
+      using TK = decltype(ktag);
+      auto launch = [&](auto d, auto g) {  // decode_kernel's D and GC
+        constexpr int DD = decltype(d)::value, GC = decltype(g)::value;
+        if constexpr (decode_has(DD, GC))
+          hipLaunchKernelGGL((decode_kernel<DD, GC, TQ, TK>), dim3(B * Hkv * Tq * splits), dim3(256), 0, stream, qp,
+                             reinterpret_cast<const TK*>(kc.data_ptr()), reinterpret_cast<const TK*>(vc.data_ptr()), ksp, vsp,
+                             op, wo, wm, B, Tq, H, Hkv, cap, (int)S, (int)q_offset, splits, (float)scale, sdev, q_rs, knp,
+                             vnp, kv_rs, cnt, p.split_keys);
+        else ok = false;
+      };
+      // the exact group sizes 1 / 4 / 8 where they are built, else the any-size form
+      const int gc = (G == 1 || G == 4 || G == 8) && decode_has(D, G) ? G : 0;
+      ok = dispatch_exact(launch, IntList<32, 64, 128, 256, 512>{}, D, IntList<0, 1, 4, 8>{}, gc) && ok;
+      if (ok && splits > 1 && !p.merge) {
+        const int rows = B * Tq * H;
+        hipLaunchKernelGGL(decode_combine_kernel<TQ>, dim3(std::min(2048, (rows * D + 255) / 256)), dim3(256), 0, stream,
+                           wo, wm, op, rows, D, splits);
+      }
+    };
+    if (p.small)
+      ok = dispatch_exact(small, IntList<64, 128, 256, 512>{}, D, IntList<1, 2, 4, 8, 16>{}, G, IntList<0, 1>{}, (int)rope) && ok;
+    else if (quant) general(int8_t{});
+    else general(qtag);
+  });
+  TORCH_CHECK(ok, who, ": head_dim 32 / 64 / 128 / 256 / 512");
   return out;
 }
 
-// k, v: [B, 1, Hkv, D] (views into the fused QKV rows allowed); caches [B, Hkv, cap, D]
+// k, v: [B, 1, Hkv, D] (views into the fused QKV rows allowed); caches [B, Hkv, cap, D]; the slot is
+// *pos_dev (device int64 [1]) when given, else pos
 void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor kc, torch::Tensor vc, c10::optional<torch::Tensor> ks,
                c10::optional<torch::Tensor> vs, c10::optional<torch::Tensor> pos_dev, int64_t pos) {
-  TORCH_CHECK(k.is_cuda() && k.dim() == 4 && k.sizes() == v.sizes() && k.size(1) == 1, "k/v must be [B, 1, Hkv, D]");
-  TORCH_CHECK(k.stride(3) == 1 && k.stride(2) == k.size(3) && v.stride(3) == 1 && v.stride(2) == v.size(3),
-              "k/v rows must be packed");
+  const char* who = "kv_append";
+  la_one_device(who, k, {v, kc, vc, ks, vs, pos_dev});
+  TORCH_CHECK(k.dim() == 4 && k.sizes() == v.sizes() && k.size(1) == 1 && v.scalar_type() == k.scalar_type(), who,
+              ": k / v must be [B, 1, Hkv, D] of one dtype");
+  TORCH_CHECK(k.stride(3) == 1 && k.stride(2) == k.size(3) && v.stride(3) == 1 && v.stride(2) == v.size(3), who,
+              ": k / v rows must be packed");
   const int B = k.size(0), Hkv = k.size(2), D = k.size(3);
-  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous() && kc.sizes() == vc.sizes() && kc.size(0) == B &&
-              kc.size(1) == Hkv && kc.size(3) == D, "cache shape");
-  const int cap = kc.size(2);
-  const int64_t* pd = nullptr;
-  if (pos_dev.has_value() && pos_dev->defined()) {
-    TORCH_CHECK(pos_dev->is_cuda() && pos_dev->scalar_type() == torch::kInt64 && pos_dev->numel() == 1);
-    pd = pos_dev->data_ptr<int64_t>();
-  } else {
-    TORCH_CHECK(pos >= 0 && pos < cap, "cache overflow");
-  }
   const bool quant = kc.scalar_type() == torch::kInt8;
-  TORCH_CHECK(!quant || (ks.has_value() && vs.has_value()), "int8 cache needs scales");
-  TORCH_CHECK(quant || kc.scalar_type() == k.scalar_type(), "cache dtype must match k/v");
-  const int rows = B * Hkv * 2;
-  auto stream = at::hip::getCurrentHIPStream();
-  auto launch = [&](auto ttag, auto ktag) {
+  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous() && kc.dim() == 4 && kc.sizes() == vc.sizes() && kc.size(0) == B &&
+                  kc.size(1) == Hkv && kc.size(3) == D && vc.scalar_type() == kc.scalar_type() &&
+                  (quant || kc.scalar_type() == k.scalar_type()),
+              who, ": contiguous caches [B, Hkv, cap, D] of k's dtype or int8");
+  const int cap = kc.size(2);
+  const int64_t* pd = la_defined(pos_dev) ? la_i64_scalar(who, "pos_dev", *pos_dev) : nullptr;
+  TORCH_CHECK(pd || (pos >= 0 && pos < cap), who, ": cache overflow");
+  float* ksp = quant ? la_f32_shape(who, "ks", ks, {B, Hkv, cap}) : nullptr;
+  float* vsp = quant ? la_f32_shape(who, "vs", vs, {B, Hkv, cap}) : nullptr;
+  la_by_elem(who, k.scalar_type(), [&](auto ttag) {
     using T = decltype(ttag);
-    using TK = decltype(ktag);
-    hipLaunchKernelGGL((kv_append_kernel<T, TK>), dim3((rows + 3) / 4), dim3(256), 0, stream,
-                       reinterpret_cast<const T*>(k.data_ptr()), reinterpret_cast<const T*>(v.data_ptr()), k.stride(0),
-                       v.stride(0), reinterpret_cast<TK*>(kc.data_ptr()), reinterpret_cast<TK*>(vc.data_ptr()),
-                       quant ? ks->data_ptr<float>() : nullptr, quant ? vs->data_ptr<float>() : nullptr, B, Hkv, D,
-                       cap, pd, (int)pos);
-  };
-  auto with_k = [&](auto ttag) {
-    if (quant) launch(ttag, int8_t{});
-    else launch(ttag, ttag);
-  };
-  if (k.scalar_type() == torch::kBFloat16) with_k(bf16{});
-  else if (k.scalar_type() == torch::kFloat32) with_k(float{});
-  else if (k.scalar_type() == torch::kFloat16) with_k(__half{});
-  else TORCH_CHECK(false, "unsupported k dtype");
+    auto launch = [&](auto ktag) {
+      using TK = decltype(ktag);
+      hipLaunchKernelGGL((kv_append_kernel<T, TK>), dim3((B * Hkv * 2 + 3) / 4), dim3(256), 0,
+                         at::hip::getCurrentHIPStream(), reinterpret_cast<const T*>(k.data_ptr()),
+                         reinterpret_cast<const T*>(v.data_ptr()), k.stride(0), v.stride(0),
+                         reinterpret_cast<TK*>(kc.data_ptr()), reinterpret_cast<TK*>(vc.data_ptr()), ksp, vsp, B, Hkv, D, cap,
+                         pd, (int)pos);
+    };
+    if (quant) launch(int8_t{});
+    else launch(ttag);
+  });
 }

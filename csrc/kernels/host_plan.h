@@ -248,4 +248,86 @@ inline GridPlan plan_decode_ln_gemm(int M, int N, int K, int ks_env) {
   return {ks, tw, ((M + 15) / 16) * ((N + tw - 1) / tw)};
 }
 
+// ---- sampler launch plan (sampling.hip) ----
+constexpr int kRT = 512;  // threads of the register kernel: 256 VGPRs each, room for a 104-logit slice
+constexpr int kPartN = 4096, kPartK = 64, kPartMaxP = 64;  // two-stage: logits per part, largest top_k, most parts
+using SampleSlices = IntList<1, 2, 3, 4, 6, 8, 10, 13, 16>;  // register kernel: 16-B chunks per thread (buckets)
+enum class Elem { BF16, F32, F16 };
+enum class SamplePath { TwoStage, Register, Stream };
+struct SamplePlan {
+  SamplePath path;
+  int slice;          // Register: chunks per thread (else 0)
+  int parts, part_k;  // TwoStage: parts per row, the top_k handed to its kernels (0: greedy) (else 0)
+};
+
+// Slices the register kernel is built for. With a nucleus filter bf16 stops at 10: the 13- and 16-chunk
+// slices already sit at 256 VGPRs and the nucleus code does not fit beside them without more scratch,
+// so rows above 40 960 logits take the streaming kernel.
+constexpr bool sample_reg_fits(Elem e, int slice, bool nuc) {
+  return slice >= 1 && (e == Elem::BF16 ? slice <= (nuc ? 10 : 16) : e == Elem::F32 && slice <= 8);
+}
+
+// temp: temperature != 0; nuc: a top-p / min-p filter is in effect; min_rows: PENROZ_SAMPLE_TWO_STAGE_MIN_ROWS
+// (default 1). The two-stage pair takes V % 8 == 0 rows of up to 256 Ki logits, greedy or top_k <= 64, that
+// are too wide for registers, and any number of rows from min_rows on: P x B part workgroups spread a row
+// over P CUs where one workgroup per row leaves most of the chip idle (a batch-64 decode step, and a
+// batch-1 step whose single-workgroup register sampler took ~38 µs of a ~600 µs GPT-2 token). The register
+// kernel takes the other V % 8 == 0 rows that fit, the streaming kernel the rest (odd V, fp16, wide rows).
+inline SamplePlan plan_sample(Elem e, int B, int V, bool temp, int top_k, bool nuc, int min_rows) {
+  const bool vec = V >= 8 && V % 8 == 0 && e != Elem::F16;
+  const int slice = bucket_of(SampleSlices{}, (V / 8 + kRT - 1) / kRT);  // 0: wider than every slice
+  const bool fits = sample_reg_fits(e, slice, nuc);
+  if (vec && (!fits || B >= min_rows) && V <= kPartMaxP * kPartN && (!temp || (top_k > 0 && top_k <= kPartK)))
+    return {SamplePath::TwoStage, 0, (V + kPartN - 1) / kPartN, temp ? top_k : 0};
+  if (vec && fits) return {SamplePath::Register, slice, 0, 0};
+  return {SamplePath::Stream, 0, 0, 0};
+}
+
+// ---- decode attention launch plan (decode_attn.hip) ----
+constexpr int kMaxMergeSplits = 16, kMergeMaxKeys = 8192;  // in-launch merge: most splits, longest context
+// What is built: decode_kernel<D, GC> with an exact group size GC only for head_dim 64 / 128 / 256 (GC 0: any
+// size <= 16); decode_small_kernel<D, G, ROPE> for G·D <= 4096 staged query values, RoPE up to head_dim 256
+constexpr bool decode_has(int D, int gc) { return gc == 0 || (D != 32 && D != 512); }
+constexpr bool decode_small_has(int64_t D, int64_t G, bool rope) {
+  return (D == 64 || D == 128 || D == 256 || D == 512) && (G == 1 || G == 2 || G == 4 || G == 8 || G == 16) &&
+         G * D <= 4096 && !(rope && D > 256);
+}
+
+struct DecodeAttnEnv {
+  int small_items = 64;    // PENROZ_DECODE_SMALL_ITEMS: the largest B·Hkv the small kernel takes (0 disables)
+  bool small_any = false;  // PENROZ_DECODE_SMALL_ANY=1 (A/B switch): also MHA head_dim 64 — GPT-2
+  int split_keys = 0;      // PENROZ_DECODE_SPLIT_KEYS >= 64: keys per split, and the small kernel's longest context
+};
+struct DecodeAttnPlan {
+  bool small;      // decode_small_kernel: one workgroup per (batch, KV head), no splits
+  int splits;      // workgroups per (batch, KV head, query row) along the keys
+  int split_keys;  // keys per split at least
+  bool merge;      // the last split workgroup to arrive merges the partials (arrival counters)
+};
+
+// The small kernel takes one query row over up to 1024 keys (GQA batch 1: Gemma-3 1B 1.57 -> 1.26 ms/token
+// at a 1024-slot cache, profiles/decode_r5.md); GQA or wide heads only: at G = 1, D = 64 (GPT-2 batch 1) the
+// general kernel is ~1 µs faster per layer. It runs ONE workgroup per item over the whole cache, so longer
+// contexts keep the key-split grid.
+// S: the keys the launch is sized for (a graph captures the cache capacity; the kernel stops at the
+// device-side length); bf16_plain: bf16 q over an unquantised bf16 cache; counters: element count of the
+// zeroed arrival counters (0: none). Enough splits for >= 512 workgroups. With a counter per item the
+// merge costs no second launch and contexts beyond 256 keys are split; without, a split costs the
+// combine launch (~4.6 µs in a replayed step) and only contexts beyond 1024 keys are. GPT-2 B = 1 at
+// 1024 keys: 0.489 ms/token unsplit vs 0.418 split four ways (profiles/decode_longctx_r6.log). Beyond
+// 8192 keys the combine launch wins again: every merging item costs its split workgroups a device-scope
+// release (Gemma-3 1B batch 1 at 16k keys, 16 splits either way: 10.89-10.91 ms/token vs 10.54-10.56).
+inline DecodeAttnPlan plan_decode_attn(int64_t B, int64_t Tq, int64_t H, int64_t Hkv, int64_t D, int64_t S, bool bf16_plain,
+                                       int64_t counters, const DecodeAttnEnv& env) {
+  const int64_t items = B * Hkv * Tq, G = Hkv > 0 && H % Hkv == 0 ? H / Hkv : 0;
+  if (bf16_plain && Tq == 1 && B * Hkv <= env.small_items && S <= (env.split_keys ? env.split_keys : 1024) &&
+      (G >= 2 || D >= 128 || env.small_any) && decode_small_has(D, G, false))
+    return {true, 1, 0, false};
+  const bool merge = items >= 1 && counters >= items && S <= kMergeMaxKeys;
+  const int keys = env.split_keys ? env.split_keys : merge ? 256 : 1024;
+  int64_t splits = items >= 1 ? std::min((512 + items - 1) / items, (S + keys - 1) / keys) : 1;
+  if (merge) splits = std::min<int64_t>(splits, kMaxMergeSplits);
+  return {false, (int)std::max<int64_t>(1, splits), keys, merge};
+}
+
 }  // namespace penroz

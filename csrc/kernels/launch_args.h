@@ -1,8 +1,13 @@
-// Operand checks of the decode GEMM / GEMV launch wrappers (decode_linear.hip, skinny_gemm.hip),
-// written once. Each checks one operand and returns its typed pointer; `who` is the entry point's
-// name for the message. Where the entry points differ, the difference is a parameter. Host only.
+// Operand checks of the decode-step launch wrappers (decode_linear.hip, skinny_gemm.hip,
+// decode_gemv_q8.hip, decode_attn.hip, sampling.hip), written once. Each checks one operand and
+// returns its typed pointer; `who` is the entry point's name for the message. Where the entry
+// points differ, the difference is a parameter. Also the wrappers' dtype -> element type dispatch
+// and their read of an integer environment switch. Host only.
 #pragma once
 #include "common.h"
+#include "host_plan.h"
+#include <cstdlib>
+#include <initializer_list>
 #include <torch/extension.h>
 
 namespace penroz {
@@ -11,6 +16,45 @@ using OptTensor = c10::optional<torch::Tensor>;
 
 inline bool la_defined(const OptTensor& t) { return t.has_value() && t->defined(); }
 inline bool la_aligned(const torch::Tensor& t, int bytes) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0; }
+
+inline int la_env_int(const char* name, int unset) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : unset;
+}
+
+// f(T{}) with T = bf16 / float / __half for the dtype; elem_of<T>() names T for host_plan.h
+template <class T>
+constexpr Elem elem_of() {
+  return std::is_same<T, bf16>::value ? Elem::BF16 : std::is_same<T, float>::value ? Elem::F32 : Elem::F16;
+}
+template <class F>
+void la_by_elem(const char* who, at::ScalarType dtype, F&& f) {
+  if (dtype == torch::kBFloat16) f(bf16{});
+  else if (dtype == torch::kFloat32) f(float{});
+  else if (dtype == torch::kFloat16) f(__half{});
+  else TORCH_CHECK(false, who, ": bf16, fp32 or fp16 expected, got ", dtype);
+}
+
+// `first` is on the GPU and every other operand given is on its device: no host pointer reaches a kernel
+inline void la_one_device(const char* who, const torch::Tensor& first, std::initializer_list<OptTensor> rest) {
+  for (const OptTensor& t : rest)
+    TORCH_CHECK(first.is_cuda() && (!la_defined(t) || t->device() == first.device()), who,
+                ": every operand must be on one GPU, the first operand's");
+}
+
+// int64 [1] scalar the kernel reads or bumps (cache position / length, step, seed)
+inline int64_t* la_i64_scalar(const char* who, const char* what, const torch::Tensor& t) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.scalar_type() == torch::kInt64 && t.numel() == 1, who, ": ", what,
+              " must be a device int64 [1]");
+  return t.data_ptr<int64_t>();
+}
+
+// fp32 contiguous tensor of exactly this shape (the int8 cache's per-token scales)
+inline float* la_f32_shape(const char* who, const char* what, const OptTensor& t, at::IntArrayRef shape) {
+  TORCH_CHECK(la_defined(t) && t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() &&
+                  t->sizes() == shape, who, ": fp32 contiguous ", what, " ", shape);
+  return t->data_ptr<float>();
+}
 
 // bf16 activation rows x [M, K]: unit column stride, rows 16-B aligned (16-B vector loads)
 inline const bf16* la_rows(const char* who, const torch::Tensor& x, int K) {

@@ -11,11 +11,11 @@
 //   uniform u: thread-major order (thread t owns elements t, t+1024, …), one block scan of
 //   the per-thread sums finds the owning thread, which walks its own elements.
 // The whole decision stays on the device (no sort, no host round trip per token).
-// sample_reg_kernel (default for V % 8 == 0, V <= 64 Ki) keeps the row in registers; wider rows
-// and batches of >= 16 rows (greedy / top-k <= 64, V <= 256 Ki) go through the two-stage
-// sample_part_kernel + sample_merge_kernel.
+// sample_reg_kernel keeps a V % 8 == 0 row of up to 64 Ki logits in registers; greedy and
+// top-k <= 64 rows of up to 256 Ki logits go through the two-stage sample_part_kernel +
+// sample_merge_kernel. plan_sample (host_plan.h) says which kernel serves a row.
 #include "common.h"
-#include <cstdlib>
+#include "launch_args.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -332,8 +332,7 @@ __global__ void __launch_bounds__(kST) sample_kernel(const T* __restrict__ logit
 // histograms are lane-private ([bin][32] copies, lanes l and l+32 share one): the first pass
 // puts almost every logit into one or two bins (sign + exponent bits), and a single shared
 // histogram then serialises tens of thousands of LDS atomics on one address.
-constexpr int kRT = 512;  // 256 VGPRs per thread: room for a 104-logit slice
-
+// (kRT = 512 threads, host_plan.h: 256 VGPRs per thread, room for a 104-logit slice)
 template <int CPT, typename T, bool NUC = false>
 __global__ void __launch_bounds__(kRT) sample_reg_kernel(const T* __restrict__ logits, const SampleIO io, int V,
                                                          float temperature, int top_k, float top_p, float min_p) {
@@ -762,7 +761,8 @@ __global__ void __launch_bounds__(kRT) sample_reg_kernel(const T* __restrict__ l
 //     ones are ranked by token index (the draw order of the one-stage kernels), softmax(v/T),
 //     inverse-CDF draw with the row's uniform.
 constexpr int kMergeBatch = 8;  // sample_merge_kernel: candidate slots per thread loaded together
-constexpr int kPartN = 4096, kPartK = 64, kPartC = 128, kPartKeep = 1024, kPartMaxP = 64,
+// (kPartN = 4096, kPartK = 64, kPartMaxP = 64: host_plan.h)
+constexpr int kPartC = 128, kPartKeep = 1024,
               kPartLds = kPartMaxP * kPartC;  // every part's candidates fit: none dropped in the merge
 
 template <typename T>
@@ -1037,151 +1037,121 @@ __global__ void __launch_bounds__(256) sample_merge_kernel(const SampleIO io, in
 
 using namespace penroz;
 
-static void launch_sample(const torch::Tensor& logits, const SampleIO& io, double temperature, int64_t top_k,
-                          double top_p, double min_p) {
-  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2);
+// moves plan_sample's switch between the register kernel and the two-stage pair (A/B); read once, at load
+static const int kTwoStageMinRows = la_env_int("PENROZ_SAMPLE_TWO_STAGE_MIN_ROWS", 1);
+
+// The launch plan (host_plan.h), for tests: (path 0 two-stage / 1 register / 2 streaming, register slice,
+// parts, the part kernel's top_k). filtered: top_p < 1 or min_p > 0; min_rows None: the environment's
+std::tuple<int64_t, int64_t, int64_t, int64_t> sample_plan(at::ScalarType dtype, int64_t B, int64_t V, double temperature,
+                                                           int64_t top_k, bool filtered, c10::optional<int64_t> min_rows) {
+  SamplePlan p{};
+  la_by_elem("sample_plan", dtype, [&](auto tag) {
+    p = plan_sample(elem_of<decltype(tag)>(), (int)B, (int)V, temperature != 0.0, (int)top_k,
+                    filtered && temperature != 0.0, min_rows ? (int)*min_rows : kTwoStageMinRows);
+  });
+  return {(int64_t)p.path, p.slice, p.parts, p.part_k};
+}
+
+// rest: the other operands (io points into them); checked here, before any launch, with logits
+static void launch_sample(const char* who, const torch::Tensor& logits, std::initializer_list<OptTensor> rest,
+                          const SampleIO& io, double temperature, int64_t top_k, double top_p, double min_p) {
+  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2 && logits.size(1) >= 1, who,
+              ": contiguous device logits [B, V >= 1]");
+  la_one_device(who, logits, rest);
   TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "top_p must be in (0, 1], got ", top_p);
   TORCH_CHECK(min_p >= 0.0 && min_p < 1.0, "min_p must be in [0, 1), got ", min_p);
-  // the nucleus instantiations run only when a filter is on: the defaults launch today's kernels
+  // the nucleus instantiations run only when a filter is on: the defaults launch the plain kernels
   const bool nuc = temperature != 0.0 && (top_p < 1.0 || min_p > 0.0);
-  const float pp = nuc ? (float)top_p : 1.f, mp = nuc ? (float)min_p : 0.f;
-  const int B = logits.size(0), V = logits.size(1);
+  const float pp = nuc ? (float)top_p : 1.f, mp = nuc ? (float)min_p : 0.f, tt = (float)temperature;
+  const int B = logits.size(0), V = logits.size(1), kk = (int)top_k;
   auto stream = at::hip::getCurrentHIPStream();
-  int chunks = (V / 8 + kRT - 1) / kRT;
-  for (int c : {1, 2, 3, 4, 6, 8, 10, 13, 16})  // instantiated slice sizes
-    if (chunks <= c) { chunks = c; break; }
-  // nucleus: the 13- and 16-chunk slices already sit at 256 VGPRs and the nucleus code does not
-  // fit beside them without more scratch, so rows above 40 960 logits take the streaming kernel
-  const bool fits = chunks <= (logits.scalar_type() == torch::kBFloat16 ? (nuc ? 10 : 16) : 8);
-  const float tt = (float)temperature;
-  const int kk = (int)top_k;
-  // the two-stage form for rows too wide for registers, and for any number of rows from
-  // kTwoStageMinRows on (P x B part workgroups spread a row over P CUs where one workgroup per row
-  // leaves most of the chip idle: a batch-64 decode step, and a batch-1 step whose single-workgroup
-  // register sampler took ~38 µs of a ~600 µs GPT-2 token). PENROZ_SAMPLE_TWO_STAGE_MIN_ROWS
-  // moves the switch (A/B; the register kernel serves the rows below it)
-  static const int kTwoStageMinRows = [] {
-    const char* e = std::getenv("PENROZ_SAMPLE_TWO_STAGE_MIN_ROWS");
-    return e ? std::atoi(e) : 1;
-  }();
-  if (V % 8 == 0 && (!fits || B >= kTwoStageMinRows) && logits.scalar_type() != torch::kFloat16 &&
-      V <= kPartMaxP * kPartN && (temperature == 0.0 || (top_k > 0 && top_k <= kPartK))) {
-    const int P = (V + kPartN - 1) / kPartN;
-    const bool topk = temperature != 0.0;
-    auto opt = logits.options();
-    auto pval = torch::empty({B, P}, opt.dtype(torch::kFloat32));
-    auto pidx = torch::empty({B, P}, opt.dtype(torch::kInt32));
-    torch::Tensor ckey, cidx, cnt;
-    if (topk) {
-      ckey = torch::empty({B, P, kPartC}, opt.dtype(torch::kInt32));
-      cidx = torch::empty({B, P, kPartC}, opt.dtype(torch::kInt32));
-      cnt = torch::empty({B, P}, opt.dtype(torch::kInt32));
-    }
-    uint32_t* ckp = topk ? reinterpret_cast<uint32_t*>(ckey.data_ptr()) : nullptr;
-    int* cip = topk ? cidx.data_ptr<int>() : nullptr;
-    int* cnp = topk ? cnt.data_ptr<int>() : nullptr;
-    const int kpart = topk ? kk : 0;
-    if (logits.scalar_type() == torch::kBFloat16)
-      hipLaunchKernelGGL(sample_part_kernel<bf16>, dim3(P, B), dim3(256), 0, stream,
-                         reinterpret_cast<const bf16*>(logits.data_ptr()), V, P, kpart, pval.data_ptr<float>(),
-                         pidx.data_ptr<int>(), ckp, cip, cnp);
-    else
-      hipLaunchKernelGGL(sample_part_kernel<float>, dim3(P, B), dim3(256), 0, stream, logits.data_ptr<float>(), V, P,
-                         kpart, pval.data_ptr<float>(), pidx.data_ptr<int>(), ckp, cip, cnp);
-    static bool lds_set = [] {  // > 64 KB of LDS per workgroup must be requested
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(sample_merge_kernel<false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPartLds * 8) == hipSuccess &&
-             hipFuncSetAttribute(reinterpret_cast<const void*>(sample_merge_kernel<true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, kPartLds * 8) == hipSuccess;
-    }();
-    TORCH_CHECK(lds_set, "sample_merge_kernel: LDS request refused");
-    if (nuc)
-      hipLaunchKernelGGL(sample_merge_kernel<true>, dim3(B), dim3(256), kPartLds * 8, stream, io, P, tt, kpart, pp, mp,
-                         pval.data_ptr<float>(), pidx.data_ptr<int>(), ckp, cip, cnp);
-    else
-      hipLaunchKernelGGL(sample_merge_kernel<false>, dim3(B), dim3(256), kPartLds * 8, stream, io, P, tt, kpart, pp, mp,
-                         pval.data_ptr<float>(), pidx.data_ptr<int>(), ckp, cip, cnp);
-    return;
-  }
-  if (V % 8 == 0 && fits && logits.scalar_type() != torch::kFloat16) {
-    auto launch = [&](auto tag) {
-      using T = decltype(tag);
-      const T* lp = reinterpret_cast<const T*>(logits.data_ptr());
-#define PENROZ_SAMPLE_REG_N(C, N) \
-  hipLaunchKernelGGL((sample_reg_kernel<C, T, N>), dim3(B), dim3(kRT), 0, stream, lp, io, V, tt, kk, pp, mp)
-#define PENROZ_SAMPLE_REG(C)                      \
-  case C:                                         \
-    if (nuc) PENROZ_SAMPLE_REG_N(C, true);        \
-    else PENROZ_SAMPLE_REG_N(C, false);           \
-    break;
-#define PENROZ_SAMPLE_REG_WIDE(C) \
-  case C: PENROZ_SAMPLE_REG_N(C, false); break;  // (never reached with a nucleus filter: fits)
-      switch (chunks) {
-        PENROZ_SAMPLE_REG(1) PENROZ_SAMPLE_REG(2) PENROZ_SAMPLE_REG(3) PENROZ_SAMPLE_REG(4) PENROZ_SAMPLE_REG(6)
-        PENROZ_SAMPLE_REG(8)
-        default:
-          if constexpr (sizeof(T) == 2) {
-            switch (chunks) { PENROZ_SAMPLE_REG(10) PENROZ_SAMPLE_REG_WIDE(13) PENROZ_SAMPLE_REG_WIDE(16) }
-          }
-      }
-#undef PENROZ_SAMPLE_REG_WIDE
-#undef PENROZ_SAMPLE_REG
-#undef PENROZ_SAMPLE_REG_N
-    };
-    if (logits.scalar_type() == torch::kBFloat16) launch(bf16{});
-    else launch(float{});
-    return;
-  }
-  auto stream_launch = [&](auto tag) {
+  bool ok = true;
+  la_by_elem(who, logits.scalar_type(), [&](auto tag) {
     using T = decltype(tag);
     const T* lp = reinterpret_cast<const T*>(logits.data_ptr());
-    if (nuc) hipLaunchKernelGGL((sample_kernel<T, true>), dim3(B), dim3(kST), 0, stream, lp, io, V, tt, kk, pp, mp);
-    else hipLaunchKernelGGL((sample_kernel<T, false>), dim3(B), dim3(kST), 0, stream, lp, io, V, tt, kk, pp, mp);
-  };
-  if (logits.scalar_type() == torch::kBFloat16) stream_launch(bf16{});
-  else if (logits.scalar_type() == torch::kFloat32) stream_launch(float{});
-  else if (logits.scalar_type() == torch::kFloat16) stream_launch(__half{});
-  else TORCH_CHECK(false, "unsupported logits dtype");
+    const SamplePlan p = plan_sample(elem_of<T>(), B, V, temperature != 0.0, kk, nuc, kTwoStageMinRows);
+    if (p.path == SamplePath::Stream) {
+      if (nuc) hipLaunchKernelGGL((sample_kernel<T, true>), dim3(B), dim3(kST), 0, stream, lp, io, V, tt, kk, pp, mp);
+      else hipLaunchKernelGGL((sample_kernel<T, false>), dim3(B), dim3(kST), 0, stream, lp, io, V, tt, kk, pp, mp);
+    } else if constexpr (std::is_same<T, __half>::value) {
+      ok = false;  // (the other two are not built for fp16, and the plan never picks them for it)
+    } else if (p.path == SamplePath::Register) {
+      auto launch = [&](auto c, auto n) {  // sample_reg_kernel's slice and NUC
+        constexpr int C = decltype(c)::value;
+        constexpr bool N = decltype(n)::value != 0;
+        if constexpr (sample_reg_fits(elem_of<T>(), C, N))
+          hipLaunchKernelGGL((sample_reg_kernel<C, T, N>), dim3(B), dim3(kRT), 0, stream, lp, io, V, tt, kk, pp, mp);
+        else ok = false;
+      };
+      ok = dispatch_exact(launch, SampleSlices{}, p.slice, IntList<0, 1>{}, (int)nuc) && ok;
+    } else {
+      const int P = p.parts;
+      const bool topk = p.part_k > 0;
+      auto opt = logits.options();
+      auto pval = torch::empty({B, P}, opt.dtype(torch::kFloat32));
+      auto pidx = torch::empty({B, P}, opt.dtype(torch::kInt32));
+      torch::Tensor ckey, cidx, cnt;
+      if (topk) {
+        ckey = torch::empty({B, P, kPartC}, opt.dtype(torch::kInt32));
+        cidx = torch::empty({B, P, kPartC}, opt.dtype(torch::kInt32));
+        cnt = torch::empty({B, P}, opt.dtype(torch::kInt32));
+      }
+      uint32_t* ckp = topk ? reinterpret_cast<uint32_t*>(ckey.data_ptr()) : nullptr;
+      int* cip = topk ? cidx.data_ptr<int>() : nullptr;
+      int* cnp = topk ? cnt.data_ptr<int>() : nullptr;
+      hipLaunchKernelGGL(sample_part_kernel<T>, dim3(P, B), dim3(256), 0, stream, lp, V, P, p.part_k,
+                         pval.data_ptr<float>(), pidx.data_ptr<int>(), ckp, cip, cnp);
+      static bool lds_set = [] {  // > 64 KB of LDS per workgroup must be requested
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(sample_merge_kernel<false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kPartLds * 8) == hipSuccess &&
+               hipFuncSetAttribute(reinterpret_cast<const void*>(sample_merge_kernel<true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, kPartLds * 8) == hipSuccess;
+      }();
+      TORCH_CHECK(lds_set, "sample_merge_kernel: LDS request refused");
+      auto merge = nuc ? sample_merge_kernel<true> : sample_merge_kernel<false>;
+      hipLaunchKernelGGL(merge, dim3(B), dim3(256), kPartLds * 8, stream, io, P, tt, p.part_k, pp, mp,
+                         pval.data_ptr<float>(), pidx.data_ptr<int>(), ckp, cip, cnp);
+    }
+  });
+  TORCH_CHECK(ok, who, ": no kernel for V = ", V);
 }
 
 torch::Tensor sample_tokens(torch::Tensor logits, c10::optional<torch::Tensor> uniform, double temperature,
                             int64_t top_k, double top_p, double min_p) {
-  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2);
+  const char* who = "sample_tokens";
   const int B = logits.size(0);
   auto out = torch::empty({B, 1}, logits.options().dtype(torch::kInt64));
-  torch::Tensor u;
-  if (uniform.has_value() && uniform->defined()) u = uniform->to(torch::kFloat32).contiguous();
-  else u = torch::zeros({B}, logits.options().dtype(torch::kFloat32));
-  TORCH_CHECK(u.numel() == B && u.is_cuda());
-  launch_sample(logits, SampleIO{u.data_ptr<float>(), nullptr, nullptr, out.data_ptr<int64_t>(), nullptr, 0}, temperature,
-                top_k, top_p, min_p);
+  torch::Tensor u = la_defined(uniform) ? uniform->to(torch::kFloat32).contiguous()
+                                        : torch::zeros({B}, logits.options().dtype(torch::kFloat32));
+  TORCH_CHECK(u.numel() == B, who, ": one uniform per row");
+  launch_sample(who, logits, {u}, SampleIO{u.data_ptr<float>(), nullptr, nullptr, out.data_ptr<int64_t>(), nullptr, 0},
+                temperature, top_k, top_p, min_p);
   return out;
 }
 
-// Graph-replayed decode: token of row r -> idx_out[r] and out_buf[r, *step]; uniforms hashed
-// from (seed, *step, r) on the device. Then one tiny kernel advances the step counters.
+// Graph-replayed decode: token of row r -> idx_out[r] and out_buf[r, *step]; uniforms hashed from
+// (seed, *step, r) on the device. With adv_a / adv_b / done (int32 [1], zero) the last row's writer
+// also advances the step counters (see SampleIO).
 void sample_step(torch::Tensor logits, double temperature, int64_t top_k, torch::Tensor seed, torch::Tensor step,
                  torch::Tensor idx_out, torch::Tensor out_buf, c10::optional<torch::Tensor> adv_a,
                  c10::optional<torch::Tensor> adv_b, c10::optional<torch::Tensor> done, double top_p, double min_p) {
-  TORCH_CHECK(logits.dim() == 2 && step.is_cuda() && step.scalar_type() == torch::kInt64 && step.numel() == 1);
-  TORCH_CHECK(seed.is_cuda() && seed.scalar_type() == torch::kInt64 && seed.numel() == 1, "seed: device int64 [1]");
+  const char* who = "sample_step";
   const int B = logits.size(0);
-  TORCH_CHECK(idx_out.scalar_type() == torch::kInt64 && idx_out.numel() == B && idx_out.is_contiguous());
-  TORCH_CHECK(out_buf.scalar_type() == torch::kInt64 && out_buf.dim() == 2 && out_buf.size(0) == B &&
-              out_buf.stride(1) == 1, "out_buf [B, n] int64");
-  SampleIO io{nullptr, seed.data_ptr<int64_t>(), step.data_ptr<int64_t>(), idx_out.data_ptr<int64_t>(),
+  TORCH_CHECK(idx_out.scalar_type() == torch::kInt64 && idx_out.numel() == B && idx_out.is_contiguous(), who,
+              ": idx_out must be contiguous int64 [B]");
+  TORCH_CHECK(out_buf.scalar_type() == torch::kInt64 && out_buf.dim() == 2 && out_buf.size(0) == B && out_buf.stride(1) == 1,
+              who, ": out_buf must be int64 [B, n]");
+  SampleIO io{nullptr, la_i64_scalar(who, "seed", seed), la_i64_scalar(who, "step", step), idx_out.data_ptr<int64_t>(),
                out_buf.data_ptr<int64_t>(), out_buf.stride(0)};
-  if (done.has_value() && done->defined()) {  // fused counter advance (see SampleIO)
-    TORCH_CHECK(adv_a.has_value() && adv_b.has_value(), "sample_step: advance needs both counters");
-    for (const torch::Tensor* t : {&*adv_a, &*adv_b})
-      TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kInt64 && t->numel() == 1, "advance counters: int64 [1]");
-    TORCH_CHECK(done->is_cuda() && done->scalar_type() == torch::kInt32 && done->numel() == 1, "done: int32 [1] (zero)");
-    io.adv_a = adv_a->data_ptr<int64_t>();
-    io.adv_b = adv_b->data_ptr<int64_t>();
+  if (la_defined(done)) {
+    TORCH_CHECK(adv_a.has_value() && adv_b.has_value(), who, ": advance needs both counters");
+    TORCH_CHECK(done->scalar_type() == torch::kInt32 && done->numel() == 1, who, ": done must be int32 [1]");
+    io.adv_a = la_i64_scalar(who, "adv_a", *adv_a);
+    io.adv_b = la_i64_scalar(who, "adv_b", *adv_b);
     io.done = reinterpret_cast<unsigned*>(done->data_ptr<int>());
     io.nrows = B;
   }
-  launch_sample(logits, io, temperature, top_k, top_p, min_p);
+  launch_sample(who, logits, {seed, step, idx_out, out_buf, adv_a, adv_b, done}, io, temperature, top_k, top_p, min_p);
 }
 
 __global__ void decode_advance_kernel(int64_t* a, int64_t* b, int64_t* c) {
@@ -1194,8 +1164,8 @@ __global__ void decode_advance_kernel(int64_t* a, int64_t* b, int64_t* c) {
 
 // +1 on three device int64 scalars (cache position, cache length, burst step) in one launch
 void decode_advance(torch::Tensor a, torch::Tensor b, torch::Tensor c) {
-  for (const auto* t : {&a, &b, &c})
-    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kInt64 && t->numel() == 1, "decode_advance: int64 [1]");
+  const char* who = "decode_advance";
+  la_one_device(who, a, {b, c});
   hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, at::hip::getCurrentHIPStream(),
-                     a.data_ptr<int64_t>(), b.data_ptr<int64_t>(), c.data_ptr<int64_t>());
+                     la_i64_scalar(who, "a", a), la_i64_scalar(who, "b", b), la_i64_scalar(who, "c", c));
 }

@@ -14,10 +14,22 @@ splits a tie at the cut by sort position) — and ``min_p`` in [0, 1) keeps i if
 top-k, top-p, min-p, then the draw over the renormalised kept set.  ``top_p`` 1 / None and
 ``min_p`` 0 / None mean no filter, and temperature 0 ignores both.
 
-GPU: ``csrc/kernels/sampling.hip`` — one workgroup per row: temperature scale, top-k by a
-radix-select threshold in LDS, top-p by the same select over fixed-point mass bins, softmax and
-inverse-CDF draw from one uniform per row, all in a single pass over the row (no sort, no host
-round trip).
+GPU: ``csrc/kernels/sampling.hip`` — temperature scale, top-k by a radix-select threshold, top-p by
+the same select over fixed-point mass bins, softmax and inverse-CDF draw from one uniform per row,
+all on the device (no sort, no host round trip). Three paths, chosen per call by ``plan_sample``
+(``csrc/kernels/host_plan.h``; ``kernels().sample_plan(dtype, B, V, temperature, top_k, filtered)``
+returns the choice):
+
+* two-stage (``sample_part_kernel`` + ``sample_merge_kernel``): a row is split into parts of 4096
+  logits, one workgroup each, and one workgroup per row merges the parts' candidates. bf16 / fp32
+  rows with ``V % 8 == 0`` and ``V`` <= 256 Ki, greedy or ``top_k`` <= 64 — at every batch size by
+  default (``PENROZ_SAMPLE_TWO_STAGE_MIN_ROWS`` = 1), and always where the row is too wide for
+  registers;
+* register-resident (``sample_reg_kernel``): one workgroup per row, the row read once into
+  registers. The other ``V % 8 == 0`` rows that fit: bf16 up to 64 Ki logits (40 Ki with a top-p /
+  min-p filter), fp32 up to 32 Ki — so ``top_k`` = 0 or > 64, or fewer rows than the switch above;
+* streaming (``sample_kernel``): one workgroup per row, several passes over the row in memory.
+  Everything else: ``V % 8 != 0``, fp16, and rows too wide for the other two.
 ``kv_quantize``: per-token absmax/127 int8 (``kv_cache.py:114-125``), written straight into
 the preallocated cache slot.
 """

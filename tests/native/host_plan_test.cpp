@@ -120,6 +120,85 @@ static void test_decode_plan_goldens() {
   EXPECT(plan_decode_ln_gemm(64, 2304, 768, 1).v == 1);  // PENROZ_DECODE_LN_KSPLIT=1
 }
 
+// Every sampler plan names a kernel that is built and covers the row
+static void test_sample_plan_properties() {
+  const int Vs[] = {0, 1, 7, 8, 64, 1024, 4096, 4104, 8192, 24576, 32768, 32776, 40960, 40968, 50257, 50304,
+                    65536, 65544, 96000, 262144, 262152, 1 << 22};
+  for (Elem e : {Elem::BF16, Elem::F32, Elem::F16})
+    for (int V : Vs)
+      for (int B : {0, 1, 2, 16, 64})
+        for (int temp = 0; temp < 2; ++temp)
+          for (int k : {0, 1, 50, 64, 65, 1000})
+            for (int nuc = 0; nuc <= temp; ++nuc)  // a filter is in effect only with a temperature
+              for (int min_rows : {0, 1, 2, 16, 1 << 30}) {
+                const SamplePlan p = plan_sample(e, B, V, temp != 0, k, nuc != 0, min_rows);
+                if (e == Elem::F16 || V % 8 != 0) EXPECT(p.path == SamplePath::Stream);
+                if (p.path == SamplePath::Register) {
+                  EXPECT(in_list(SampleSlices{}, p.slice) && sample_reg_fits(e, p.slice, nuc != 0));
+                  EXPECT((long long)p.slice * kRT * 8 >= V && p.parts == 0 && p.part_k == 0);
+                  EXPECT(B < min_rows || (temp && (k == 0 || k > kPartK)));  // else the two-stage pair has it
+                } else if (p.path == SamplePath::TwoStage) {
+                  EXPECT(p.parts >= 1 && p.parts <= kPartMaxP && (long long)p.parts * kPartN >= V && p.slice == 0);
+                  EXPECT(temp ? (p.part_k == k && k >= 1 && k <= kPartK) : p.part_k == 0);
+                } else {
+                  EXPECT(p.slice == 0 && p.parts == 0 && p.part_k == 0);
+                }
+              }
+  // the fit rule: bf16 up to 16 chunks, 10 with a filter; fp32 up to 8; fp16 never; nothing outside the list
+  for (int c = -1; c <= 20; ++c) {
+    EXPECT(sample_reg_fits(Elem::BF16, c, false) == (c >= 1 && c <= 16) && sample_reg_fits(Elem::BF16, c, true) == (c >= 1 && c <= 10));
+    EXPECT(sample_reg_fits(Elem::F32, c, false) == (c >= 1 && c <= 8) && sample_reg_fits(Elem::F32, c, true) == (c >= 1 && c <= 8));
+    EXPECT(!sample_reg_fits(Elem::F16, c, false) && !sample_reg_fits(Elem::F16, c, true));
+  }
+  // by hand, default switch (1 row): GPT-2's padded vocabulary
+  const SamplePlan a = plan_sample(Elem::BF16, 1, 50304, true, 50, false, 1), b = plan_sample(Elem::BF16, 1, 50304, true, 0, false, 1);
+  EXPECT(a.path == SamplePath::TwoStage && a.parts == 13 && a.part_k == 50 && b.path == SamplePath::Register && b.slice == 13);
+  EXPECT(plan_sample(Elem::BF16, 1, 50304, true, 0, true, 1).path == SamplePath::Stream);
+  EXPECT(plan_sample(Elem::BF16, 1, 50304, true, 50, false, 2).slice == 13);
+}
+
+// Every decode attention plan is launchable: at least one split, a merge only within its limits,
+// the small kernel only where it is built
+static void test_decode_attn_plan_properties() {
+  const DecodeAttnEnv envs[] = {{}, {0, false, 0}, {1024, true, 0}, {64, false, 64}, {64, false, 4096}};
+  for (const DecodeAttnEnv& env : envs)
+    for (int B : {0, 1, 3, 64, 65, 512})
+      for (int Tq : {0, 1, 2, 17})
+        for (int Hkv : {0, 1, 2, 3, 12})
+          for (int G : {1, 2, 3, 4, 8, 16, 32})
+            for (int D : {0, 32, 64, 96, 128, 256, 512})
+              for (long long S : {0LL, 1LL, 256LL, 257LL, 1024LL, 1025LL, 8192LL, 8193LL, 16384LL, 1LL << 20})
+                for (long long counters : {0LL, 1LL, 4096LL, 1LL << 13})
+                  for (int plain = 0; plain < 2; ++plain) {
+                    const int H = Hkv ? G * Hkv : G;  // Hkv = 0: degenerate, must not divide
+                    const DecodeAttnPlan p = plan_decode_attn(B, Tq, H, Hkv, D, S, plain != 0, counters, env);
+                    EXPECT(p.splits >= 1);
+                    if (p.merge) EXPECT(!p.small && p.splits <= 16 && S <= 8192 && counters >= (long long)B * Hkv * Tq);
+                    if (!p.small) EXPECT(p.split_keys >= 64 && (long long)(p.splits - 1) * p.split_keys < (S > 0 ? S : 1));
+                    if (p.small) {
+                      EXPECT(plain && Tq == 1 && Hkv >= 1 && p.splits == 1 && !p.merge);
+                      EXPECT((G == 1 || G == 2 || G == 4 || G == 8 || G == 16) && (D == 64 || D == 128 || D == 256 || D == 512));
+                      EXPECT(G * D <= 4096 && B * Hkv <= env.small_items && S <= (env.split_keys ? env.split_keys : 1024));
+                      EXPECT(decode_small_has(D, G, false));
+                    }
+                  }
+  EXPECT(!plan_decode_attn(1, 1, 7, 2, 64, 100, true, 0, {}).small);  // H % Hkv != 0
+  EXPECT(!decode_small_has(512, 16, false) && decode_small_has(512, 8, false) && !decode_small_has(512, 8, true));
+  EXPECT(decode_small_has(256, 16, true) && !decode_small_has(32, 1, false) && !decode_small_has(64, 3, false));
+  EXPECT(decode_has(32, 0) && decode_has(512, 0) && !decode_has(32, 1) && !decode_has(512, 8) && decode_has(64, 4));
+  // by hand, default switches: GPT-2 (12 heads of 64) and a Gemma-3 1B layer (4 query heads on 1 KV head of 256)
+  struct G { int B, H, Hkv, D; long long S, counters; bool small; int splits, keys; bool merge; };
+  const G gold[] = {{1, 12, 12, 64, 1024, 4096, false, 4, 256, true}, {1, 12, 12, 64, 1024, 0, false, 1, 1024, false},
+                    {64, 12, 12, 64, 1024, 4096, false, 1, 256, true}, {1, 4, 1, 256, 1024, 4096, true, 1, 0, false},
+                    {1, 4, 1, 256, 1025, 0, false, 2, 1024, false}, {65, 4, 1, 256, 1024, 0, false, 1, 1024, false},
+                    {1, 16, 1, 512, 512, 0, false, 1, 1024, false}, {1, 8, 1, 512, 512, 0, true, 1, 0, false},
+                    {1, 4, 1, 256, 16384, 8192, false, 16, 1024, false}, {1, 4, 1, 256, 8192, 8192, false, 16, 256, true}};
+  for (const G& g : gold) {
+    const DecodeAttnPlan p = plan_decode_attn(g.B, 1, g.H, g.Hkv, g.D, g.S, true, g.counters, {});
+    EXPECT(p.small == g.small && p.splits == g.splits && p.split_keys == g.keys && p.merge == g.merge);
+  }
+}
+
 int main() {
   // GPT-2 124M / XL weight-gradient shapes (K = tokens per step) and edge cases
   const int shapes[][3] = {{2304, 768, 65536}, {768, 768, 65536}, {3072, 768, 65536}, {768, 3072, 65536},
@@ -174,6 +253,8 @@ int main() {
   test_dispatch();
   test_gemv_plan_properties();
   test_decode_plan_goldens();
+  test_sample_plan_properties();
+  test_decode_attn_plan_properties();
   std::printf("host_plan_test: %s (%d failures)\n", fails ? "FAILED" : "ok", fails);
   return fails ? 1 : 0;
 }

@@ -90,3 +90,78 @@ def test_attn_work_plan_off_and_many_rounds(monkeypatch):
     assert _ext.kernels().attn_work_plan(8, 768, 256, 128, 32, 1024, 256, 2.7)[:2] == [8, 8]
     r = _ext.kernels().attn_work_plan(8, 32, 256, 128, 32, 1024, 256, 2.7)
     assert r[1] < 8  # the Gemma-3 1B B=8 forward grid (one round) is split
+
+
+# sampler paths of sample_plan's first field
+TWO_STAGE, REGISTER, STREAM = 0, 1, 2
+
+
+def _sample_plan(dtype, V, temperature, top_k, filtered, B=1, min_rows=None):
+    import torch
+    dt = {"bf16": torch.bfloat16, "fp32": torch.float32, "fp16": torch.float16}[dtype]
+    return _ext.kernels().sample_plan(dt, B, V, temperature, top_k, filtered, min_rows)
+
+
+@pytest.mark.parametrize("dtype,V,temperature,top_k,filtered,plan", [
+    ("bf16", 50304, 0.8, 50, False, (TWO_STAGE, 0, 13, 50)),
+    ("bf16", 50304, 0.8, 0, False, (REGISTER, 13, 0, 0)),
+    ("bf16", 50304, 0.8, 0, True, (STREAM, 0, 0, 0)),  # 13 chunks: not built with the nucleus code
+    ("bf16", 40960, 0.8, 0, True, (REGISTER, 10, 0, 0)),
+    ("bf16", 40960, 0.8, 100, False, (REGISTER, 10, 0, 0)),  # top_k above the two-stage pair's 64
+    ("fp32", 8192, 0.8, 50, False, (TWO_STAGE, 0, 2, 50)),
+    ("bf16", 262144, 0.8, 50, False, (TWO_STAGE, 0, 64, 50)),
+    ("bf16", 262152, 0.8, 50, False, (STREAM, 0, 0, 0)),  # one chunk past 64 parts
+    ("fp32", 96000, 0.8, 0, False, (STREAM, 0, 0, 0)),
+    ("fp32", 96000, 0.0, 0, False, (TWO_STAGE, 0, 24, 0)),  # greedy
+    ("fp32", 1024, 0.8, 0, False, (REGISTER, 1, 0, 0)),
+    ("fp16", 4096, 0.8, 50, False, (STREAM, 0, 0, 0)),
+    ("fp16", 4096, 0.0, 0, False, (STREAM, 0, 0, 0)),
+    ("bf16", 50257, 0.8, 50, True, (STREAM, 0, 0, 0)),
+    ("bf16", 50257, 0.0, 0, False, (STREAM, 0, 0, 0)),
+])
+def test_sample_plan_table(dtype, V, temperature, top_k, filtered, plan):
+    """Which sampler kernel serves a row (host_plan.h plan_sample), worked out by hand from the
+    launch rule; PENROZ_SAMPLE_TWO_STAGE_MIN_ROWS at its default of 1."""
+    assert _sample_plan(dtype, V, temperature, top_k, filtered, min_rows=1) == plan
+    assert _sample_plan(dtype, V, temperature, top_k, filtered) == plan  # None: the process's own value (unset: 1)
+
+
+def test_sample_plan_min_rows_and_filter_at_temperature_zero():
+    """With the switch at 2 rows a single bf16 row of 50 304 logits stays in registers; two rows
+    take the two-stage pair. Temperature 0 ignores the filters."""
+    assert _sample_plan("bf16", 50304, 0.8, 50, False, B=1, min_rows=2) == (REGISTER, 13, 0, 0)
+    assert _sample_plan("bf16", 50304, 0.8, 50, False, B=2, min_rows=2) == (TWO_STAGE, 0, 13, 50)
+    assert _sample_plan("bf16", 50304, 0.0, 0, True, min_rows=1) == _sample_plan("bf16", 50304, 0.0, 0, False, min_rows=1)
+
+
+# (B, H, Hkv, D, S, bf16_plain, counters) -> (small, splits, keys per split, merge); None: not asserted
+_DECODE_PLANS = [
+    ((1, 12, 12, 64, 1024, True, 4096), (False, 4, 256, True)),
+    ((1, 12, 12, 64, 1024, True, 0), (False, 1, 1024, False)),
+    ((64, 12, 12, 64, 1024, True, 4096), (False, 1, None, None)),
+    ((64, 12, 12, 64, 1024, True, 0), (False, 1, None, None)),
+    ((1, 4, 1, 256, 1024, True, 4096), (True, 1, None, False)),
+    ((1, 4, 1, 256, 1024, True, 0), (True, 1, None, False)),
+    ((1, 4, 1, 256, 1024, False, 4096), (False, 4, 256, True)),  # fp32 / fp16 q or an int8 cache
+    ((1, 4, 1, 256, 1025, True, 4096), (False, None, None, None)),
+    ((1, 4, 1, 256, 1025, True, 0), (False, None, None, None)),
+    ((65, 4, 1, 256, 1024, True, 0), (False, None, None, None)),
+    ((1, 16, 1, 512, 1024, True, 0), (False, None, None, None)),
+    ((1, 8, 1, 512, 1024, True, 0), (True, 1, None, False)),
+    ((1, 4, 1, 256, 16384, True, 8192), (False, 16, 1024, False)),
+    ((1, 4, 1, 256, 8192, True, 8192), (False, 16, 256, True)),
+]
+
+
+@pytest.mark.parametrize("shape,plan", _DECODE_PLANS)
+def test_decode_attn_plan_table(shape, plan):
+    """decode_attn's launch plan (host_plan.h plan_decode_attn), worked out by hand from the launch
+    rule with the environment switches unset, and decode_small_applies (what ops/attention.py asks)
+    agreeing with it."""
+    B, H, Hkv, D, S, plain, counters = shape
+    K = _ext.kernels()
+    got = K.decode_attn_plan(B, 1, H, Hkv, D, S, plain, counters)
+    assert all(w is None or g == w for g, w in zip(got, plan)), got
+    assert got[1] >= 1 and (not got[3] or (got[1] <= 16 and S <= 8192))
+    assert K.decode_small_applies(B, 1, H, Hkv, D, S) == K.decode_attn_plan(B, 1, H, Hkv, D, S, True, counters)[0]
+    assert not K.decode_attn_plan(B, 2, H, Hkv, D, S, plain, counters)[0]  # two query rows: never the small kernel

@@ -673,8 +673,11 @@ def test_sampling():
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32, torch.float16])
 @pytest.mark.parametrize("V", [50304, 50257, 24576, 96000])
 def test_sampling_wide_rows(dt, V):
-    """Full-vocabulary rows: register-resident kernel (V % 8 == 0, bf16 up to 64 Ki / fp32 up to
-    32 Ki) and the streaming kernel (other widths, fp16) against fp32 torch references."""
+    """Full-vocabulary rows against fp32 torch references, on the kernels the sampler's plan
+    (sample_plan) picks for 64 and 4000 rows: for V % 8 == 0 bf16 / fp32 rows the two-stage pair
+    serves the greedy and top_k = 1 / 50 calls, the register-resident kernel top_k = 1000 and the
+    draw without top-k where the row fits (bf16 up to 64 Ki, fp32 up to 32 Ki logits) and the
+    streaming kernel where it does not; odd V and fp16 always take the streaming kernel."""
     torch.manual_seed(V)
     B = 64
     logits = (torch.randn(B, V, device=DEV) * 3).to(dt)
@@ -1433,6 +1436,52 @@ def test_decode_launchers_reject_bad_operands(entry):
             with pytest.raises(RuntimeError, match=f"^{entry}: "):
                 call(_launcher_operands(**{**base, **shape}))
     torch.cuda.synchronize()
+
+
+def test_sampler_and_decode_attn_reject_host_operands():
+    """sample_step, decode_attn and kv_append refuse, before any launch, an operand that is not on
+    the GPU (a host pointer would reach the kernel) and cache scales of the wrong shape; the valid
+    call that follows still gives the right answer."""
+    K = _ext.kernels()
+    torch.manual_seed(0)
+    B, V = 2, 1024
+    logits = torch.randn(B, V, device=DEV)
+    seed, step = torch.tensor([7], device=DEV), torch.tensor([1], device=DEV)
+    idx = torch.zeros(B, 1, dtype=torch.long, device=DEV)
+    out = torch.full((B, 4), -1, dtype=torch.long, device=DEV)
+    for bad in (dict(idx=idx.cpu()), dict(out=out.cpu())):
+        o = {**dict(idx=idx, out=out), **bad}
+        with pytest.raises(RuntimeError, match="^sample_step: "):
+            K.sample_step(logits, 0.0, 0, seed, step, o["idx"], o["out"])
+    K.sample_step(logits, 0.0, 0, seed, step, idx, out)
+    assert torch.equal(idx.view(-1), logits.argmax(-1)) and torch.equal(out[:, 1], idx.view(-1))
+    assert bool((out[:, [0, 2, 3]] == -1).all())
+
+    H, D, cap, S = 4, 64, 256, 100
+    rows = torch.randn(B, 1, 3 * H * D, device=DEV).bfloat16()
+    q, k, v = (rows[:, :, i * H * D:(i + 1) * H * D].view(B, 1, H, D) for i in range(3))
+    kq = torch.randint(-127, 127, (B, H, cap, D), device=DEV, dtype=torch.int8)
+    vq = torch.randint(-127, 127, (B, H, cap, D), device=DEV, dtype=torch.int8)
+    ks, vs = torch.rand(B, H, cap, device=DEV) * 0.02, torch.rand(B, H, cap, device=DEV) * 0.02
+    kc, vc = torch.randn(B, H, cap, D, device=DEV).bfloat16(), torch.randn(B, H, cap, D, device=DEV).bfloat16()
+    scale = 1.0 / math.sqrt(D)
+    with pytest.raises(RuntimeError, match="^decode_attn: "):
+        K.decode_attn(q, kq, vq, ks.cpu(), vs, S, S - 1, scale)
+    with pytest.raises(RuntimeError, match="^decode_attn: "):
+        K.decode_attn(q, kq, vq, ks, vs[:, :, :cap - 1].contiguous(), S, S - 1, scale)
+    with pytest.raises(RuntimeError, match="^decode_attn: "):
+        K.decode_attn(q, kc.clone(), vc.clone(), None, None, S, S - 1, scale, None, k.cpu(), v)
+    got = K.decode_attn(q, kq, vq, ks, vs, S, S - 1, scale)
+    ref = A.reference_cache_attention(q.float(), kq[:, :, :S].float() * ks[:, :, :S, None],
+                                      vq[:, :, :S].float() * vs[:, :, :S, None], S - 1)
+    _close(got, ref, 0.05, 0.02)
+    before = kc.clone()
+    with pytest.raises(RuntimeError, match="^kv_append: "):
+        K.kv_append(k, v, kc, vc, None, None, torch.tensor([S]), 0)
+    assert torch.equal(kc, before)
+    K.kv_append(k, v, kc, vc, None, None, torch.tensor([S], device=DEV), 0)
+    assert torch.equal(kc[:, :, S], k[:, 0]) and torch.equal(vc[:, :, S], v[:, 0])
+    assert torch.equal(kc[:, :, :S], before[:, :, :S]) and torch.equal(kc[:, :, S + 1:], before[:, :, S + 1:])
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

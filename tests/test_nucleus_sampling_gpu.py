@@ -50,6 +50,19 @@ PATHS = {
 ALL = sorted(PATHS)
 
 
+FREQ = {"reg": (1024, F32, 0), "stream": (4096, F16, 0), "rank": (1024, BF, 100), "merge": (8192, BF, 50)}
+# sample_plan's path (0 two-stage, 1 register, 2 streaming) that each label's prefix stands for
+LABEL_PATH = {"merge": 0, "reg": 1, "rank": 1, "stream": 2}
+
+
+@pytest.mark.parametrize("path", ALL + sorted(FREQ))
+def test_labels_name_the_kernel_the_launcher_picks(path):
+    """The launcher's own plan for the case with top_p = 0.9, at every row count the tests below use."""
+    V, dt, k = (PATHS[path] if path in PATHS else FREQ[path])[:3]
+    for B in (1, 8, 32, 64, 256, 2048, 4000):
+        assert _ext.kernels().sample_plan(dt, B, V, 0.8, k, True)[0] == LABEL_PATH[path.split("-")[0]], B
+
+
 def oracle(logits, T, top_k, exact_k, top_p=1.0, min_p=0.0):
     """fp64: (kept mask [B, V], renormalised probabilities [B, V], prefix masses / Z in
     descending-logit order [B, V])."""
@@ -153,9 +166,6 @@ def test_random_rows_draw_inside_the_nucleus(path):
         assert bool(mask.gather(1, t).all()), (path, u)
         again = K.sample_tokens(logits, torch.full((B,), u, device=DEV), 0.8, k, 0.9, 0.0)
         assert torch.equal(t, again)  # same inputs, same tokens
-
-
-FREQ = {"reg": (1024, F32, 0), "stream": (4096, F16, 0), "rank": (1024, BF, 100), "merge": (8192, BF, 50)}
 
 
 @pytest.mark.parametrize("cut", ["top_p", "min_p"])
