@@ -4,11 +4,17 @@ or a Gemma-3 1B shaped model (RoPE, GQA 4:1, head_dim 256, 262k vocab; HF config
 python bench/bench_decode.py [--model gpt2|gemma3-1b] [--batch 64] [--prompt 64] [--new 128] [--turbo]
                              [--top-k 50] [--top-p P] [--min-p P]      (--top-k 0: no top-k)
                              [--weights bf16|int8] [--ab ROUNDS]
+                             [--repetition-penalty R] [--presence-penalty P] [--frequency-penalty F]
+                             [--ab-penalties ROUNDS]
 Prints one JSON line: generated tokens/s over all rows (BASELINE config 4: batch 64 /generate).
 --weights int8: the batch 1-4 decode steps read int8 weight copies (ops/weight_quant.py). --ab ROUNDS:
 both weight formats on one model in this one process, alternating, ROUNDS timed runs each; the line
 then holds both arms (ms/step of every run, median, min, the linears' weight bytes per token and the
 rate they were read at) and the int8 / bf16 ratio of the medians.
+--repetition-penalty / --presence-penalty / --frequency-penalty: logit penalties (ops/penalties.py) in the
+decode step. --ab-penalties ROUNDS: the same process alternates between runs with those penalties and
+runs without (one decoder, its two captured graphs), ROUNDS timed runs each; the line holds both arms
+and the penalised / plain ratio of the medians.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,6 +40,11 @@ ap.add_argument("--top-p", type=float, default=None)
 ap.add_argument("--min-p", type=float, default=None)
 ap.add_argument("--weights", default="bf16", choices=["bf16", "int8"], help="decode weight format")
 ap.add_argument("--ab", type=int, default=0, metavar="ROUNDS", help="alternate bf16 and int8 weights, ROUNDS runs each")
+ap.add_argument("--repetition-penalty", type=float, default=None)
+ap.add_argument("--presence-penalty", type=float, default=None)
+ap.add_argument("--frequency-penalty", type=float, default=None)
+ap.add_argument("--ab-penalties", type=int, default=0, metavar="ROUNDS",
+                help="alternate runs with and without the penalties, ROUNDS runs each")
 a = ap.parse_args()
 if a.turbo:
     M.create_kv_cache = lambda n, cap=None: KV.TurboQuantKVCache(n, cap)
@@ -53,14 +64,17 @@ if a.dtype == "bf16":
     m.to(dtype=torch.bfloat16)
 ctx = torch.randint(0, V, (a.batch, a.prompt)).tolist()
 samp = dict(temperature=1.0, top_k=a.top_k or None, top_p=a.top_p, min_p=a.min_p)
+pens = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
+            frequency_penalty=a.frequency_penalty)
 
 
-def timed(weights: str, new: int) -> float:
+def timed(weights: str, new: int, penalised: bool = True) -> float:
     """Seconds of one generate_batch of ``new`` tokens with this weight format ("" selects bf16
-    whatever PENROZ_DECODE_WEIGHTS says)."""
+    whatever PENROZ_DECODE_WEIGHTS says), with the command line's penalties or without any."""
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    m.generate_batch(ctx, a.block, new, weight_quant="int8" if weights == "int8" else "", **samp)
+    m.generate_batch(ctx, a.block, new, weight_quant="int8" if weights == "int8" else "", **samp,
+                     **(pens if penalised else {}))
     torch.cuda.synchronize()
     return time.perf_counter() - t0
 
@@ -99,10 +113,33 @@ if a.ab:
                       "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
                       "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
     sys.exit(0)
+if a.ab_penalties:
+    from penroz.ops.penalties import check_penalties
+    assert check_penalties(**pens) is not None, "--ab-penalties needs a penalty that is not neutral"
+    arms = {"plain": [], "penalised": []}
+    for arm in arms:
+        timed(a.weights, 4, arm == "penalised")  # warmup: both graphs of the one decoder captured
+    for _ in range(a.ab_penalties):
+        for arm in arms:  # alternating: both arms see the same drift of clocks and neighbours
+            arms[arm].append(timed(a.weights, a.new, arm == "penalised") / a.new * 1e3)
+    res = {}
+    for arm, ms in arms.items():
+        med = sorted(ms)[len(ms) // 2]
+        res[arm] = {"ms_per_step": [round(v, 4) for v in ms], "median": round(med, 4), "min": round(min(ms), 4)}
+    decs = list(m.__dict__.get("_graph_decoders", {}).values())
+    print(json.dumps({"metric": "decode ms/step, with vs without logit penalties, alternating in one process",
+                      "arms": res, "penalised_over_plain_median": round(res["penalised"]["median"] / res["plain"]["median"], 4),
+                      "penalised_minus_plain_us": round((res["penalised"]["median"] - res["plain"]["median"]) * 1e3, 2),
+                      **pens, "decoders": len(decs), "batch": a.batch, "prompt": a.prompt, "new_tokens": a.new,
+                      "block": a.block, "rounds": a.ab_penalties, "top_k": a.top_k or None, "top_p": a.top_p,
+                      "min_p": a.min_p, "weights": a.weights, "weights_in_effect": in_effect(),
+                      "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
+                      "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
+    sys.exit(0)
 timed(a.weights, 4)  # warmup
 dt = timed(a.weights, a.new)
 print(json.dumps({"metric": "decode tokens/sec (all rows)", "value": a.batch * a.new / dt, "batch": a.batch,
                   "prompt": a.prompt, "new_tokens": a.new, "block": a.block, "ms_per_step": dt / a.new * 1e3, "dtype": a.dtype,
-                  "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p,
+                  "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p, **pens,
                   "weights": a.weights, "weights_in_effect": in_effect(),
                   "kv_cache": "int8-turboquant" if a.turbo else a.dtype, "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))

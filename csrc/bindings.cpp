@@ -68,6 +68,10 @@ void sample_step(torch::Tensor logits, double temperature, int64_t top_k, torch:
 void decode_advance(torch::Tensor a, torch::Tensor b, torch::Tensor c);
 std::tuple<int64_t, int64_t, int64_t, int64_t> sample_plan(at::ScalarType dtype, int64_t B, int64_t V, double temperature,
                                                            int64_t top_k, bool filtered, c10::optional<int64_t> min_rows);
+// logit_penalty.hip
+void penalty_begin(torch::Tensor cnt, torch::Tensor uniq, torch::Tensor n_uniq, torch::Tensor prompt);
+void penalty_apply(torch::Tensor logits, torch::Tensor cnt, torch::Tensor uniq, torch::Tensor n_uniq,
+                   torch::Tensor params, c10::optional<torch::Tensor> new_tok);
 // decode_attn.hip
 torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c10::optional<torch::Tensor> k_scale,
                           c10::optional<torch::Tensor> v_scale, int64_t S, int64_t q_offset, double scale,
@@ -233,6 +237,13 @@ PYBIND11_MODULE(penroz_kernels, m) {
         pybind11::arg("temperature"), pybind11::arg("top_k"), pybind11::arg("filtered") = false,
         pybind11::arg("two_stage_min_rows") = pybind11::none(),
         "the sampler's launch plan: (path 0 two-stage / 1 register / 2 streaming, slice, parts, part top_k) (host only)");
+  m.def("penalty_begin", &penalty_begin, pybind11::arg("cnt"), pybind11::arg("uniq"), pybind11::arg("n_uniq"),
+        pybind11::arg("prompt"),
+        "logit penalties, start of a generate call: clear the listed tokens' counts, mark the prompt's (int64 [B, T])");
+  m.def("penalty_apply", &penalty_apply, pybind11::arg("logits"), pybind11::arg("cnt"), pybind11::arg("uniq"),
+        pybind11::arg("n_uniq"), pybind11::arg("params"), pybind11::arg("new_tok") = pybind11::none(),
+        "logit penalties, one sampling: count new_tok (int64 [B]), then repetition / presence / frequency "
+        "(params fp32 [3]) on the listed tokens of logits [B, V], in place");
   m.def("decode_attn", &decode_attn, pybind11::arg("q"), pybind11::arg("kc"), pybind11::arg("vc"), pybind11::arg("k_scale"),
         pybind11::arg("v_scale"), pybind11::arg("S"), pybind11::arg("q_offset"), pybind11::arg("scale"),
         pybind11::arg("seq_len_dev") = pybind11::none(), pybind11::arg("k_new") = pybind11::none(),

@@ -29,6 +29,10 @@ between steps lives on the device:
 * with ``weight_quant="int8"`` the decode programs' batch 1-4 step reads int8 copies of every
   linear's weight (``ops/weight_quant.py``, ``csrc/kernels/decode_gemv_q8.hip``), built per weight
   version before the warm-up step; ``GraphDecoder.weight_quant`` records whether that is in effect.
+* repetition / presence / frequency penalties (``ops/penalties.py``, ``csrc/kernels/logit_penalty.hip``)
+  act on the logits between the lm_head and the sampler, from count tables the decoder owns; their
+  values are read from the device. The step with that kernel and the step without it are two graphs
+  of one decoder (``GraphDecoder.set_penalties``): same KV cache, same program.
 
 The host only tracks the cache length (one per replay) to switch to the reference's
 sliding-window re-prefill when the window is full, and copies each burst of tokens back once
@@ -53,6 +57,7 @@ from penroz.ops import attention as attn_ops
 from penroz.ops import fused as fused_ops
 from penroz.ops import gemm as gemm_ops
 from penroz.ops import norms as norm_ops
+from penroz.ops import penalties as pen_ops
 from penroz.ops import rope as rope_ops
 from penroz.ops import sampling as samp_ops
 from penroz.ops import weight_quant as wq_ops
@@ -709,6 +714,12 @@ class GraphDecoder:
             else:
                 _log_q8_unused(rows, self.program)
         self._done_t = torch.zeros(1, dtype=torch.int32, device=self.device)  # sample_step's arrival counter
+        # logit penalties: the state (made when first asked for; its buffers are static), whether the
+        # step applies them, and the captured graph of the mode ``graph`` does not hold right now
+        self.penalties: pen_ops.PenaltyState | None = None
+        self._penalised = False
+        self._count_new = True  # (False during a capture's warm-up step: its token is not a real one)
+        self._graphs: dict = {}
 
     # ------------------------------------------------------------------ cache attachment
     def attach(self):
@@ -737,6 +748,10 @@ class GraphDecoder:
                     acts, _ = model(self.idx, skip_softmax=True)
                 logits = acts[-1]
                 last = logits[:, -1, :] if logits.ndim == 3 else logits
+            if self._penalised:
+                # counts idx, the token the previous step sampled, then rewrites the seen tokens'
+                # logits in the tensor the sampler reads
+                last = self.penalties.apply(last.contiguous(), self.idx if self._count_new else None)
             if _ext.available() and last.is_cuda:
                 # one sampler kernel writes the token into the next step's input and the burst
                 # buffer (uniforms hashed on the device), one kernel advances the counters
@@ -778,6 +793,20 @@ class GraphDecoder:
         """Once per generate call: the seed every burst of this call derives from."""
         self.run_seed = int(run_seed) & (2 ** 64 - 1)
 
+    def set_penalties(self, values: tuple[float, float, float] | None):
+        """Once per generate call: ``ops.penalties.check_penalties``' result. None: ``run()`` replays
+        the step without the penalty kernel; values: the step with it, which reads them from the
+        device — other values replay the same graph. Each of the two graphs is captured on first use."""
+        on = values is not None
+        if on:
+            if self.penalties is None:
+                self.penalties = pen_ops.PenaltyState()
+            self.penalties.set_params(*values)
+        if on != self._penalised:
+            self._graphs[self._penalised] = self.graph
+            self.graph = self._graphs.pop(on, None)
+            self._penalised = on
+
     def _burst_seed(self, start: int) -> int:
         v = (self.run_seed + self._HASH_STEP * int(start)) & (2 ** 64 - 1)
         return v - 2 ** 64 if v >= 2 ** 63 else v
@@ -794,11 +823,18 @@ class GraphDecoder:
         # warm-up really executes a step, so it must start from the true state: it then writes
         # exactly the cache slot the first real step rewrites.
         self._set_state(last_tok, cache_len, start)
+        # the penalty tables exist and hold this call's prompt (the eager prefill step applied them):
+        # nothing is allocated inside the capture, and the warm-up step counts no token
+        assert not self._penalised or self.penalties.ready, "penalties: begin() and a first apply come before a capture"
         from penroz.models.executor import shared_stream
         side = shared_stream(self.device, "side")  # (no new pool stream per capture)
         side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            self._step()
+        self._count_new = False
+        try:
+            with torch.cuda.stream(side):
+                self._step()
+        finally:
+            self._count_new = True
         torch.cuda.current_stream(self.device).wait_stream(side)
         self._set_state(last_tok, cache_len, start)
         g = torch.cuda.CUDAGraph()
@@ -815,7 +851,8 @@ class GraphDecoder:
         self.graph = g
         self._set_state(last_tok, cache_len, start)  # capture does not execute; state is as before
         log.info(f"captured decode graph: rows={self.rows} block={self.capacity} "
-                 f"temperature={self.temperature} top_k={self.top_k} top_p={self.top_p} min_p={self.min_p}")
+                 f"temperature={self.temperature} top_k={self.top_k} top_p={self.top_p} min_p={self.min_p} "
+                 f"penalties={'on' if self._penalised else 'off'}")
 
     @torch.inference_mode()
     def run(self, last_tok: Tensor, n_steps: int, start: int = 0) -> Tensor:

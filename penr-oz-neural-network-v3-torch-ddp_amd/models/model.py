@@ -43,6 +43,7 @@ import torch.distributed as dist
 from penroz.models.kv_cache import KVCache, create_kv_cache
 from penroz.models.layers import CausalSelfAttention, PositionEmbedding, SoftmaxOnLast
 from penroz.models.mapper import Mapper
+from penroz.ops import penalties as pen_ops
 from penroz.ops import sampling as samp_ops
 from penroz.ops import fused as fused_ops
 from penroz.ops import weight_quant as wq_ops
@@ -377,9 +378,12 @@ class NeuralNetworkModel(nn.Module):
 
     def _prepare_generation(self, input_context: list, max_new_tokens: int, temperature: float, top_k: int | None,
                             top_p: float | None = None, min_p: float | None = None,
-                            weight_quant: str | None = None):
+                            weight_quant: str | None = None,
+                            *, repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                            frequency_penalty: float | None = None):
         samp_ops._check_filters(top_p, min_p)  # a bad range fails before any forward pass
         wq_ops.resolve(weight_quant)  # (and an unknown decode weight format)
+        pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)  # (and a bad penalty)
         self.eval()
         device = next(self.parameters()).device
         context = torch.tensor(input_context, dtype=torch.long, device=device)
@@ -388,6 +392,9 @@ class NeuralNetworkModel(nn.Module):
         top_k_msg = "" if top_k is None else f" top {top_k}"
         top_k_msg += "" if top_p is None else f" top_p {top_p}"
         top_k_msg += "" if min_p is None else f" min_p {min_p}"
+        for name, v in (("repetition", repetition_penalty), ("presence", presence_penalty),
+                        ("frequency", frequency_penalty)):
+            top_k_msg += "" if v is None else f" {name}_penalty {v}"
         log.info(f"Generating at most {max_new_tokens}{top_k_msg} tokens with {temperature} temperature "
                  f"using device {device}")
         softmax_layer = self.layers[-1] if self._is_softmax_last else SoftmaxOnLast(dim=-1)
@@ -397,7 +404,21 @@ class NeuralNetworkModel(nn.Module):
     def _generate_next_token(self, context: Tensor, block_size: int, temperature: float, top_k: int | None,
                              softmax_layer=None, kv_cache: KVCache | None = None,
                              pos_embeddings: list[PositionEmbedding] | None = None, *,
-                             top_p: float | None = None, min_p: float | None = None) -> Tensor:
+                             top_p: float | None = None, min_p: float | None = None,
+                             repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                             frequency_penalty: float | None = None,
+                             penalty_state: pen_ops.PenaltyState | None = None,
+                             penalty_new: Tensor | None = None) -> Tensor:
+        """``penalty_state``: the generate call's penalty bookkeeping (its values already set, its
+        ``begin`` run on the call's prompt); ``penalty_new`` [rows, 1]: the tokens the previous step
+        sampled, which this step counts (None on a call's first step). Penalty values without a state
+        take the whole ``context`` as the prompt."""
+        if penalty_state is None:
+            pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+            if pen is not None:
+                penalty_state, penalty_new = pen_ops.PenaltyState(), None
+                penalty_state.set_params(*pen)
+                penalty_state.begin(context)
         if kv_cache is not None and kv_cache.seq_len() > 0:
             if kv_cache.seq_len() >= block_size:
                 # sliding window: clear and re-prefill the last block_size tokens
@@ -414,40 +435,65 @@ class NeuralNetworkModel(nn.Module):
         activations, _ = self(model_input, skip_softmax=True)
         logits = activations[-1]
         last = logits[:, -1, :] if logits.ndim == 3 else logits
+        if penalty_state is not None:  # between the lm_head and the sampler, as in the captured step
+            last = penalty_state.apply(last.contiguous(), penalty_new)
         return samp_ops.sample(last, temperature, top_k, top_p=top_p, min_p=min_p)
 
     @torch.inference_mode()
     def generate_tokens(self, input_context: list, block_size: int, max_new_tokens: int,
                         temperature=1.0, top_k: int | None = None, stop_token: int | None = None, *,
                         top_p: float | None = None, min_p: float | None = None,
-                        weight_quant: str | None = None) -> list:
+                        weight_quant: str | None = None,
+                        repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                        frequency_penalty: float | None = None) -> list:
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
-        "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS."""
+        "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
+        ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
+        to the logits before temperature and the filters; 1.0 / 0.0 / 0.0 or None: off."""
         return [t for t in self._generate(input_context, block_size, max_new_tokens, temperature, top_k,
                                           stop_token, full_context=True, top_p=top_p, min_p=min_p,
-                                          weight_quant=weight_quant)][-1]
+                                          weight_quant=weight_quant, repetition_penalty=repetition_penalty,
+                                          presence_penalty=presence_penalty,
+                                          frequency_penalty=frequency_penalty)][-1]
 
     @torch.inference_mode()
     def generate_tokens_stream(self, input_context: list, block_size: int, max_new_tokens: int,
                                temperature=1.0, top_k: int | None = None, stop_token: int | None = None, *,
                                top_p: float | None = None, min_p: float | None = None,
-                               weight_quant: str | None = None):
+                               weight_quant: str | None = None,
+                               repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                               frequency_penalty: float | None = None):
         log.info("Streaming token generation started")
         for tok in self._generate(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
-                                  full_context=False, top_p=top_p, min_p=min_p, weight_quant=weight_quant):
+                                  full_context=False, top_p=top_p, min_p=min_p, weight_quant=weight_quant,
+                                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                                  frequency_penalty=frequency_penalty):
             yield tok
         log.info("Streaming token generation completed")
 
     def _token_bursts(self, context: Tensor, block_size: int, max_new_tokens: int, temperature, top_k,
                       softmax_layer, burst: int, *, top_p: float | None = None, min_p: float | None = None,
-                      weight_quant: str | None = None):
+                      weight_quant: str | None = None,
+                      repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                      frequency_penalty: float | None = None):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
-        (cache full) run eagerly, exactly as the per-token path."""
+        (cache full) run eagerly, exactly as the per-token path. Logit penalties keep one state per
+        call — the decoder's, where there is one, so the counts carry across bursts and re-prefills:
+        ``begin`` on the whole prompt, the first sampling counts nothing, every later one counts the
+        token sampled before it (eager steps: ``last``; graph steps: the decoder's ``idx``)."""
         from penroz.models import graph_decode
         rows = context.shape[0]
+        pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k, top_p, min_p,
                                        wq_ops.resolve(weight_quant))
+        if dec is not None:
+            dec.set_penalties(pen)
+        state = None
+        if pen is not None:
+            state = dec.penalties if dec is not None else pen_ops.PenaltyState()
+            state.set_params(*pen)
+            state.begin(context)
         if dec is None:
             cache, pos = self._attach_kv_cache(capacity=block_size)
         else:
@@ -465,7 +511,8 @@ class NeuralNetworkModel(nn.Module):
                 n = cache.seq_len() if cache is not None else 0
                 if dec is None or n == 0 or n >= block_size:
                     new = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache,
-                                                    pos, top_p=top_p, min_p=min_p)
+                                                    pos, top_p=top_p, min_p=min_p, penalty_state=state,
+                                                    penalty_new=last)
                     for p in pos:
                         p.position_offset = 0
                 else:
@@ -485,9 +532,13 @@ class NeuralNetworkModel(nn.Module):
                 dec.detach()
 
     def _generate(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token, full_context, *,
-                  top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None):
+                  top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None,
+                  repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                  frequency_penalty: float | None = None):
+        pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                    frequency_penalty=frequency_penalty)
         context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k,
-                                                          top_p, min_p, weight_quant)
+                                                          top_p, min_p, weight_quant, **pens)
         rows = context.shape[0]
         generated = []
         done = torch.zeros(rows, dtype=torch.bool)
@@ -495,7 +546,7 @@ class NeuralNetworkModel(nn.Module):
         stopped = False
         with torch.inference_mode():
             for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, softmax_layer,
-                                          burst, top_p=top_p, min_p=min_p, weight_quant=weight_quant):
+                                          burst, top_p=top_p, min_p=min_p, weight_quant=weight_quant, **pens):
                 toks = new.tolist()
                 for j in range(new.shape[1]):
                     col = [r[j] for r in toks]
@@ -514,10 +565,20 @@ class NeuralNetworkModel(nn.Module):
             yield context[0].tolist()
 
     def _generate_eager(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
-                        full_context, *, top_p: float | None = None, min_p: float | None = None):
+                        full_context, *, top_p: float | None = None, min_p: float | None = None,
+                        repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                        frequency_penalty: float | None = None):
         """Per-token path (kept for A/B and as the reference-shaped loop)."""
-        context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k,
-                                                          top_p, min_p)
+        context, softmax_layer = self._prepare_generation(
+            input_context, max_new_tokens, temperature, top_k, top_p, min_p,
+            repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+            frequency_penalty=frequency_penalty)
+        pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        state = last = None
+        if pen is not None:
+            state = pen_ops.PenaltyState()
+            state.set_params(*pen)
+            state.begin(context)
         cache, pos = self._attach_kv_cache(capacity=block_size)
         rows = context.shape[0]
         generated = []
@@ -526,8 +587,9 @@ class NeuralNetworkModel(nn.Module):
             with torch.inference_mode():
                 for _ in range(max_new_tokens):
                     nxt = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache, pos,
-                                                    top_p=top_p, min_p=min_p)
+                                                    top_p=top_p, min_p=min_p, penalty_state=state, penalty_new=last)
                     context = torch.cat((context, nxt.to(context.device)), dim=1)
+                    last = context[:, -1:]
                     toks = nxt.view(-1).tolist()
                     generated.append(toks[0])
                     if not full_context:
@@ -547,13 +609,17 @@ class NeuralNetworkModel(nn.Module):
     def generate_batch(self, input_context: list, block_size: int, max_new_tokens: int, temperature=1.0,
                        top_k: int | None = None, stop_token: int | None = None, *,
                        top_p: float | None = None, min_p: float | None = None,
-                       weight_quant: str | None = None) -> list[list[int]]:
+                       weight_quant: str | None = None,
+                       repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                       frequency_penalty: float | None = None) -> list[list[int]]:
         """All rows' contexts (the reference returns row 0 only — bug 5)."""
+        pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                    frequency_penalty=frequency_penalty)
         context, sm = self._prepare_generation(input_context, max_new_tokens, temperature, top_k, top_p, min_p,
-                                               weight_quant)
+                                               weight_quant, **pens)
         burst = 32 if stop_token is not None else max_new_tokens
         for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, sm, burst,
-                                      top_p=top_p, min_p=min_p, weight_quant=weight_quant):
+                                      top_p=top_p, min_p=min_p, weight_quant=weight_quant, **pens):
             if stop_token is not None:
                 hit = (new == stop_token).all(dim=0).nonzero()
                 if hit.numel():

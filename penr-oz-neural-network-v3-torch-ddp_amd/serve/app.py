@@ -28,6 +28,8 @@ from typing import Dict
 
 from fastapi import Body, FastAPI, HTTPException, Request
 from fastapi.concurrency import run_in_threadpool
+from fastapi.encoders import jsonable_encoder
+from fastapi.exceptions import RequestValidationError
 from fastapi.params import Query
 from fastapi.responses import HTMLResponse, JSONResponse, RedirectResponse, Response, StreamingResponse
 from fastapi.staticfiles import StaticFiles
@@ -136,6 +138,14 @@ class GenerateRequest(ModelRequest):
                                 description="Nucleus sampling: keep the most likely tokens up to this probability mass")
     min_p: float | None = Field(None, ge=0, lt=1, examples=[None],
                                 description="Keep tokens at least this likely relative to the most likely one")
+    repetition_penalty: float | None = Field(None, gt=0, allow_inf_nan=False, examples=[None],
+                                             description="Divide the positive (multiply the negative) logits of tokens "
+                                                         "seen in the prompt or generated so far; 1.0: off")
+    presence_penalty: float | None = Field(None, allow_inf_nan=False, examples=[None],
+                                           description="Subtracted from the logit of every token generated so far")
+    frequency_penalty: float | None = Field(None, allow_inf_nan=False, examples=[None],
+                                            description="Subtracted from a token's logit once per time it was "
+                                                        "generated")
     stop_token: int | None = Field(None, examples=[None], description="Token id that halts generation")
     weight_quant: str | None = Field(None, examples=[None],
                                      description="Decode weight format: \"int8\" (weight-only int8 for batch 1-4 "
@@ -194,6 +204,23 @@ async def key_error_handler(_: Request, e: KeyError):
 @app.exception_handler(ValueError)
 async def value_error_handler(_: Request, e: ValueError):
     raise HTTPException(status_code=400, detail=f"Value error occurred: {e}")
+
+
+def _json_safe(v):
+    """Non-finite floats as text: a 422 echoes the offending input, and NaN / Infinity (which the
+    schema refuses, e.g. for the logit penalties) are not JSON."""
+    if isinstance(v, float) and not math.isfinite(v):
+        return str(v)
+    if isinstance(v, dict):
+        return {k: _json_safe(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_json_safe(x) for x in v]
+    return v
+
+
+@app.exception_handler(RequestValidationError)
+async def validation_error_handler(_: Request, e: RequestValidationError):
+    return JSONResponse(status_code=422, content={"detail": jsonable_encoder(_json_safe(e.errors()))})
 
 
 # ------------------------------------------------------------------------------ serving cache
@@ -414,6 +441,8 @@ def model_generate(body: GenerateRequest = Body(...)):
     if body.weight_quant is not None:  # an unknown format is a 400 before the model is touched (streams too)
         wq_ops.resolve(body.weight_quant)
     model = load_for_serving(body.model_id)
+    penalties = dict(repetition_penalty=body.repetition_penalty, presence_penalty=body.presence_penalty,
+                     frequency_penalty=body.frequency_penalty)
     if body.stream:
         # the lock is held for the stream's whole lifetime (the KV cache stays attached between
         # chunks) and released by the background task even when the client goes away mid-stream
@@ -421,12 +450,12 @@ def model_generate(body: GenerateRequest = Body(...)):
         st = _LockedStream(model, model.generate_tokens_stream(body.input, body.block_size, body.max_new_tokens,
                                                               body.temperature, body.top_k, body.stop_token,
                                                               top_p=body.top_p, min_p=body.min_p,
-                                                              weight_quant=body.weight_quant))
+                                                              weight_quant=body.weight_quant, **penalties))
         return StreamingResponse(st.gen, media_type="text/plain", background=BackgroundTask(st.close))
     with _Held(model):
         tokens = model.generate_tokens(body.input, body.block_size, body.max_new_tokens, body.temperature,
                                        body.top_k, body.stop_token, top_p=body.top_p, min_p=body.min_p,
-                                       weight_quant=body.weight_quant)
+                                       weight_quant=body.weight_quant, **penalties)
     return {"tokens": tokens}
 
 
