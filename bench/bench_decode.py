@@ -6,6 +6,7 @@ python bench/bench_decode.py [--model gpt2|gemma3-1b] [--batch 64] [--prompt 64]
                              [--weights bf16|int8] [--ab ROUNDS]
                              [--repetition-penalty R] [--presence-penalty P] [--frequency-penalty F]
                              [--ab-penalties ROUNDS]
+                             [--logprobs N[,N...]] [--ab-logprobs ROUNDS]
 Prints one JSON line: generated tokens/s over all rows (BASELINE config 4: batch 64 /generate).
 --weights int8: the batch 1-4 decode steps read int8 weight copies (ops/weight_quant.py). --ab ROUNDS:
 both weight formats on one model in this one process, alternating, ROUNDS timed runs each; the line
@@ -15,6 +16,10 @@ rate they were read at) and the int8 / bf16 ratio of the medians.
 decode step. --ab-penalties ROUNDS: the same process alternates between runs with those penalties and
 runs without (one decoder, its two captured graphs), ROUNDS timed runs each; the line holds both arms
 and the penalised / plain ratio of the medians.
+--logprobs N: per-token log-probabilities with the N most likely tokens (ops/logprobs.py) in the decode
+step. --ab-logprobs ROUNDS: the same process alternates between runs without them and runs with every
+N listed (one decoder, two captured graphs, N read on the device), ROUNDS timed runs each; the line holds
+every arm and its difference to the run without. A run's time includes reading the results back.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -45,7 +50,12 @@ ap.add_argument("--presence-penalty", type=float, default=None)
 ap.add_argument("--frequency-penalty", type=float, default=None)
 ap.add_argument("--ab-penalties", type=int, default=0, metavar="ROUNDS",
                 help="alternate runs with and without the penalties, ROUNDS runs each")
+ap.add_argument("--logprobs", default=None, metavar="N[,N...]",
+                help="log-probabilities with the N most likely tokens (0-20); a list for --ab-logprobs")
+ap.add_argument("--ab-logprobs", type=int, default=0, metavar="ROUNDS",
+                help="alternate runs without log-probabilities and with every N of --logprobs, ROUNDS runs each")
 a = ap.parse_args()
+lp_ns = [int(v) for v in a.logprobs.split(",")] if a.logprobs else []
 if a.turbo:
     M.create_kv_cache = lambda n, cap=None: KV.TurboQuantKVCache(n, cap)
 torch.manual_seed(0)
@@ -68,13 +78,14 @@ pens = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence
             frequency_penalty=a.frequency_penalty)
 
 
-def timed(weights: str, new: int, penalised: bool = True) -> float:
+def timed(weights: str, new: int, penalised: bool = True, logprobs: int | None = None) -> float:
     """Seconds of one generate_batch of ``new`` tokens with this weight format ("" selects bf16
-    whatever PENROZ_DECODE_WEIGHTS says), with the command line's penalties or without any."""
+    whatever PENROZ_DECODE_WEIGHTS says), with the command line's penalties or without any, and
+    with ``logprobs`` (None: without)."""
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     m.generate_batch(ctx, a.block, new, weight_quant="int8" if weights == "int8" else "", **samp,
-                     **(pens if penalised else {}))
+                     **(pens if penalised else {}), logprobs=logprobs)
     torch.cuda.synchronize()
     return time.perf_counter() - t0
 
@@ -136,10 +147,34 @@ if a.ab_penalties:
                       "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
                       "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
     sys.exit(0)
-timed(a.weights, 4)  # warmup
-dt = timed(a.weights, a.new)
+if a.ab_logprobs:
+    assert lp_ns, "--ab-logprobs needs --logprobs N[,N...]"
+    arms = {None: [], **{n: [] for n in lp_ns}}
+    for arm in arms:
+        timed(a.weights, 4, logprobs=arm)  # warmup: both graphs of the one decoder captured
+    for _ in range(a.ab_logprobs):
+        for arm in arms:  # alternating: every arm sees the same drift of clocks and neighbours
+            arms[arm].append(timed(a.weights, a.new, logprobs=arm) / a.new * 1e3)
+    res = {}
+    for arm, ms in arms.items():
+        med = sorted(ms)[len(ms) // 2]
+        res["off" if arm is None else f"n={arm}"] = {"ms_per_step": [round(v, 4) for v in ms], "median": round(med, 4),
+                                                     "min": round(min(ms), 4)}
+    for k, v in res.items():
+        v["minus_off_us"] = round((v["median"] - res["off"]["median"]) * 1e3, 2)
+    decs = list(m.__dict__.get("_graph_decoders", {}).values())
+    print(json.dumps({"metric": "decode ms/step, without vs with log-probabilities, alternating in one process",
+                      "arms": res, **pens, "decoders": len(decs), "batch": a.batch, "prompt": a.prompt,
+                      "new_tokens": a.new, "block": a.block, "rounds": a.ab_logprobs, "top_k": a.top_k or None,
+                      "top_p": a.top_p, "min_p": a.min_p, "weights": a.weights, "weights_in_effect": in_effect(),
+                      "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
+                      "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
+    sys.exit(0)
+lp_n = lp_ns[0] if lp_ns else None
+timed(a.weights, 4, logprobs=lp_n)  # warmup
+dt = timed(a.weights, a.new, logprobs=lp_n)
 print(json.dumps({"metric": "decode tokens/sec (all rows)", "value": a.batch * a.new / dt, "batch": a.batch,
                   "prompt": a.prompt, "new_tokens": a.new, "block": a.block, "ms_per_step": dt / a.new * 1e3, "dtype": a.dtype,
-                  "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p, **pens,
+                  "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p, **pens, "logprobs": lp_n,
                   "weights": a.weights, "weights_in_effect": in_effect(),
                   "kv_cache": "int8-turboquant" if a.turbo else a.dtype, "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))

@@ -126,6 +126,13 @@ std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t> decode_gemv_q8_limits();
 std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t> decode_gemv_q8_plan(int64_t M, int64_t N, int64_t K, bool ln,
                                                                             int64_t rows_per_wave);
 std::tuple<int64_t, int64_t, int64_t> decode_gemv_q8_pair_plan(int64_t N, int64_t K, int64_t pairs_per_wave);
+// token_logprobs.hip
+std::tuple<int64_t, int64_t> token_logprobs_plan(int64_t V);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> token_logprobs(torch::Tensor logits, torch::Tensor tokens,
+                                                                       int64_t n);
+void token_logprobs_step(torch::Tensor logits, torch::Tensor idx, torch::Tensor step, torch::Tensor n_t,
+                         torch::Tensor lp_buf, torch::Tensor top_id_buf, torch::Tensor top_lp_buf,
+                         torch::Tensor workspace);
 // adamw.hip
 torch::Tensor update_moments(std::vector<torch::Tensor> ws, std::vector<torch::Tensor> ps);
 // gemm_nt.hip
@@ -237,6 +244,16 @@ PYBIND11_MODULE(penroz_kernels, m) {
         pybind11::arg("temperature"), pybind11::arg("top_k"), pybind11::arg("filtered") = false,
         pybind11::arg("two_stage_min_rows") = pybind11::none(),
         "the sampler's launch plan: (path 0 two-stage / 1 register / 2 streaming, slice, parts, part top_k) (host only)");
+  m.def("token_logprobs_plan", &token_logprobs_plan, pybind11::arg("V"),
+        "token_logprobs' launch plan: (parts per row, fp32 workspace floats per row); V above 1 Mi is refused (host only)");
+  m.def("token_logprobs", &token_logprobs, pybind11::arg("logits"), pybind11::arg("tokens"), pybind11::arg("n"),
+        "log-probability of tokens (int64 [B]) under logits [B, V] and the n <= 20 most likely tokens: "
+        "(lp fp32 [B], top_id int64 [B, min(n, V)], top_lp fp32 [B, min(n, V)])");
+  m.def("token_logprobs_step", &token_logprobs_step, pybind11::arg("logits"), pybind11::arg("idx"),
+        pybind11::arg("step"), pybind11::arg("n_t"), pybind11::arg("lp_buf"), pybind11::arg("top_id_buf"),
+        pybind11::arg("top_lp_buf"), pybind11::arg("workspace"),
+        "decode-step log-probabilities, after the sampler and the counter advance: writes column *step - 1 of "
+        "lp_buf [B, cap] and top_id_buf (int32) / top_lp_buf [B, cap, 20]; n_t int32 [1] on the device");
   m.def("penalty_begin", &penalty_begin, pybind11::arg("cnt"), pybind11::arg("uniq"), pybind11::arg("n_uniq"),
         pybind11::arg("prompt"),
         "logit penalties, start of a generate call: clear the listed tokens' counts, mark the prompt's (int64 [B, T])");

@@ -283,6 +283,20 @@ inline SamplePlan plan_sample(Elem e, int B, int V, bool temp, int top_k, bool n
   return {SamplePath::Stream, 0, 0, 0};
 }
 
+// ---- token log-probabilities launch plan (token_logprobs.hip) ----
+constexpr int kLogprobPartN = 4096, kLogprobMaxN = 20, kLogprobMaxParts = 256;  // logits per part, largest n, most parts
+struct LogprobPlan {
+  int parts;          // part workgroups per row (0: V is outside [1, 1 Mi])
+  int64_t ws_floats;  // workspace per row: m [P], s [P] and the parts' candidates, 64-bit keys [P, kLogprobMaxN]
+};
+
+// One merge workgroup has a thread per part, so a row has at most 256 parts: V <= 1 Mi.
+inline LogprobPlan plan_logprobs(int64_t V) {
+  if (V < 1 || V > (int64_t)kLogprobMaxParts * kLogprobPartN) return {0, 0};
+  const int parts = (int)((V + kLogprobPartN - 1) / kLogprobPartN);
+  return {parts, (int64_t)parts * (2 + 2 * kLogprobMaxN)};
+}
+
 // ---- decode attention launch plan (decode_attn.hip) ----
 constexpr int kMaxMergeSplits = 16, kMergeMaxKeys = 8192;  // in-launch merge: most splits, longest context
 // What is built: decode_kernel<D, GC> with an exact group size GC only for head_dim 64 / 128 / 256 (GC 0: any

@@ -33,6 +33,10 @@ between steps lives on the device:
   act on the logits between the lm_head and the sampler, from count tables the decoder owns; their
   values are read from the device. The step with that kernel and the step without it are two graphs
   of one decoder (``GraphDecoder.set_penalties``): same KV cache, same program.
+* per-token log-probabilities (``ops/logprobs.py``, ``csrc/kernels/token_logprobs.hip``) are computed
+  behind the sampler from the logits it read and the token it wrote, into burst buffers the decoder
+  owns; ``n`` is read from the device. With them the step is another graph of the same decoder
+  (``GraphDecoder.set_logprobs``): up to four, by (penalised, log-probabilities on).
 
 The host only tracks the cache length (one per replay) to switch to the reference's
 sliding-window re-prefill when the window is full, and copies each burst of tokens back once
@@ -56,6 +60,7 @@ from penroz.ops import activations as act_ops
 from penroz.ops import attention as attn_ops
 from penroz.ops import fused as fused_ops
 from penroz.ops import gemm as gemm_ops
+from penroz.ops import logprobs as lp_ops
 from penroz.ops import norms as norm_ops
 from penroz.ops import penalties as pen_ops
 from penroz.ops import rope as rope_ops
@@ -719,7 +724,12 @@ class GraphDecoder:
         self.penalties: pen_ops.PenaltyState | None = None
         self._penalised = False
         self._count_new = True  # (False during a capture's warm-up step: its token is not a real one)
-        self._graphs: dict = {}
+        # per-token log-probabilities: the buffers (made when first asked for), whether the step computes
+        # them, and what the last run() left: (lp [rows, n_steps], top_id, top_lp [rows, n_steps, 20]) or None
+        self.logprobs: lp_ops.LogprobState | None = None
+        self._lp_on = False
+        self.last_logprobs: tuple[Tensor, Tensor, Tensor] | None = None
+        self._graphs: dict = {}  # (penalised, log-probabilities on) -> the captured graphs ``graph`` is not
 
     # ------------------------------------------------------------------ cache attachment
     def attach(self):
@@ -752,6 +762,7 @@ class GraphDecoder:
                 # counts idx, the token the previous step sampled, then rewrites the seen tokens'
                 # logits in the tensor the sampler reads
                 last = self.penalties.apply(last.contiguous(), self.idx if self._count_new else None)
+            last = last.contiguous()  # the one tensor the sampler and the log-probabilities read
             if _ext.available() and last.is_cuda:
                 # one sampler kernel writes the token into the next step's input and the burst
                 # buffer (uniforms hashed on the device), one kernel advances the counters
@@ -760,11 +771,11 @@ class GraphDecoder:
                 # the nucleus / min-p cut is made by the sampler inside the captured graph
                 nuc = () if self.top_p is None and self.min_p is None else (self.top_p or 1.0, self.min_p or 0.0)
                 if FUSED_ADVANCE:  # the sampler's last row advances the counters itself
-                    _ext.kernels().sample_step(last.contiguous(), self.temperature, k, self.seed_t, self.step_t,
+                    _ext.kernels().sample_step(last, self.temperature, k, self.seed_t, self.step_t,
                                                self.idx, self.out, self.cache.pos_t, self.cache.len_t, self._done_t,
                                                *nuc)
                 else:
-                    _ext.kernels().sample_step(last.contiguous(), self.temperature, k, self.seed_t, self.step_t,
+                    _ext.kernels().sample_step(last, self.temperature, k, self.seed_t, self.step_t,
                                                self.idx, self.out, None, None, None, *nuc)
                     _ext.kernels().decode_advance(self.cache.pos_t, self.cache.len_t, self.step_t)
             else:
@@ -775,6 +786,10 @@ class GraphDecoder:
                 self.cache.pos_t.add_(1)
                 self.cache.len_t.add_(1)
                 self.step_t.add_(1)
+            if self._lp_on:
+                # behind the sampler and the counter advance: idx holds the token just chosen, and
+                # column step_t - 1 of the burst buffers is this step's
+                lp_ops.step_logprobs(self.logprobs, last, self.idx, self.step_t)
         finally:
             self.cache.graph_mode = False
             for p in self.pos_layers:
@@ -802,10 +817,25 @@ class GraphDecoder:
             if self.penalties is None:
                 self.penalties = pen_ops.PenaltyState()
             self.penalties.set_params(*values)
-        if on != self._penalised:
-            self._graphs[self._penalised] = self.graph
-            self.graph = self._graphs.pop(on, None)
-            self._penalised = on
+        self._select(on, self._lp_on)
+
+    def set_logprobs(self, n: int | None):
+        """Once per generate call: ``ops.logprobs.check_logprobs``' result. None: ``run()`` replays the
+        step as it is without them, no kernel more; a number: the step with the two log-probability
+        kernels, which read ``n`` from the device — other values replay the same graph."""
+        on = n is not None
+        if on:
+            if self.logprobs is None:
+                self.logprobs = lp_ops.LogprobState(self.rows, self.capacity, self.device)
+            self.logprobs.set_n(n)
+        self._select(self._penalised, on)
+
+    def _select(self, penalised: bool, lp_on: bool):
+        """Make ``graph`` the captured step of this mode (None: captured on first use)."""
+        if (penalised, lp_on) != (self._penalised, self._lp_on):
+            self._graphs[(self._penalised, self._lp_on)] = self.graph
+            self.graph = self._graphs.pop((penalised, lp_on), None)
+            self._penalised, self._lp_on = penalised, lp_on
 
     def _burst_seed(self, start: int) -> int:
         v = (self.run_seed + self._HASH_STEP * int(start)) & (2 ** 64 - 1)
@@ -852,13 +882,14 @@ class GraphDecoder:
         self._set_state(last_tok, cache_len, start)  # capture does not execute; state is as before
         log.info(f"captured decode graph: rows={self.rows} block={self.capacity} "
                  f"temperature={self.temperature} top_k={self.top_k} top_p={self.top_p} min_p={self.min_p} "
-                 f"penalties={'on' if self._penalised else 'off'}")
+                 f"penalties={'on' if self._penalised else 'off'} logprobs={'on' if self._lp_on else 'off'}")
 
     @torch.inference_mode()
     def run(self, last_tok: Tensor, n_steps: int, start: int = 0) -> Tensor:
         """Decode ``n_steps`` tokens after ``last_tok`` [rows, 1] from the current cache; returns
         the [rows, n_steps] new tokens (device). ``start``: absolute index (within this generate
-        call) of the first of them. The cache must have room for n_steps more."""
+        call) of the first of them. The cache must have room for n_steps more. With log-probabilities
+        on, ``last_logprobs`` then holds this burst's (views of the burst buffers, like the tokens)."""
         cache_len = self.cache.seq_len()
         assert 0 < cache_len and cache_len + n_steps <= self.capacity, (cache_len, n_steps, self.capacity)
         if self.graph is None:
@@ -868,6 +899,7 @@ class GraphDecoder:
         for _ in range(n_steps):
             self.graph.replay()
         self.cache._len = [cache_len + n_steps] * self.cache.num_layers
+        self.last_logprobs = self.logprobs.burst(n_steps) if self._lp_on else None
         return self.out[:, :n_steps]
 
 

@@ -43,6 +43,7 @@ import torch.distributed as dist
 from penroz.models.kv_cache import KVCache, create_kv_cache
 from penroz.models.layers import CausalSelfAttention, PositionEmbedding, SoftmaxOnLast
 from penroz.models.mapper import Mapper
+from penroz.ops import logprobs as lp_ops
 from penroz.ops import penalties as pen_ops
 from penroz.ops import sampling as samp_ops
 from penroz.ops import fused as fused_ops
@@ -380,10 +381,11 @@ class NeuralNetworkModel(nn.Module):
                             top_p: float | None = None, min_p: float | None = None,
                             weight_quant: str | None = None,
                             *, repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                            frequency_penalty: float | None = None):
+                            frequency_penalty: float | None = None, logprobs: int | None = None):
         samp_ops._check_filters(top_p, min_p)  # a bad range fails before any forward pass
         wq_ops.resolve(weight_quant)  # (and an unknown decode weight format)
         pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)  # (and a bad penalty)
+        lp_ops.check_logprobs(logprobs)  # (and a bad number of log-probabilities)
         self.eval()
         device = next(self.parameters()).device
         context = torch.tensor(input_context, dtype=torch.long, device=device)
@@ -395,6 +397,7 @@ class NeuralNetworkModel(nn.Module):
         for name, v in (("repetition", repetition_penalty), ("presence", presence_penalty),
                         ("frequency", frequency_penalty)):
             top_k_msg += "" if v is None else f" {name}_penalty {v}"
+        top_k_msg += "" if logprobs is None else f" logprobs {logprobs}"
         log.info(f"Generating at most {max_new_tokens}{top_k_msg} tokens with {temperature} temperature "
                  f"using device {device}")
         softmax_layer = self.layers[-1] if self._is_softmax_last else SoftmaxOnLast(dim=-1)
@@ -408,11 +411,12 @@ class NeuralNetworkModel(nn.Module):
                              repetition_penalty: float | None = None, presence_penalty: float | None = None,
                              frequency_penalty: float | None = None,
                              penalty_state: pen_ops.PenaltyState | None = None,
-                             penalty_new: Tensor | None = None) -> Tensor:
+                             penalty_new: Tensor | None = None, logprobs: int | None = None):
         """``penalty_state``: the generate call's penalty bookkeeping (its values already set, its
         ``begin`` run on the call's prompt); ``penalty_new`` [rows, 1]: the tokens the previous step
         sampled, which this step counts (None on a call's first step). Penalty values without a state
-        take the whole ``context`` as the prompt."""
+        take the whole ``context`` as the prompt. ``logprobs`` n: returns (tokens, ``ops.logprobs.
+        token_logprobs`` of the logits the sampler was given) instead of the tokens alone."""
         if penalty_state is None:
             pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
             if pen is not None:
@@ -437,7 +441,9 @@ class NeuralNetworkModel(nn.Module):
         last = logits[:, -1, :] if logits.ndim == 3 else logits
         if penalty_state is not None:  # between the lm_head and the sampler, as in the captured step
             last = penalty_state.apply(last.contiguous(), penalty_new)
-        return samp_ops.sample(last, temperature, top_k, top_p=top_p, min_p=min_p)
+        nxt = samp_ops.sample(last, temperature, top_k, top_p=top_p, min_p=min_p)
+        n = lp_ops.check_logprobs(logprobs)
+        return nxt if n is None else (nxt, lp_ops.token_logprobs(last, nxt, n))
 
     @torch.inference_mode()
     def generate_tokens(self, input_context: list, block_size: int, max_new_tokens: int,
@@ -445,16 +451,19 @@ class NeuralNetworkModel(nn.Module):
                         top_p: float | None = None, min_p: float | None = None,
                         weight_quant: str | None = None,
                         repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                        frequency_penalty: float | None = None) -> list:
+                        frequency_penalty: float | None = None, logprobs: int | None = None):
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
         "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
-        to the logits before temperature and the filters; 1.0 / 0.0 / 0.0 or None: off."""
+        to the logits before temperature and the filters; 1.0 / 0.0 / 0.0 or None: off.
+        ``logprobs`` n in 0..20 (ops/logprobs.py): returns ``(tokens, info)`` instead of the tokens, with
+        ``info = {"token_logprobs": [float, ...], "top_logprobs": [[[id, logprob], ... n], ...]}``, one
+        entry per generated token of row 0, the stop token included."""
         return [t for t in self._generate(input_context, block_size, max_new_tokens, temperature, top_k,
                                           stop_token, full_context=True, top_p=top_p, min_p=min_p,
                                           weight_quant=weight_quant, repetition_penalty=repetition_penalty,
                                           presence_penalty=presence_penalty,
-                                          frequency_penalty=frequency_penalty)][-1]
+                                          frequency_penalty=frequency_penalty, logprobs=logprobs)][-1]
 
     @torch.inference_mode()
     def generate_tokens_stream(self, input_context: list, block_size: int, max_new_tokens: int,
@@ -462,12 +471,13 @@ class NeuralNetworkModel(nn.Module):
                                top_p: float | None = None, min_p: float | None = None,
                                weight_quant: str | None = None,
                                repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                               frequency_penalty: float | None = None):
+                               frequency_penalty: float | None = None, logprobs: int | None = None):
+        """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``."""
         log.info("Streaming token generation started")
         for tok in self._generate(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
                                   full_context=False, top_p=top_p, min_p=min_p, weight_quant=weight_quant,
                                   repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                                  frequency_penalty=frequency_penalty):
+                                  frequency_penalty=frequency_penalty, logprobs=logprobs):
             yield tok
         log.info("Streaming token generation completed")
 
@@ -475,20 +485,25 @@ class NeuralNetworkModel(nn.Module):
                       softmax_layer, burst: int, *, top_p: float | None = None, min_p: float | None = None,
                       weight_quant: str | None = None,
                       repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                      frequency_penalty: float | None = None):
+                      frequency_penalty: float | None = None, logprobs: int | None = None):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
         (cache full) run eagerly, exactly as the per-token path. Logit penalties keep one state per
         call — the decoder's, where there is one, so the counts carry across bursts and re-prefills:
         ``begin`` on the whole prompt, the first sampling counts nothing, every later one counts the
-        token sampled before it (eager steps: ``last``; graph steps: the decoder's ``idx``)."""
+        token sampled before it (eager steps: ``last``; graph steps: the decoder's ``idx``).
+        With ``logprobs`` n every item is ``(new, (lp [rows, k], top_id, top_lp [rows, k, >= min(n, V)]))``
+        (device; ``ops.logprobs.to_lists`` reads them): a burst's from the decoder's buffers, an eager
+        step's from ``ops.logprobs.token_logprobs``, in generation order."""
         from penroz.models import graph_decode
         rows = context.shape[0]
+        n_lp = lp_ops.check_logprobs(logprobs)
         pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k, top_p, min_p,
                                        wq_ops.resolve(weight_quant))
         if dec is not None:
             dec.set_penalties(pen)
+            dec.set_logprobs(n_lp)
         state = None
         if pen is not None:
             state = dec.penalties if dec is not None else pen_ops.PenaltyState()
@@ -512,17 +527,20 @@ class NeuralNetworkModel(nn.Module):
                 if dec is None or n == 0 or n >= block_size:
                     new = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache,
                                                     pos, top_p=top_p, min_p=min_p, penalty_state=state,
-                                                    penalty_new=last)
+                                                    penalty_new=last, logprobs=n_lp)
+                    if n_lp is not None:
+                        new, lps = new[0], tuple(t.unsqueeze(1) for t in new[1])  # one step: [rows, 1, ...]
                     for p in pos:
                         p.position_offset = 0
                 else:
                     k = min(remaining, block_size - n, burst)
                     new = dec.run(last, k, start=produced)
+                    lps = dec.last_logprobs
                 context = torch.cat((context, new.to(context.device)), dim=1)
                 last = context[:, -1:]
                 remaining -= new.shape[1]
                 produced += new.shape[1]
-                yield new
+                yield new if n_lp is None else (new, lps)
         finally:
             if cache is not None:
                 cache.log_metrics()
@@ -534,26 +552,33 @@ class NeuralNetworkModel(nn.Module):
     def _generate(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token, full_context, *,
                   top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None,
                   repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                  frequency_penalty: float | None = None):
+                  frequency_penalty: float | None = None, logprobs: int | None = None):
         pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                    frequency_penalty=frequency_penalty)
+                    frequency_penalty=frequency_penalty, logprobs=logprobs)
         context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k,
                                                           top_p, min_p, weight_quant, **pens)
         rows = context.shape[0]
         generated = []
+        info = {"token_logprobs": [], "top_logprobs": []}  # row 0's, when asked for
         done = torch.zeros(rows, dtype=torch.bool)
         burst = 1 if (not full_context or stop_token is not None) else max_new_tokens
         stopped = False
         with torch.inference_mode():
             for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, softmax_layer,
                                           burst, top_p=top_p, min_p=min_p, weight_quant=weight_quant, **pens):
+                if logprobs is not None:  # copied back once per burst, with the tokens
+                    new, lps = new
+                    lp0, top0 = (r[0] for r in lp_ops.to_lists(*(t[:1] for t in lps), logprobs))
                 toks = new.tolist()
                 for j in range(new.shape[1]):
                     col = [r[j] for r in toks]
                     context = torch.cat((context, new[:, j:j + 1].to(context.device)), dim=1)
                     generated.append(col[0])
+                    if logprobs is not None:
+                        info["token_logprobs"].append(lp0[j])
+                        info["top_logprobs"].append(top0[j])
                     if not full_context:
-                        yield col[0]
+                        yield col[0] if logprobs is None else (col[0], lp0[j], top0[j])
                     if stop_token is not None:
                         done |= torch.tensor([t == stop_token for t in col])
                         if bool(done[0]) and (rows == 1 or bool(done.all())):
@@ -562,17 +587,18 @@ class NeuralNetworkModel(nn.Module):
                 if stopped:
                     break
         if full_context:
-            yield context[0].tolist()
+            yield context[0].tolist() if logprobs is None else (context[0].tolist(), info)
 
     def _generate_eager(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
                         full_context, *, top_p: float | None = None, min_p: float | None = None,
                         repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                        frequency_penalty: float | None = None):
+                        frequency_penalty: float | None = None, logprobs: int | None = None):
         """Per-token path (kept for A/B and as the reference-shaped loop)."""
         context, softmax_layer = self._prepare_generation(
             input_context, max_new_tokens, temperature, top_k, top_p, min_p,
             repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-            frequency_penalty=frequency_penalty)
+            frequency_penalty=frequency_penalty, logprobs=logprobs)
+        info = {"token_logprobs": [], "top_logprobs": []}
         pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         state = last = None
         if pen is not None:
@@ -587,13 +613,19 @@ class NeuralNetworkModel(nn.Module):
             with torch.inference_mode():
                 for _ in range(max_new_tokens):
                     nxt = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache, pos,
-                                                    top_p=top_p, min_p=min_p, penalty_state=state, penalty_new=last)
+                                                    top_p=top_p, min_p=min_p, penalty_state=state, penalty_new=last,
+                                                    logprobs=logprobs)
+                    if logprobs is not None:
+                        nxt, lps = nxt
+                        lp0, top0 = (r[0][0] for r in lp_ops.to_lists(*(t[:1].unsqueeze(1) for t in lps), logprobs))
+                        info["token_logprobs"].append(lp0)
+                        info["top_logprobs"].append(top0)
                     context = torch.cat((context, nxt.to(context.device)), dim=1)
                     last = context[:, -1:]
                     toks = nxt.view(-1).tolist()
                     generated.append(toks[0])
                     if not full_context:
-                        yield toks[0]
+                        yield toks[0] if logprobs is None else (toks[0], lp0, top0)
                     if stop_token is not None:
                         done |= torch.tensor([t == stop_token for t in toks])
                         if bool(done[0]) and (rows == 1 or bool(done.all())):
@@ -603,7 +635,7 @@ class NeuralNetworkModel(nn.Module):
                 cache.log_metrics()
             self._detach_kv_cache(pos)
         if full_context:
-            yield context[0].tolist()
+            yield context[0].tolist() if logprobs is None else (context[0].tolist(), info)
 
     @torch.inference_mode()
     def generate_batch(self, input_context: list, block_size: int, max_new_tokens: int, temperature=1.0,
@@ -611,22 +643,33 @@ class NeuralNetworkModel(nn.Module):
                        top_p: float | None = None, min_p: float | None = None,
                        weight_quant: str | None = None,
                        repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                       frequency_penalty: float | None = None) -> list[list[int]]:
-        """All rows' contexts (the reference returns row 0 only — bug 5)."""
+                       frequency_penalty: float | None = None, logprobs: int | None = None):
+        """All rows' contexts (the reference returns row 0 only — bug 5). With ``logprobs`` n:
+        ``(contexts, [info per row])``, each ``info`` (``generate_tokens``) as long as that row's
+        returned continuation."""
         pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                    frequency_penalty=frequency_penalty)
+                    frequency_penalty=frequency_penalty, logprobs=logprobs)
         context, sm = self._prepare_generation(input_context, max_new_tokens, temperature, top_k, top_p, min_p,
                                                weight_quant, **pens)
+        infos = [{"token_logprobs": [], "top_logprobs": []} for _ in range(context.shape[0])]
         burst = 32 if stop_token is not None else max_new_tokens
         for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, sm, burst,
                                       top_p=top_p, min_p=min_p, weight_quant=weight_quant, **pens):
+            if logprobs is not None:
+                new, lps = new
+            keep, stopped = new.shape[1], False
             if stop_token is not None:
                 hit = (new == stop_token).all(dim=0).nonzero()
                 if hit.numel():
-                    context = torch.cat((context, new[:, :int(hit[0]) + 1].to(context.device)), dim=1)
-                    break
-            context = torch.cat((context, new.to(context.device)), dim=1)
-        return context.tolist()
+                    keep, stopped = int(hit[0]) + 1, True
+            context = torch.cat((context, new[:, :keep].to(context.device)), dim=1)
+            if logprobs is not None:
+                for info, lp, top in zip(infos, *lp_ops.to_lists(*(t[:, :keep] for t in lps), logprobs)):
+                    info["token_logprobs"] += lp
+                    info["top_logprobs"] += top
+            if stopped:
+                break
+        return context.tolist() if logprobs is None else (context.tolist(), infos)
 
     # ------------------------------------------------------------------ training
     @classmethod

@@ -146,6 +146,9 @@ class GenerateRequest(ModelRequest):
     frequency_penalty: float | None = Field(None, allow_inf_nan=False, examples=[None],
                                             description="Subtracted from a token's logit once per time it was "
                                                         "generated")
+    logprobs: int | None = Field(None, ge=0, le=20, examples=[None],
+                                 description="Return each generated token's log-probability and this many most "
+                                             "likely tokens with theirs (0: the chosen tokens' only); null: off")
     stop_token: int | None = Field(None, examples=[None], description="Token id that halts generation")
     weight_quant: str | None = Field(None, examples=[None],
                                      description="Decode weight format: \"int8\" (weight-only int8 for batch 1-4 "
@@ -274,6 +277,13 @@ class _Held:
         self.lock.release()
 
 
+def _logprob_line(item) -> str:
+    """A streamed (token, logprob, [[id, logprob], ...]) as ``token<TAB>logprob`` and one
+    ``<TAB>id:logprob`` per top entry; floats by ``repr`` (they read back exactly)."""
+    token, lp, top = item
+    return "\t".join([str(token), repr(lp)] + [f"{i}:{v!r}" for i, v in top])
+
+
 class _LockedStream:
     """A token stream that owns the model's serving lock from before the response starts until
     the stream is finished OR abandoned. The response's background task (run by Starlette after
@@ -281,7 +291,8 @@ class _LockedStream:
     while a threadpool thread is still inside it producing a token — so its ``finally`` releases
     the lock at once instead of whenever the abandoned generator is garbage-collected."""
 
-    def __init__(self, model, tokens):
+    def __init__(self, model, tokens, line=str):
+        self.line = line  # an item of ``tokens`` as the text of its line
         self.lock = serving_lock(model)
         if not self.lock.acquire(timeout=_lock_timeout_s()):
             raise HTTPException(status_code=503, detail="Model is busy serving another request; retry later.")
@@ -298,7 +309,7 @@ class _LockedStream:
     def _run(self, tokens):
         try:
             for token in tokens:
-                yield f"{token}\n"
+                yield f"{self.line(token)}\n"
         finally:
             self._release()
 
@@ -443,6 +454,8 @@ def model_generate(body: GenerateRequest = Body(...)):
     model = load_for_serving(body.model_id)
     penalties = dict(repetition_penalty=body.repetition_penalty, presence_penalty=body.presence_penalty,
                      frequency_penalty=body.frequency_penalty)
+    if body.logprobs is not None:  # (a keyword of its own only when asked for: without it the calls are as before)
+        penalties["logprobs"] = body.logprobs
     if body.stream:
         # the lock is held for the stream's whole lifetime (the KV cache stays attached between
         # chunks) and released by the background task even when the client goes away mid-stream
@@ -450,12 +463,16 @@ def model_generate(body: GenerateRequest = Body(...)):
         st = _LockedStream(model, model.generate_tokens_stream(body.input, body.block_size, body.max_new_tokens,
                                                               body.temperature, body.top_k, body.stop_token,
                                                               top_p=body.top_p, min_p=body.min_p,
-                                                              weight_quant=body.weight_quant, **penalties))
+                                                              weight_quant=body.weight_quant, **penalties),
+                           line=str if body.logprobs is None else _logprob_line)
         return StreamingResponse(st.gen, media_type="text/plain", background=BackgroundTask(st.close))
     with _Held(model):
         tokens = model.generate_tokens(body.input, body.block_size, body.max_new_tokens, body.temperature,
                                        body.top_k, body.stop_token, top_p=body.top_p, min_p=body.min_p,
                                        weight_quant=body.weight_quant, **penalties)
+    if body.logprobs is not None:
+        tokens, info = tokens
+        return {"tokens": tokens, "logprobs": info}
     return {"tokens": tokens}
 
 
