@@ -7,6 +7,7 @@ python bench/bench_decode.py [--model gpt2|gemma3-1b] [--batch 64] [--prompt 64]
                              [--repetition-penalty R] [--presence-penalty P] [--frequency-penalty F]
                              [--ab-penalties ROUNDS]
                              [--logprobs N[,N...]] [--ab-logprobs ROUNDS]
+                             [--stop IDS[/IDS...]] [--ab-stop ROUNDS]
 Prints one JSON line: generated tokens/s over all rows (BASELINE config 4: batch 64 /generate).
 --weights int8: the batch 1-4 decode steps read int8 weight copies (ops/weight_quant.py). --ab ROUNDS:
 both weight formats on one model in this one process, alternating, ROUNDS timed runs each; the line
@@ -20,6 +21,12 @@ and the penalised / plain ratio of the medians.
 step. --ab-logprobs ROUNDS: the same process alternates between runs without them and runs with every
 N listed (one decoder, two captured graphs, N read on the device), ROUNDS timed runs each; the line holds
 every arm and its difference to the run without. A run's time includes reading the results back.
+--stop IDS: stop sequences (ops/stopping.py), each a comma-separated list of token ids, several divided by
+"/", checked on the device at the end of the decode step; the default of --ab-stop is one sequence of eight
+ids, which random weights never complete, so every run generates all its tokens. --ab-stop ROUNDS: the same
+process alternates between runs without and with the stop check (one decoder, two captured graphs, bursts of
+PENROZ_STOP_BURST steps in the second), ROUNDS timed runs each; the line holds both arms, their difference
+and how many rows finished early (0 is what the comparison needs).
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -54,7 +61,14 @@ ap.add_argument("--logprobs", default=None, metavar="N[,N...]",
                 help="log-probabilities with the N most likely tokens (0-20); a list for --ab-logprobs")
 ap.add_argument("--ab-logprobs", type=int, default=0, metavar="ROUNDS",
                 help="alternate runs without log-probabilities and with every N of --logprobs, ROUNDS runs each")
+ap.add_argument("--stop", default=None, metavar="IDS[/IDS...]",
+                help="stop sequences: comma-separated token ids, several divided by '/'")
+ap.add_argument("--ab-stop", type=int, default=0, metavar="ROUNDS",
+                help="alternate runs without and with the stop check, ROUNDS runs each")
 a = ap.parse_args()
+if a.ab_stop and not a.stop:
+    a.stop = "1,2,3,4,5,6,7,8"
+stop_seqs = [[int(t) for t in seq.split(",")] for seq in a.stop.split("/")] if a.stop else None
 lp_ns = [int(v) for v in a.logprobs.split(",")] if a.logprobs else []
 if a.turbo:
     M.create_kv_cache = lambda n, cap=None: KV.TurboQuantKVCache(n, cap)
@@ -78,16 +92,23 @@ pens = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence
             frequency_penalty=a.frequency_penalty)
 
 
-def timed(weights: str, new: int, penalised: bool = True, logprobs: int | None = None) -> float:
+early = 0  # rows of the last timed() run that a stop sequence finished
+
+
+def timed(weights: str, new: int, penalised: bool = True, logprobs: int | None = None, stop=None) -> float:
     """Seconds of one generate_batch of ``new`` tokens with this weight format ("" selects bf16
-    whatever PENROZ_DECODE_WEIGHTS says), with the command line's penalties or without any, and
-    with ``logprobs`` (None: without)."""
+    whatever PENROZ_DECODE_WEIGHTS says), with the command line's penalties or without any, with
+    ``logprobs`` (None: without) and with the stop sequences ``stop`` (None: without)."""
+    global early
+    kw = {} if stop is None else {"stop": stop}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    m.generate_batch(ctx, a.block, new, weight_quant="int8" if weights == "int8" else "", **samp,
-                     **(pens if penalised else {}), logprobs=logprobs)
+    out = m.generate_batch(ctx, a.block, new, weight_quant="int8" if weights == "int8" else "", **samp,
+                           **(pens if penalised else {}), logprobs=logprobs, **kw)
     torch.cuda.synchronize()
-    return time.perf_counter() - t0
+    dt = time.perf_counter() - t0
+    early = sum(i["finish_reason"] == "stop" for i in out[1]) if stop is not None else 0
+    return dt
 
 
 def weight_bytes(weights: str) -> int:
@@ -170,11 +191,35 @@ if a.ab_logprobs:
                       "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
                       "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
     sys.exit(0)
+if a.ab_stop:
+    arms = {"off": [], "on": []}
+    finished = 0
+    for arm in arms:
+        timed(a.weights, 4, stop=stop_seqs if arm == "on" else None)  # warmup: both graphs of the one decoder captured
+    for _ in range(a.ab_stop):
+        for arm in arms:  # alternating: both arms see the same drift of clocks and neighbours
+            arms[arm].append(timed(a.weights, a.new, stop=stop_seqs if arm == "on" else None) / a.new * 1e3)
+            finished += early
+    res = {}
+    for arm, ms in arms.items():
+        med = sorted(ms)[len(ms) // 2]
+        res[arm] = {"ms_per_step": [round(v, 4) for v in ms], "median": round(med, 4), "min": round(min(ms), 4)}
+    decs = list(m.__dict__.get("_graph_decoders", {}).values())
+    print(json.dumps({"metric": "decode ms/step, without vs with the stop check, alternating in one process",
+                      "arms": res, "on_minus_off_us": round((res["on"]["median"] - res["off"]["median"]) * 1e3, 2),
+                      "on_minus_off_min_us": round((res["on"]["min"] - res["off"]["min"]) * 1e3, 2),
+                      "stop": stop_seqs, "rows_finished_early": finished, "stop_burst": M._stop_burst(), **pens,
+                      "decoders": len(decs), "batch": a.batch, "prompt": a.prompt, "new_tokens": a.new,
+                      "block": a.block, "rounds": a.ab_stop, "top_k": a.top_k or None, "top_p": a.top_p,
+                      "min_p": a.min_p, "weights": a.weights, "weights_in_effect": in_effect(),
+                      "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
+                      "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
+    sys.exit(0)
 lp_n = lp_ns[0] if lp_ns else None
-timed(a.weights, 4, logprobs=lp_n)  # warmup
-dt = timed(a.weights, a.new, logprobs=lp_n)
+timed(a.weights, 4, logprobs=lp_n, stop=stop_seqs)  # warmup
+dt = timed(a.weights, a.new, logprobs=lp_n, stop=stop_seqs)
 print(json.dumps({"metric": "decode tokens/sec (all rows)", "value": a.batch * a.new / dt, "batch": a.batch,
                   "prompt": a.prompt, "new_tokens": a.new, "block": a.block, "ms_per_step": dt / a.new * 1e3, "dtype": a.dtype,
                   "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p, **pens, "logprobs": lp_n,
-                  "weights": a.weights, "weights_in_effect": in_effect(),
+                  "stop": stop_seqs, "weights": a.weights, "weights_in_effect": in_effect(),
                   "kv_cache": "int8-turboquant" if a.turbo else a.dtype, "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))

@@ -133,6 +133,13 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> token_logprobs(torch::Te
 void token_logprobs_step(torch::Tensor logits, torch::Tensor idx, torch::Tensor step, torch::Tensor n_t,
                          torch::Tensor lp_buf, torch::Tensor top_id_buf, torch::Tensor top_lp_buf,
                          torch::Tensor workspace);
+// stop_check.hip
+void stop_begin(torch::Tensor tail, torch::Tensor n_gen, torch::Tensor done, torch::Tensor finish_at);
+void stop_observe(torch::Tensor seqs, torch::Tensor seq_len, torch::Tensor n_seqs, torch::Tensor tail,
+                  torch::Tensor n_gen, torch::Tensor done, torch::Tensor finish_at, torch::Tensor tok);
+void stop_step(torch::Tensor seqs, torch::Tensor seq_len, torch::Tensor n_seqs, torch::Tensor tail,
+               torch::Tensor n_gen, torch::Tensor done, torch::Tensor finish_at, torch::Tensor idx,
+               torch::Tensor out_buf, torch::Tensor step);
 // adamw.hip
 torch::Tensor update_moments(std::vector<torch::Tensor> ws, std::vector<torch::Tensor> ps);
 // gemm_nt.hip
@@ -254,6 +261,19 @@ PYBIND11_MODULE(penroz_kernels, m) {
         pybind11::arg("top_lp_buf"), pybind11::arg("workspace"),
         "decode-step log-probabilities, after the sampler and the counter advance: writes column *step - 1 of "
         "lp_buf [B, cap] and top_id_buf (int32) / top_lp_buf [B, cap, 20]; n_t int32 [1] on the device");
+  m.def("stop_begin", &stop_begin, pybind11::arg("tail"), pybind11::arg("n_gen"), pybind11::arg("done"),
+        pybind11::arg("finish_at"),
+        "stop sequences, start of a generate call: clear tail (int32 [B, 8], -1), n_gen, done and finish_at (int32 [B])");
+  m.def("stop_observe", &stop_observe, pybind11::arg("seqs"), pybind11::arg("seq_len"), pybind11::arg("n_seqs"),
+        pybind11::arg("tail"), pybind11::arg("n_gen"), pybind11::arg("done"), pybind11::arg("finish_at"),
+        pybind11::arg("tok"),
+        "stop sequences, one generated token per row (int64 [B], in place): running rows are checked against "
+        "seqs int32 [16, 8] / seq_len int32 [16] / n_seqs int32 [1], finished rows get their finishing token");
+  m.def("stop_step", &stop_step, pybind11::arg("seqs"), pybind11::arg("seq_len"), pybind11::arg("n_seqs"),
+        pybind11::arg("tail"), pybind11::arg("n_gen"), pybind11::arg("done"), pybind11::arg("finish_at"),
+        pybind11::arg("idx"), pybind11::arg("out_buf"), pybind11::arg("step"),
+        "stop_observe at the end of a decode step, after the sampler and the counter advance: the token is idx "
+        "[B, 1]; finished rows rewrite it and out_buf[b, *step - 1]");
   m.def("penalty_begin", &penalty_begin, pybind11::arg("cnt"), pybind11::arg("uniq"), pybind11::arg("n_uniq"),
         pybind11::arg("prompt"),
         "logit penalties, start of a generate call: clear the listed tokens' counts, mark the prompt's (int64 [B, T])");

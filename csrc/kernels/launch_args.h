@@ -1,5 +1,5 @@
 // Operand checks of the decode-step launch wrappers (decode_linear.hip, skinny_gemm.hip,
-// decode_gemv_q8.hip, decode_attn.hip, sampling.hip, logit_penalty.hip, token_logprobs.hip), written once. Each checks one operand and
+// decode_gemv_q8.hip, decode_attn.hip, sampling.hip, logit_penalty.hip, token_logprobs.hip, stop_check.hip), written once. Each checks one operand and
 // returns its typed pointer; `who` is the entry point's name for the message. Where the entry
 // points differ, the difference is a parameter. Also the wrappers' dtype -> element type dispatch
 // and their read of an integer environment switch. Host only.
@@ -47,6 +47,13 @@ inline int64_t* la_i64_scalar(const char* who, const char* what, const torch::Te
   TORCH_CHECK(t.defined() && t.is_cuda() && t.scalar_type() == torch::kInt64 && t.numel() == 1, who, ": ", what,
               " must be a device int64 [1]");
   return t.data_ptr<int64_t>();
+}
+
+// int32 contiguous tensor of exactly this shape (the stop check's sequences and per-row state)
+inline int* la_i32_shape(const char* who, const char* what, const torch::Tensor& t, at::IntArrayRef shape) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.scalar_type() == torch::kInt32 && t.is_contiguous() && t.sizes() == shape,
+              who, ": int32 contiguous ", what, " ", shape);
+  return t.data_ptr<int>();
 }
 
 // fp32 contiguous tensor of exactly this shape (the int8 cache's per-token scales)

@@ -36,7 +36,12 @@ between steps lives on the device:
 * per-token log-probabilities (``ops/logprobs.py``, ``csrc/kernels/token_logprobs.hip``) are computed
   behind the sampler from the logits it read and the token it wrote, into burst buffers the decoder
   owns; ``n`` is read from the device. With them the step is another graph of the same decoder
-  (``GraphDecoder.set_logprobs``): up to four, by (penalised, log-probabilities on).
+  (``GraphDecoder.set_logprobs``): by (penalised, log-probabilities on).
+* stop sequences (``ops/stopping.py``, ``csrc/kernels/stop_check.hip``) are checked by the step's last
+  kernel against the token just chosen: per-row finish state on the device, finished rows frozen on
+  their finishing token in the next step's input and the burst buffer. The stop set is read from the
+  device; the step with the check is a further graph of the decoder (``GraphDecoder.set_stop``): up to
+  eight, by (penalised, log-probabilities on, stop check on).
 
 The host only tracks the cache length (one per replay) to switch to the reference's
 sliding-window re-prefill when the window is full, and copies each burst of tokens back once
@@ -65,6 +70,7 @@ from penroz.ops import norms as norm_ops
 from penroz.ops import penalties as pen_ops
 from penroz.ops import rope as rope_ops
 from penroz.ops import sampling as samp_ops
+from penroz.ops import stopping as stop_ops
 from penroz.ops import weight_quant as wq_ops
 
 log = logging.getLogger(__name__)
@@ -729,7 +735,10 @@ class GraphDecoder:
         self.logprobs: lp_ops.LogprobState | None = None
         self._lp_on = False
         self.last_logprobs: tuple[Tensor, Tensor, Tensor] | None = None
-        self._graphs: dict = {}  # (penalised, log-probabilities on) -> the captured graphs ``graph`` is not
+        # stop sequences: the state (made when first asked for) and whether the step ends with the check
+        self.stop: stop_ops.StopState | None = None
+        self._stop_on = False
+        self._graphs: dict = {}  # (penalised, log-probabilities on, stop check on) -> the captured graphs ``graph`` is not
 
     # ------------------------------------------------------------------ cache attachment
     def attach(self):
@@ -790,6 +799,10 @@ class GraphDecoder:
                 # behind the sampler and the counter advance: idx holds the token just chosen, and
                 # column step_t - 1 of the burst buffers is this step's
                 lp_ops.step_logprobs(self.logprobs, last, self.idx, self.step_t)
+            if self._stop_on and self._count_new:
+                # last in the step: checks the token just chosen, and freezes the rows that finished
+                # before on theirs (idx and this step's column of the burst buffer)
+                self.stop.step(self.idx, self.out, self.step_t)
         finally:
             self.cache.graph_mode = False
             for p in self.pos_layers:
@@ -817,7 +830,7 @@ class GraphDecoder:
             if self.penalties is None:
                 self.penalties = pen_ops.PenaltyState()
             self.penalties.set_params(*values)
-        self._select(on, self._lp_on)
+        self._select(on, self._lp_on, self._stop_on)
 
     def set_logprobs(self, n: int | None):
         """Once per generate call: ``ops.logprobs.check_logprobs``' result. None: ``run()`` replays the
@@ -828,14 +841,27 @@ class GraphDecoder:
             if self.logprobs is None:
                 self.logprobs = lp_ops.LogprobState(self.rows, self.capacity, self.device)
             self.logprobs.set_n(n)
-        self._select(self._penalised, on)
+        self._select(self._penalised, on, self._stop_on)
 
-    def _select(self, penalised: bool, lp_on: bool):
+    def set_stop(self, stop: list[list[int]] | None):
+        """Once per generate call: ``ops.stopping.check_stop``'s result. None: ``run()`` replays the step
+        as it is without the check, no kernel more; sequences: the step that ends with the stop check,
+        which reads them from the device — another set replays the same graph. The caller runs
+        ``stop.begin()`` once per call and reads ``stop.read()`` after a burst."""
+        on = stop is not None
+        if on:
+            if self.stop is None:
+                self.stop = stop_ops.StopState(self.rows, self.device)
+            self.stop.set_stop(stop)
+        self._select(self._penalised, self._lp_on, on)
+
+    def _select(self, penalised: bool, lp_on: bool, stop_on: bool):
         """Make ``graph`` the captured step of this mode (None: captured on first use)."""
-        if (penalised, lp_on) != (self._penalised, self._lp_on):
-            self._graphs[(self._penalised, self._lp_on)] = self.graph
-            self.graph = self._graphs.pop((penalised, lp_on), None)
-            self._penalised, self._lp_on = penalised, lp_on
+        mode = (self._penalised, self._lp_on, self._stop_on)
+        if (penalised, lp_on, stop_on) != mode:
+            self._graphs[mode] = self.graph
+            self.graph = self._graphs.pop((penalised, lp_on, stop_on), None)
+            self._penalised, self._lp_on, self._stop_on = penalised, lp_on, stop_on
 
     def _burst_seed(self, start: int) -> int:
         v = (self.run_seed + self._HASH_STEP * int(start)) & (2 ** 64 - 1)
@@ -882,7 +908,8 @@ class GraphDecoder:
         self._set_state(last_tok, cache_len, start)  # capture does not execute; state is as before
         log.info(f"captured decode graph: rows={self.rows} block={self.capacity} "
                  f"temperature={self.temperature} top_k={self.top_k} top_p={self.top_p} min_p={self.min_p} "
-                 f"penalties={'on' if self._penalised else 'off'} logprobs={'on' if self._lp_on else 'off'}")
+                 f"penalties={'on' if self._penalised else 'off'} logprobs={'on' if self._lp_on else 'off'} "
+                 f"stop={'on' if self._stop_on else 'off'}")
 
     @torch.inference_mode()
     def run(self, last_tok: Tensor, n_steps: int, start: int = 0) -> Tensor:

@@ -46,6 +46,7 @@ from penroz.models.mapper import Mapper
 from penroz.ops import logprobs as lp_ops
 from penroz.ops import penalties as pen_ops
 from penroz.ops import sampling as samp_ops
+from penroz.ops import stopping as stop_ops
 from penroz.ops import fused as fused_ops
 from penroz.ops import weight_quant as wq_ops
 from penroz.parallel import dist as ddp
@@ -55,6 +56,13 @@ from penroz.utils import diagnostics
 
 log = logging.getLogger(__name__)
 MODELS_FOLDER = ckpt.MODELS_FOLDER
+
+
+def _stop_burst() -> int:
+    """PENROZ_STOP_BURST: with stop sequences, the most decode steps a graph burst replays before the
+    host reads the rows' finish state (with the tokens). A row that finishes inside a burst costs the
+    rest of it in frozen steps; a short burst costs a host round trip more often. Read per call."""
+    return max(1, int(os.environ.get("PENROZ_STOP_BURST", "16")))
 
 
 def _status(code: str, message: str) -> dict:
@@ -377,15 +385,27 @@ class NeuralNetworkModel(nn.Module):
         for p in (pos_embeddings or self._find_position_embeddings()):
             p.position_offset = 0
 
+    def _vocab_size(self) -> int | None:
+        """How many logits a row has, where the layer list shows it (it ends with a linear layer)."""
+        for layer in reversed(list(self.layers)):
+            if isinstance(layer, nn.Linear):
+                return layer.out_features
+            if not isinstance(layer, SoftmaxOnLast):
+                return None
+        return None
+
     def _prepare_generation(self, input_context: list, max_new_tokens: int, temperature: float, top_k: int | None,
                             top_p: float | None = None, min_p: float | None = None,
                             weight_quant: str | None = None,
                             *, repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                            frequency_penalty: float | None = None, logprobs: int | None = None):
+                            frequency_penalty: float | None = None, logprobs: int | None = None,
+                            stop: list | None = None, stop_token: int | None = None):
         samp_ops._check_filters(top_p, min_p)  # a bad range fails before any forward pass
         wq_ops.resolve(weight_quant)  # (and an unknown decode weight format)
         pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)  # (and a bad penalty)
         lp_ops.check_logprobs(logprobs)  # (and a bad number of log-probabilities)
+        if stop_ops.check_stop(stop, self._vocab_size()) is not None and stop_token is not None:  # (and a bad stop set)
+            raise ValueError("give stop_token or stop, not both (a stop_token s is the stop sequence [s])")
         self.eval()
         device = next(self.parameters()).device
         context = torch.tensor(input_context, dtype=torch.long, device=device)
@@ -398,6 +418,7 @@ class NeuralNetworkModel(nn.Module):
                         ("frequency", frequency_penalty)):
             top_k_msg += "" if v is None else f" {name}_penalty {v}"
         top_k_msg += "" if logprobs is None else f" logprobs {logprobs}"
+        top_k_msg += "" if not stop else f" stop {len(stop)} sequences"
         log.info(f"Generating at most {max_new_tokens}{top_k_msg} tokens with {temperature} temperature "
                  f"using device {device}")
         softmax_layer = self.layers[-1] if self._is_softmax_last else SoftmaxOnLast(dim=-1)
@@ -411,12 +432,20 @@ class NeuralNetworkModel(nn.Module):
                              repetition_penalty: float | None = None, presence_penalty: float | None = None,
                              frequency_penalty: float | None = None,
                              penalty_state: pen_ops.PenaltyState | None = None,
-                             penalty_new: Tensor | None = None, logprobs: int | None = None):
+                             penalty_new: Tensor | None = None, logprobs: int | None = None,
+                             stop: list | None = None, stop_state: stop_ops.StopState | None = None):
         """``penalty_state``: the generate call's penalty bookkeeping (its values already set, its
         ``begin`` run on the call's prompt); ``penalty_new`` [rows, 1]: the tokens the previous step
         sampled, which this step counts (None on a call's first step). Penalty values without a state
         take the whole ``context`` as the prompt. ``logprobs`` n: returns (tokens, ``ops.logprobs.
-        token_logprobs`` of the logits the sampler was given) instead of the tokens alone."""
+        token_logprobs`` of the logits the sampler was given) instead of the tokens alone.
+        ``stop_state``: the generate call's stop bookkeeping (ops/stopping.py); the sampled tokens pass
+        through its ``observe`` — rows that finished before get their finishing token — before they are
+        returned. ``stop`` without a state: this token is the call's first (the prompt takes no part)."""
+        if stop_state is None and stop_ops.check_stop(stop, self._vocab_size()) is not None:
+            stop_state = stop_ops.StopState(context.shape[0], context.device)
+            stop_state.set_stop(stop_ops.check_stop(stop))
+            stop_state.begin()
         if penalty_state is None:
             pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
             if pen is not None:
@@ -443,7 +472,10 @@ class NeuralNetworkModel(nn.Module):
             last = penalty_state.apply(last.contiguous(), penalty_new)
         nxt = samp_ops.sample(last, temperature, top_k, top_p=top_p, min_p=min_p)
         n = lp_ops.check_logprobs(logprobs)
-        return nxt if n is None else (nxt, lp_ops.token_logprobs(last, nxt, n))
+        lps = None if n is None else lp_ops.token_logprobs(last, nxt, n)  # (of the token as sampled)
+        if stop_state is not None:
+            nxt = stop_state.observe(nxt)
+        return nxt if n is None else (nxt, lps)
 
     @torch.inference_mode()
     def generate_tokens(self, input_context: list, block_size: int, max_new_tokens: int,
@@ -451,19 +483,24 @@ class NeuralNetworkModel(nn.Module):
                         top_p: float | None = None, min_p: float | None = None,
                         weight_quant: str | None = None,
                         repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                        frequency_penalty: float | None = None, logprobs: int | None = None):
+                        frequency_penalty: float | None = None, logprobs: int | None = None,
+                        stop: list | None = None):
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
         "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
         to the logits before temperature and the filters; 1.0 / 0.0 / 0.0 or None: off.
         ``logprobs`` n in 0..20 (ops/logprobs.py): returns ``(tokens, info)`` instead of the tokens, with
         ``info = {"token_logprobs": [float, ...], "top_logprobs": [[[id, logprob], ... n], ...]}``, one
-        entry per generated token of row 0, the stop token included."""
+        entry per generated token of row 0, the stop token included.
+        ``stop``: up to 16 sequences of up to 8 token ids (ops/stopping.py), checked on the device against
+        the generated tokens; generation ends with the first sequence completed, which is kept. Returns
+        ``(tokens, info)`` with ``info["finish_reason"]`` "stop" or "length" and ``info["stop_sequence"]``
+        the index into ``stop`` or None (beside the log-probability entries, when both are asked for)."""
         return [t for t in self._generate(input_context, block_size, max_new_tokens, temperature, top_k,
                                           stop_token, full_context=True, top_p=top_p, min_p=min_p,
                                           weight_quant=weight_quant, repetition_penalty=repetition_penalty,
                                           presence_penalty=presence_penalty,
-                                          frequency_penalty=frequency_penalty, logprobs=logprobs)][-1]
+                                          frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop)][-1]
 
     @torch.inference_mode()
     def generate_tokens_stream(self, input_context: list, block_size: int, max_new_tokens: int,
@@ -471,13 +508,15 @@ class NeuralNetworkModel(nn.Module):
                                top_p: float | None = None, min_p: float | None = None,
                                weight_quant: str | None = None,
                                repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                               frequency_penalty: float | None = None, logprobs: int | None = None):
-        """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``."""
+                               frequency_penalty: float | None = None, logprobs: int | None = None,
+                               stop: list | None = None):
+        """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``. With
+        ``stop`` the stream ends with the token that completes a stop sequence."""
         log.info("Streaming token generation started")
         for tok in self._generate(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
                                   full_context=False, top_p=top_p, min_p=min_p, weight_quant=weight_quant,
                                   repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                                  frequency_penalty=frequency_penalty, logprobs=logprobs):
+                                  frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop):
             yield tok
         log.info("Streaming token generation completed")
 
@@ -485,7 +524,8 @@ class NeuralNetworkModel(nn.Module):
                       softmax_layer, burst: int, *, top_p: float | None = None, min_p: float | None = None,
                       weight_quant: str | None = None,
                       repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                      frequency_penalty: float | None = None, logprobs: int | None = None):
+                      frequency_penalty: float | None = None, logprobs: int | None = None,
+                      stop_run: stop_ops.StopRun | None = None):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
         (cache full) run eagerly, exactly as the per-token path. Logit penalties keep one state per
@@ -494,7 +534,13 @@ class NeuralNetworkModel(nn.Module):
         token sampled before it (eager steps: ``last``; graph steps: the decoder's ``idx``).
         With ``logprobs`` n every item is ``(new, (lp [rows, k], top_id, top_lp [rows, k, >= min(n, V)]))``
         (device; ``ops.logprobs.to_lists`` reads them): a burst's from the decoder's buffers, an eager
-        step's from ``ops.logprobs.token_logprobs``, in generation order."""
+        step's from ``ops.logprobs.token_logprobs``, in generation order.
+        With ``stop_run`` (stop sequences, ops/stopping.py) the call keeps one ``StopState`` — the
+        decoder's, where there is one — left in ``stop_run.state`` and begun here, once. Every token
+        passes through it where it is made: an eager step's through ``observe`` before it joins the
+        context, a graph step's in the step's last kernel; graph bursts are at most PENROZ_STOP_BURST
+        steps. The consumer reads ``stop_run.state.read(new)`` after each block and stops asking once
+        every row is done, so no further step, eager or graphed, runs past the finish."""
         from penroz.models import graph_decode
         rows = context.shape[0]
         n_lp = lp_ops.check_logprobs(logprobs)
@@ -504,6 +550,17 @@ class NeuralNetworkModel(nn.Module):
         if dec is not None:
             dec.set_penalties(pen)
             dec.set_logprobs(n_lp)
+            dec.set_stop(stop_run.seqs if stop_run is not None else None)
+        stop_state = None
+        if stop_run is not None:
+            if dec is not None:
+                stop_state = dec.stop
+            else:
+                stop_state = stop_ops.StopState(rows, context.device)
+                stop_state.set_stop(stop_run.seqs)
+            stop_state.begin()
+            stop_run.state = stop_state
+            burst = min(burst, _stop_burst())
         state = None
         if pen is not None:
             state = dec.penalties if dec is not None else pen_ops.PenaltyState()
@@ -527,7 +584,7 @@ class NeuralNetworkModel(nn.Module):
                 if dec is None or n == 0 or n >= block_size:
                     new = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache,
                                                     pos, top_p=top_p, min_p=min_p, penalty_state=state,
-                                                    penalty_new=last, logprobs=n_lp)
+                                                    penalty_new=last, logprobs=n_lp, stop_state=stop_state)
                     if n_lp is not None:
                         new, lps = new[0], tuple(t.unsqueeze(1) for t in new[1])  # one step: [rows, 1, ...]
                     for p in pos:
@@ -552,25 +609,43 @@ class NeuralNetworkModel(nn.Module):
     def _generate(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token, full_context, *,
                   top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None,
                   repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                  frequency_penalty: float | None = None, logprobs: int | None = None):
+                  frequency_penalty: float | None = None, logprobs: int | None = None, stop: list | None = None):
+        """Row 0's generation. ``stop`` (ops/stopping.py): every row is checked on the device, the call
+        ends once all have finished, row 0's tokens end with its own finish, and the full-context result
+        is ``(tokens, info)`` with ``finish_reason`` / ``stop_sequence`` in ``info``. A ``stop_token`` with
+        one row and no streaming takes the same device check as the sequence ``[stop_token]`` — long
+        bursts instead of one replay and one host read per token — and returns what it always did; with
+        more rows, or streaming, it keeps the per-token host check below."""
         pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                     frequency_penalty=frequency_penalty, logprobs=logprobs)
         context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k,
-                                                          top_p, min_p, weight_quant, **pens)
+                                                          top_p, min_p, weight_quant, stop=stop,
+                                                          stop_token=stop_token, **pens)
         rows = context.shape[0]
+        seqs, V = stop_ops.check_stop(stop), self._vocab_size()
+        routed = (seqs is None and stop_token is not None and rows == 1 and full_context and V is not None
+                  and isinstance(stop_token, int) and 0 <= stop_token < V)
+        run = stop_ops.StopRun([[stop_token]] if routed else seqs) if (routed or seqs is not None) else None
         generated = []
-        info = {"token_logprobs": [], "top_logprobs": []}  # row 0's, when asked for
+        info = {"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {}  # row 0's, when asked for
         done = torch.zeros(rows, dtype=torch.bool)
-        burst = 1 if (not full_context or stop_token is not None) else max_new_tokens
+        s_done, s_fin = [0] * rows, [0] * rows  # the device's finish state, as last read
+        burst = 1 if (not full_context or (stop_token is not None and not routed)) else max_new_tokens
         stopped = False
         with torch.inference_mode():
             for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, softmax_layer,
-                                          burst, top_p=top_p, min_p=min_p, weight_quant=weight_quant, **pens):
+                                          burst, top_p=top_p, min_p=min_p, weight_quant=weight_quant, stop_run=run,
+                                          **pens):
                 if logprobs is not None:  # copied back once per burst, with the tokens
                     new, lps = new
                     lp0, top0 = (r[0] for r in lp_ops.to_lists(*(t[:1] for t in lps), logprobs))
-                toks = new.tolist()
+                if run is not None:  # the rows' finish state comes back in the tokens' copy
+                    toks, s_done, s_fin = run.state.read(new)
+                else:
+                    toks = new.tolist()
                 for j in range(new.shape[1]):
+                    if run is not None and s_done[0] and len(generated) >= s_fin[0]:
+                        break  # row 0 finished: the rest of its block repeats the finishing token
                     col = [r[j] for r in toks]
                     context = torch.cat((context, new[:, j:j + 1].to(context.device)), dim=1)
                     generated.append(col[0])
@@ -579,26 +654,39 @@ class NeuralNetworkModel(nn.Module):
                         info["top_logprobs"].append(top0[j])
                     if not full_context:
                         yield col[0] if logprobs is None else (col[0], lp0[j], top0[j])
-                    if stop_token is not None:
+                    if stop_token is not None and not routed:
                         done |= torch.tensor([t == stop_token for t in col])
                         if bool(done[0]) and (rows == 1 or bool(done.all())):
                             stopped = True
                             break
-                if stopped:
+                if stopped or (run is not None and all(s_done)):
                     break
+        if run is not None and not routed:
+            info.update(stop_ops.finish_info(s_done[0], len(generated), s_fin[0])[1])
         if full_context:
-            yield context[0].tolist() if logprobs is None else (context[0].tolist(), info)
+            plain = logprobs is None and (run is None or routed)
+            yield context[0].tolist() if plain else (context[0].tolist(), info)
 
     def _generate_eager(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
                         full_context, *, top_p: float | None = None, min_p: float | None = None,
                         repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                        frequency_penalty: float | None = None, logprobs: int | None = None):
-        """Per-token path (kept for A/B and as the reference-shaped loop)."""
+                        frequency_penalty: float | None = None, logprobs: int | None = None,
+                        stop: list | None = None):
+        """Per-token path (kept for A/B and as the reference-shaped loop). ``stop``: every token passes
+        through one ``StopState`` and its finish state is read per token, as everything is here."""
         context, softmax_layer = self._prepare_generation(
             input_context, max_new_tokens, temperature, top_k, top_p, min_p,
             repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-            frequency_penalty=frequency_penalty, logprobs=logprobs)
-        info = {"token_logprobs": [], "top_logprobs": []}
+            frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop, stop_token=stop_token)
+        info = {"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {}
+        seqs = stop_ops.check_stop(stop)
+        stop_state = None
+        if seqs is not None:
+            stop_state = stop_ops.StopState(context.shape[0], context.device)
+            stop_state.set_stop(seqs)
+            stop_state.begin()
+        s_done, s_fin = [0] * context.shape[0], [0] * context.shape[0]
+        prompt_len = context.shape[1]
         pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         state = last = None
         if pen is not None:
@@ -614,14 +702,22 @@ class NeuralNetworkModel(nn.Module):
                 for _ in range(max_new_tokens):
                     nxt = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache, pos,
                                                     top_p=top_p, min_p=min_p, penalty_state=state, penalty_new=last,
-                                                    logprobs=logprobs)
+                                                    logprobs=logprobs, stop_state=stop_state)
                     if logprobs is not None:
                         nxt, lps = nxt
+                    context = torch.cat((context, nxt.to(context.device)), dim=1)
+                    last = context[:, -1:]
+                    if stop_state is not None:
+                        past = bool(s_done[0])  # row 0 finished before this token: only other rows still run
+                        s_done, s_fin = stop_state.read()
+                        if past:
+                            if all(s_done):
+                                break
+                            continue
+                    if logprobs is not None:
                         lp0, top0 = (r[0][0] for r in lp_ops.to_lists(*(t[:1].unsqueeze(1) for t in lps), logprobs))
                         info["token_logprobs"].append(lp0)
                         info["top_logprobs"].append(top0)
-                    context = torch.cat((context, nxt.to(context.device)), dim=1)
-                    last = context[:, -1:]
                     toks = nxt.view(-1).tolist()
                     generated.append(toks[0])
                     if not full_context:
@@ -630,12 +726,17 @@ class NeuralNetworkModel(nn.Module):
                         done |= torch.tensor([t == stop_token for t in toks])
                         if bool(done[0]) and (rows == 1 or bool(done.all())):
                             break
+                    if stop_state is not None and all(s_done):
+                        break
         finally:
             if cache is not None:
                 cache.log_metrics()
             self._detach_kv_cache(pos)
+        if stop_state is not None:
+            info.update(stop_ops.finish_info(s_done[0], len(generated), s_fin[0])[1])
         if full_context:
-            yield context[0].tolist() if logprobs is None else (context[0].tolist(), info)
+            tokens = context[0, :prompt_len + len(generated)].tolist()  # (rows that ran on leave frozen copies)
+            yield tokens if logprobs is None and stop_state is None else (tokens, info)
 
     @torch.inference_mode()
     def generate_batch(self, input_context: list, block_size: int, max_new_tokens: int, temperature=1.0,
@@ -643,18 +744,26 @@ class NeuralNetworkModel(nn.Module):
                        top_p: float | None = None, min_p: float | None = None,
                        weight_quant: str | None = None,
                        repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                       frequency_penalty: float | None = None, logprobs: int | None = None):
+                       frequency_penalty: float | None = None, logprobs: int | None = None,
+                       stop: list | None = None):
         """All rows' contexts (the reference returns row 0 only — bug 5). With ``logprobs`` n:
         ``(contexts, [info per row])``, each ``info`` (``generate_tokens``) as long as that row's
-        returned continuation."""
+        returned continuation. With ``stop`` (ops/stopping.py) every row finishes on its own: the
+        contexts are ragged, each cut behind the token that completed a stop sequence, the call ends
+        once all rows have finished, and the result is ``(contexts, [info per row])`` with
+        ``finish_reason`` / ``stop_sequence`` per row (and the log-probability lists, cut to match)."""
         pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                     frequency_penalty=frequency_penalty, logprobs=logprobs)
         context, sm = self._prepare_generation(input_context, max_new_tokens, temperature, top_k, top_p, min_p,
-                                               weight_quant, **pens)
-        infos = [{"token_logprobs": [], "top_logprobs": []} for _ in range(context.shape[0])]
+                                               weight_quant, stop=stop, stop_token=stop_token, **pens)
+        seqs = stop_ops.check_stop(stop)
+        run = stop_ops.StopRun(seqs) if seqs is not None else None
+        rows, prompt_len = context.shape
+        s_done, s_fin = [0] * rows, [0] * rows
+        infos = [{"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {} for _ in range(rows)]
         burst = 32 if stop_token is not None else max_new_tokens
         for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, sm, burst,
-                                      top_p=top_p, min_p=min_p, weight_quant=weight_quant, **pens):
+                                      top_p=top_p, min_p=min_p, weight_quant=weight_quant, stop_run=run, **pens):
             if logprobs is not None:
                 new, lps = new
             keep, stopped = new.shape[1], False
@@ -667,9 +776,22 @@ class NeuralNetworkModel(nn.Module):
                 for info, lp, top in zip(infos, *lp_ops.to_lists(*(t[:, :keep] for t in lps), logprobs)):
                     info["token_logprobs"] += lp
                     info["top_logprobs"] += top
+            if run is not None:  # one small read per burst; the tokens are read once, at the end
+                s_done, s_fin = run.state.read()
+                stopped = all(s_done)
             if stopped:
                 break
-        return context.tolist() if logprobs is None else (context.tolist(), infos)
+        if run is None:
+            return context.tolist() if logprobs is None else (context.tolist(), infos)
+        contexts = context.tolist()
+        for b, info in enumerate(infos):  # ragged: each row ends with its own finish
+            keep, fin = stop_ops.finish_info(s_done[b], context.shape[1] - prompt_len, s_fin[b])
+            contexts[b] = contexts[b][:prompt_len + keep]
+            for key in ("token_logprobs", "top_logprobs"):
+                if key in info:
+                    del info[key][keep:]
+            info.update(fin)
+        return contexts, infos
 
     # ------------------------------------------------------------------ training
     @classmethod

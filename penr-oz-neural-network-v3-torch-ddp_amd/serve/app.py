@@ -37,6 +37,7 @@ from pydantic import BaseModel, Field
 
 from penroz.models.mapper import Mapper
 from penroz.models.model import NeuralNetworkModel
+from penroz.ops import stopping as stop_ops
 from penroz.ops import weight_quant as wq_ops
 from penroz.parallel import launcher
 from penroz.utils.loaders import Downloader, Loader
@@ -150,6 +151,10 @@ class GenerateRequest(ModelRequest):
                                  description="Return each generated token's log-probability and this many most "
                                              "likely tokens with theirs (0: the chosen tokens' only); null: off")
     stop_token: int | None = Field(None, examples=[None], description="Token id that halts generation")
+    stop: list[list[int]] | None = Field(None, examples=[None],
+                                         description="Stop sequences: up to 16 lists of up to 8 token ids; generation "
+                                                     "ends with the first one completed by the generated tokens, "
+                                                     "which is kept; null or []: off")
     weight_quant: str | None = Field(None, examples=[None],
                                      description="Decode weight format: \"int8\" (weight-only int8 for batch 1-4 "
                                                  "decode steps), \"\" (bf16), null: PENROZ_DECODE_WEIGHTS")
@@ -451,11 +456,16 @@ def evaluate_model(body: EvaluateRequest = Body(...)):
 def model_generate(body: GenerateRequest = Body(...)):
     if body.weight_quant is not None:  # an unknown format is a 400 before the model is touched (streams too)
         wq_ops.resolve(body.weight_quant)
+    stop = stop_ops.check_stop(body.stop)  # (and a malformed stop set; ids beyond the vocabulary: once it is known)
+    if stop is not None and body.stop_token is not None:
+        raise ValueError("give stop_token or stop, not both (a stop_token s is the stop sequence [s])")
     model = load_for_serving(body.model_id)
     penalties = dict(repetition_penalty=body.repetition_penalty, presence_penalty=body.presence_penalty,
                      frequency_penalty=body.frequency_penalty)
     if body.logprobs is not None:  # (a keyword of its own only when asked for: without it the calls are as before)
         penalties["logprobs"] = body.logprobs
+    if stop is not None:  # (likewise)
+        penalties["stop"] = stop
     if body.stream:
         # the lock is held for the stream's whole lifetime (the KV cache stays attached between
         # chunks) and released by the background task even when the client goes away mid-stream
@@ -470,10 +480,15 @@ def model_generate(body: GenerateRequest = Body(...)):
         tokens = model.generate_tokens(body.input, body.block_size, body.max_new_tokens, body.temperature,
                                        body.top_k, body.stop_token, top_p=body.top_p, min_p=body.min_p,
                                        weight_quant=body.weight_quant, **penalties)
+    if body.logprobs is None and stop is None:
+        return {"tokens": tokens}
+    tokens, info = tokens
+    out = {"tokens": tokens}
+    if stop is not None:
+        out["finish_reason"], out["stop_sequence"] = info.pop("finish_reason"), info.pop("stop_sequence")
     if body.logprobs is not None:
-        tokens, info = tokens
-        return {"tokens": tokens, "logprobs": info}
-    return {"tokens": tokens}
+        out["logprobs"] = info
+    return out
 
 
 @app.post("/decode/")
