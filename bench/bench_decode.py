@@ -8,6 +8,7 @@ python bench/bench_decode.py [--model gpt2|gemma3-1b] [--batch 64] [--prompt 64]
                              [--ab-penalties ROUNDS]
                              [--logprobs N[,N...]] [--ab-logprobs ROUNDS]
                              [--stop IDS[/IDS...]] [--ab-stop ROUNDS]
+                             [--logit-bias N] [--allowed N] [--ab-bias ROUNDS]
 Prints one JSON line: generated tokens/s over all rows (BASELINE config 4: batch 64 /generate).
 --weights int8: the batch 1-4 decode steps read int8 weight copies (ops/weight_quant.py). --ab ROUNDS:
 both weight formats on one model in this one process, alternating, ROUNDS timed runs each; the line
@@ -27,6 +28,11 @@ ids, which random weights never complete, so every run generates all its tokens.
 process alternates between runs without and with the stop check (one decoder, two captured graphs, bursts of
 PENROZ_STOP_BURST steps in the second), ROUNDS timed runs each; the line holds both arms, their difference
 and how many rows finished early (0 is what the comparison needs).
+--logit-bias N: N random logit-bias entries (ops/logit_bias.py; ids drawn without replacement, biases in
+[-5, 5]); --allowed N: an allowed set of N random ids; both rewrite the logits in front of the sampler inside
+the decode step. --ab-bias ROUNDS: the same process alternates between runs without, with the entries
+(default 300) and with the allowed set (default 1000) — one decoder, its three captured graphs — ROUNDS timed
+runs each; the line holds every arm, its difference to the run without, and the bytes the mask form stores.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -65,7 +71,13 @@ ap.add_argument("--stop", default=None, metavar="IDS[/IDS...]",
                 help="stop sequences: comma-separated token ids, several divided by '/'")
 ap.add_argument("--ab-stop", type=int, default=0, metavar="ROUNDS",
                 help="alternate runs without and with the stop check, ROUNDS runs each")
+ap.add_argument("--logit-bias", type=int, default=0, metavar="N", help="N random logit-bias entries (1-1024)")
+ap.add_argument("--allowed", type=int, default=0, metavar="N", help="an allowed set of N random token ids")
+ap.add_argument("--ab-bias", type=int, default=0, metavar="ROUNDS",
+                help="alternate runs without, with the entries and with the allowed set, ROUNDS runs each")
 a = ap.parse_args()
+if a.ab_bias:
+    a.logit_bias, a.allowed = a.logit_bias or 300, a.allowed or 1000
 if a.ab_stop and not a.stop:
     a.stop = "1,2,3,4,5,6,7,8"
 stop_seqs = [[int(t) for t in seq.split(",")] for seq in a.stop.split("/")] if a.stop else None
@@ -90,17 +102,28 @@ ctx = torch.randint(0, V, (a.batch, a.prompt)).tolist()
 samp = dict(temperature=1.0, top_k=a.top_k or None, top_p=a.top_p, min_p=a.min_p)
 pens = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
             frequency_penalty=a.frequency_penalty)
+g_bias = torch.Generator().manual_seed(1)
+bias_entries = ({int(i): float(b) for i, b in zip(torch.randperm(V, generator=g_bias)[:a.logit_bias].tolist(),
+                                                  torch.empty(a.logit_bias).uniform_(-5, 5, generator=g_bias).tolist())}
+                if a.logit_bias else None)
+allowed_ids = torch.randperm(V, generator=g_bias)[:a.allowed].tolist() if a.allowed else None
 
 
 early = 0  # rows of the last timed() run that a stop sequence finished
 
 
-def timed(weights: str, new: int, penalised: bool = True, logprobs: int | None = None, stop=None) -> float:
+def timed(weights: str, new: int, penalised: bool = True, logprobs: int | None = None, stop=None,
+          logit_bias=None, allowed=None) -> float:
     """Seconds of one generate_batch of ``new`` tokens with this weight format ("" selects bf16
     whatever PENROZ_DECODE_WEIGHTS says), with the command line's penalties or without any, with
-    ``logprobs`` (None: without) and with the stop sequences ``stop`` (None: without)."""
+    ``logprobs`` (None: without), with the stop sequences ``stop`` (None: without) and with the logit-bias
+    entries ``logit_bias`` / the allowed ids ``allowed`` (None: without)."""
     global early
     kw = {} if stop is None else {"stop": stop}
+    if logit_bias is not None:
+        kw["logit_bias"] = logit_bias
+    if allowed is not None:
+        kw["allowed_token_ids"] = allowed
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     out = m.generate_batch(ctx, a.block, new, weight_quant="int8" if weights == "int8" else "", **samp,
@@ -215,11 +238,37 @@ if a.ab_stop:
                       "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
                       "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
     sys.exit(0)
+if a.ab_bias:
+    arms = {"off": {}, "entries": {"logit_bias": bias_entries}, "allowed": {"allowed": allowed_ids}}
+    times = {arm: [] for arm in arms}
+    for arm, kw in arms.items():
+        timed(a.weights, 4, **kw)  # warmup: the three graphs of the one decoder captured
+    for _ in range(a.ab_bias):
+        for arm, kw in arms.items():  # alternating: every arm sees the same drift of clocks and neighbours
+            times[arm].append(timed(a.weights, a.new, **kw) / a.new * 1e3)
+    res = {}
+    for arm, ms in times.items():
+        med = sorted(ms)[len(ms) // 2]
+        res[arm] = {"ms_per_step": [round(v, 4) for v in ms], "median": round(med, 4), "min": round(min(ms), 4)}
+    for v in res.values():
+        v["minus_off_us"] = round((v["median"] - res["off"]["median"]) * 1e3, 2)
+        v["minus_off_min_us"] = round((v["min"] - res["off"]["min"]) * 1e3, 2)
+    decs = list(m.__dict__.get("_graph_decoders", {}).values())
+    elem = 2 if a.dtype == "bf16" else 4
+    print(json.dumps({"metric": "decode ms/step, without vs with the logit-bias rewrite, alternating in one process",
+                      "arms": res, "entries": a.logit_bias, "allowed_ids": a.allowed,
+                      "mask_bytes_stored_per_step": a.batch * (V - a.allowed) * elem, **pens, "decoders": len(decs),
+                      "batch": a.batch, "prompt": a.prompt, "new_tokens": a.new, "block": a.block, "rounds": a.ab_bias,
+                      "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p, "weights": a.weights,
+                      "weights_in_effect": in_effect(), "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
+                      "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
+    sys.exit(0)
 lp_n = lp_ns[0] if lp_ns else None
-timed(a.weights, 4, logprobs=lp_n, stop=stop_seqs)  # warmup
-dt = timed(a.weights, a.new, logprobs=lp_n, stop=stop_seqs)
+bias_kw = dict(logit_bias=bias_entries, allowed=allowed_ids)
+timed(a.weights, 4, logprobs=lp_n, stop=stop_seqs, **bias_kw)  # warmup
+dt = timed(a.weights, a.new, logprobs=lp_n, stop=stop_seqs, **bias_kw)
 print(json.dumps({"metric": "decode tokens/sec (all rows)", "value": a.batch * a.new / dt, "batch": a.batch,
                   "prompt": a.prompt, "new_tokens": a.new, "block": a.block, "ms_per_step": dt / a.new * 1e3, "dtype": a.dtype,
                   "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p, **pens, "logprobs": lp_n,
-                  "stop": stop_seqs, "weights": a.weights, "weights_in_effect": in_effect(),
+                  "stop": stop_seqs, "logit_bias_entries": a.logit_bias, "allowed_ids": a.allowed, "weights": a.weights, "weights_in_effect": in_effect(),
                   "kv_cache": "int8-turboquant" if a.turbo else a.dtype, "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))

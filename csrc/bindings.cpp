@@ -140,6 +140,11 @@ void stop_observe(torch::Tensor seqs, torch::Tensor seq_len, torch::Tensor n_seq
 void stop_step(torch::Tensor seqs, torch::Tensor seq_len, torch::Tensor n_seqs, torch::Tensor tail,
                torch::Tensor n_gen, torch::Tensor done, torch::Tensor finish_at, torch::Tensor idx,
                torch::Tensor out_buf, torch::Tensor step);
+// logit_bias.hip
+void logit_bias_apply(torch::Tensor logits, torch::Tensor ids, torch::Tensor bias, torch::Tensor until,
+                      torch::Tensor n_entries, c10::optional<torch::Tensor> allow, bool allow_on, torch::Tensor base_t,
+                      c10::optional<torch::Tensor> step_t);
+std::tuple<int64_t, int64_t, int64_t> logit_bias_plan(int64_t B, int64_t V, bool allow_on);
 // adamw.hip
 torch::Tensor update_moments(std::vector<torch::Tensor> ws, std::vector<torch::Tensor> ps);
 // gemm_nt.hip
@@ -281,6 +286,14 @@ PYBIND11_MODULE(penroz_kernels, m) {
         pybind11::arg("n_uniq"), pybind11::arg("params"), pybind11::arg("new_tok") = pybind11::none(),
         "logit penalties, one sampling: count new_tok (int64 [B]), then repetition / presence / frequency "
         "(params fp32 [3]) on the listed tokens of logits [B, V], in place");
+  m.def("logit_bias_apply", &logit_bias_apply, pybind11::arg("logits"), pybind11::arg("ids"), pybind11::arg("bias"),
+        pybind11::arg("until"), pybind11::arg("n_entries"), pybind11::arg("allow"), pybind11::arg("allow_on"),
+        pybind11::arg("base_t"), pybind11::arg("step_t") = pybind11::none(),
+        "logit bias / banned / allowed tokens / min_tokens, one sampling: rewrites logits [B, V] in place from the "
+        "entries (ids, until int32 [1024], bias fp32 [1024], n_entries int32 [1]) and, with allow_on, the allowed "
+        "mask int32 [ceil(V / 32)]; t = *base_t + *step_t (int64 [1] on the device)");
+  m.def("logit_bias_plan", &logit_bias_plan, pybind11::arg("B"), pybind11::arg("V"), pybind11::arg("allow_on"),
+        "logit_bias_apply's launch plan: (workgroups per row, workgroups, mask words); all 0: refused (host only)");
   m.def("decode_attn", &decode_attn, pybind11::arg("q"), pybind11::arg("kc"), pybind11::arg("vc"), pybind11::arg("k_scale"),
         pybind11::arg("v_scale"), pybind11::arg("S"), pybind11::arg("q_offset"), pybind11::arg("scale"),
         pybind11::arg("seq_len_dev") = pybind11::none(), pybind11::arg("k_new") = pybind11::none(),

@@ -297,6 +297,36 @@ inline LogprobPlan plan_logprobs(int64_t V) {
   return {parts, (int64_t)parts * (2 + 2 * kLogprobMaxN)};
 }
 
+// ---- logit bias launch plan (logit_bias.hip) ----
+constexpr int kBiasThreads = 256, kBiasMaxEntries = 1024, kBiasSpan = 2048;  // workgroup, most entries, tokens per mask part
+struct LogitBiasPlan {
+  int per_row;         // workgroups per row: the entries' one, and the mask parts (0: refused)
+  int64_t grid;        // B x per_row (0: refused)
+  int64_t mask_words;  // 32-bit words of the allowed mask: ceil(V / 32)
+};
+
+// Entries alone: one workgroup per row. With the allowed mask: ceil(V / kBiasSpan) more per row, each
+// storing into its own span. Refused (all zero): B < 1, V outside [1, 2^31), or a grid of 2^31 or more.
+inline LogitBiasPlan plan_logit_bias(int64_t B, int64_t V, bool mask) {
+  if (B < 1 || V < 1 || V >= (int64_t(1) << 31)) return {0, 0, 0};
+  const int64_t per_row = 1 + (mask ? (V + kBiasSpan - 1) / kBiasSpan : 0);
+  if (B > ((int64_t(1) << 31) - 1) / per_row) return {0, 0, 0};
+  return {(int)per_row, B * per_row, (V + 31) / 32};
+}
+
+// The launch's index arithmetic, shared by the kernel and the host test (constexpr: host and device).
+// Workgroup wg serves row wg / per_row; its part wg % per_row is 0 for the entries, p >= 1 for the mask
+// span p - 1. Thread tid of a mask part covers, in round k, the token below: consecutive lanes take
+// consecutive tokens. Token v's bit is bit v % 32 of word v / 32.
+constexpr int kBiasMaskRounds = kBiasSpan / kBiasThreads;
+constexpr int64_t bias_row_of(int64_t wg, int per_row) { return wg / per_row; }
+constexpr int bias_part_of(int64_t wg, int per_row) { return (int)(wg % per_row); }
+constexpr int64_t bias_mask_token(int part, int tid, int k) {
+  return (int64_t)(part - 1) * kBiasSpan + (int64_t)k * kBiasThreads + tid;
+}
+constexpr int64_t bias_mask_word(int64_t v) { return v >> 5; }
+constexpr bool bias_allowed(unsigned word, int64_t v) { return (word >> (v & 31)) & 1u; }
+
 // ---- decode attention launch plan (decode_attn.hip) ----
 constexpr int kMaxMergeSplits = 16, kMergeMaxKeys = 8192;  // in-launch merge: most splits, longest context
 // What is built: decode_kernel<D, GC> with an exact group size GC only for head_dim 64 / 128 / 256 (GC 0: any

@@ -42,6 +42,11 @@ between steps lives on the device:
   their finishing token in the next step's input and the burst buffer. The stop set is read from the
   device; the step with the check is a further graph of the decoder (``GraphDecoder.set_stop``): up to
   eight, by (penalised, log-probabilities on, stop check on).
+* logit bias, banned and allowed tokens and ``min_tokens`` (``ops/logit_bias.py``,
+  ``csrc/kernels/logit_bias.hip``) rewrite the logits behind the penalties, in front of the sampler and
+  the log-probabilities, in one launch that reads its entries, its mask and ``t`` from the device. The
+  graph mode gains a fourth element (``GraphDecoder.set_logit_bias``): off, entries, or entries + mask —
+  the last two differ in their grid, so they are separate graphs.
 
 The host only tracks the cache length (one per replay) to switch to the reference's
 sliding-window re-prefill when the window is full, and copies each burst of tokens back once
@@ -65,6 +70,7 @@ from penroz.ops import activations as act_ops
 from penroz.ops import attention as attn_ops
 from penroz.ops import fused as fused_ops
 from penroz.ops import gemm as gemm_ops
+from penroz.ops import logit_bias as bias_ops
 from penroz.ops import logprobs as lp_ops
 from penroz.ops import norms as norm_ops
 from penroz.ops import penalties as pen_ops
@@ -738,7 +744,12 @@ class GraphDecoder:
         # stop sequences: the state (made when first asked for) and whether the step ends with the check
         self.stop: stop_ops.StopState | None = None
         self._stop_on = False
-        self._graphs: dict = {}  # (penalised, log-probabilities on, stop check on) -> the captured graphs ``graph`` is not
+        # logit bias / banned / allowed tokens / min_tokens: the state (made when first asked for) and the
+        # form of the step's rewrite: "off", "entries" or "mask" (entries and the allowed mask)
+        self.bias: bias_ops.BiasState | None = None
+        self._bias_form = "off"
+        # (penalised, log-probabilities on, stop check on, bias form) -> the captured graphs ``graph`` is not
+        self._graphs: dict = {}
 
     # ------------------------------------------------------------------ cache attachment
     def attach(self):
@@ -771,6 +782,9 @@ class GraphDecoder:
                 # counts idx, the token the previous step sampled, then rewrites the seen tokens'
                 # logits in the tensor the sampler reads
                 last = self.penalties.apply(last.contiguous(), self.idx if self._count_new else None)
+            if self._bias_form != "off":
+                # behind the penalties: t = base_t (the burst's start) + step_t, read on the device
+                last = self.bias.step(last.contiguous(), self.step_t)
             last = last.contiguous()  # the one tensor the sampler and the log-probabilities read
             if _ext.available() and last.is_cuda:
                 # one sampler kernel writes the token into the next step's input and the burst
@@ -855,13 +869,28 @@ class GraphDecoder:
             self.stop.set_stop(stop)
         self._select(self._penalised, self._lp_on, on)
 
-    def _select(self, penalised: bool, lp_on: bool, stop_on: bool):
-        """Make ``graph`` the captured step of this mode (None: captured on first use)."""
-        mode = (self._penalised, self._lp_on, self._stop_on)
-        if (penalised, lp_on, stop_on) != mode:
+    def set_logit_bias(self, canonical: bias_ops.Canonical | None):
+        """Once per generate call: ``ops.logit_bias.check_logit_bias``' result. None: ``run()`` replays the
+        step as it is without the rewrite, no kernel more; a canonical form: the step with the rewrite, which
+        reads the entries, the allowed mask and ``min_tokens`` from the device — other values, another set
+        and another ``min_tokens`` replay the same graph. With and without an allowed set are two graphs
+        (their grids differ), each captured on first use."""
+        if canonical is not None:
+            if self.bias is None:
+                self.bias = bias_ops.BiasState(self.device)
+            self.bias.set(canonical)
+        self._select(self._penalised, self._lp_on, self._stop_on,
+                     "off" if canonical is None else self.bias.form)
+
+    def _select(self, penalised: bool, lp_on: bool, stop_on: bool, bias_form: str | None = None):
+        """Make ``graph`` the captured step of this mode (None: captured on first use). ``bias_form``
+        None: as it is."""
+        bias_form = self._bias_form if bias_form is None else bias_form
+        mode = (self._penalised, self._lp_on, self._stop_on, self._bias_form)
+        if (penalised, lp_on, stop_on, bias_form) != mode:
             self._graphs[mode] = self.graph
-            self.graph = self._graphs.pop((penalised, lp_on, stop_on), None)
-            self._penalised, self._lp_on, self._stop_on = penalised, lp_on, stop_on
+            self.graph = self._graphs.pop((penalised, lp_on, stop_on, bias_form), None)
+            self._penalised, self._lp_on, self._stop_on, self._bias_form = penalised, lp_on, stop_on, bias_form
 
     def _burst_seed(self, start: int) -> int:
         v = (self.run_seed + self._HASH_STEP * int(start)) & (2 ** 64 - 1)
@@ -873,6 +902,8 @@ class GraphDecoder:
         self.cache.pos_t.fill_(cache_len)
         self.cache.len_t.fill_(cache_len + 1)
         self.step_t.zero_()
+        if self._bias_form != "off":
+            self.bias.base_t.fill_(int(start))  # the step's t = start + step_t
 
     def _capture(self, last_tok: Tensor, cache_len: int, start: int = 0):
         # warm-up run on a side stream (lazy allocations, kernel loading), then capture. The
@@ -909,7 +940,7 @@ class GraphDecoder:
         log.info(f"captured decode graph: rows={self.rows} block={self.capacity} "
                  f"temperature={self.temperature} top_k={self.top_k} top_p={self.top_p} min_p={self.min_p} "
                  f"penalties={'on' if self._penalised else 'off'} logprobs={'on' if self._lp_on else 'off'} "
-                 f"stop={'on' if self._stop_on else 'off'}")
+                 f"stop={'on' if self._stop_on else 'off'} logit_bias={self._bias_form}")
 
     @torch.inference_mode()
     def run(self, last_tok: Tensor, n_steps: int, start: int = 0) -> Tensor:

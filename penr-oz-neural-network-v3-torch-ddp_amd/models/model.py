@@ -43,6 +43,7 @@ import torch.distributed as dist
 from penroz.models.kv_cache import KVCache, create_kv_cache
 from penroz.models.layers import CausalSelfAttention, PositionEmbedding, SoftmaxOnLast
 from penroz.models.mapper import Mapper
+from penroz.ops import logit_bias as bias_ops
 from penroz.ops import logprobs as lp_ops
 from penroz.ops import penalties as pen_ops
 from penroz.ops import sampling as samp_ops
@@ -394,18 +395,37 @@ class NeuralNetworkModel(nn.Module):
                 return None
         return None
 
+    def _logit_bias(self, max_new_tokens: int, temperature: float, end_tokens, *, logit_bias=None,
+                    banned_token_ids=None, allowed_token_ids=None, min_tokens=None) -> bias_ops.Canonical | None:
+        """``ops.logit_bias.check_logit_bias`` against this model's vocabulary: the canonical form, None
+        when everything is neutral, ValueError for a malformed value."""
+        V = self._vocab_size()
+        bias = bias_ops.check_logit_bias(logit_bias, banned_token_ids, allowed_token_ids, min_tokens, end_tokens, V,
+                                         max_new_tokens, temperature)
+        if bias is not None and V is None:
+            raise ValueError("logit_bias / banned_token_ids / allowed_token_ids / min_tokens need a model whose "
+                             "layer list ends with the vocabulary projection")
+        return bias
+
     def _prepare_generation(self, input_context: list, max_new_tokens: int, temperature: float, top_k: int | None,
                             top_p: float | None = None, min_p: float | None = None,
                             weight_quant: str | None = None,
                             *, repetition_penalty: float | None = None, presence_penalty: float | None = None,
                             frequency_penalty: float | None = None, logprobs: int | None = None,
-                            stop: list | None = None, stop_token: int | None = None):
+                            stop: list | None = None, stop_token: int | None = None,
+                            logit_bias: dict | None = None, banned_token_ids: list | None = None,
+                            allowed_token_ids: list | None = None, min_tokens: int | None = None):
         samp_ops._check_filters(top_p, min_p)  # a bad range fails before any forward pass
         wq_ops.resolve(weight_quant)  # (and an unknown decode weight format)
         pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)  # (and a bad penalty)
         lp_ops.check_logprobs(logprobs)  # (and a bad number of log-probabilities)
-        if stop_ops.check_stop(stop, self._vocab_size()) is not None and stop_token is not None:  # (and a bad stop set)
+        seqs = stop_ops.check_stop(stop, self._vocab_size())
+        if seqs is not None and stop_token is not None:  # (and a bad stop set)
             raise ValueError("give stop_token or stop, not both (a stop_token s is the stop sequence [s])")
+        # (and a bad logit bias, banned or allowed set or min_tokens, ids checked against the vocabulary)
+        bias = self._logit_bias(max_new_tokens, temperature, bias_ops.end_tokens_of(stop_token, seqs),
+                                logit_bias=logit_bias, banned_token_ids=banned_token_ids,
+                                allowed_token_ids=allowed_token_ids, min_tokens=min_tokens)
         self.eval()
         device = next(self.parameters()).device
         context = torch.tensor(input_context, dtype=torch.long, device=device)
@@ -419,10 +439,14 @@ class NeuralNetworkModel(nn.Module):
             top_k_msg += "" if v is None else f" {name}_penalty {v}"
         top_k_msg += "" if logprobs is None else f" logprobs {logprobs}"
         top_k_msg += "" if not stop else f" stop {len(stop)} sequences"
+        if bias is not None:
+            top_k_msg += f" logit bias {len(bias.ids)} entries"
+            top_k_msg += "" if bias.allowed is None else f" {len(bias.allowed)} allowed ids"
+            top_k_msg += "" if not min_tokens else f" min_tokens {min_tokens}"
         log.info(f"Generating at most {max_new_tokens}{top_k_msg} tokens with {temperature} temperature "
                  f"using device {device}")
         softmax_layer = self.layers[-1] if self._is_softmax_last else SoftmaxOnLast(dim=-1)
-        return context, softmax_layer
+        return context, softmax_layer, bias  # (bias: ops.logit_bias' canonical form, None when it is off)
 
     @torch.inference_mode()
     def _generate_next_token(self, context: Tensor, block_size: int, temperature: float, top_k: int | None,
@@ -433,7 +457,10 @@ class NeuralNetworkModel(nn.Module):
                              frequency_penalty: float | None = None,
                              penalty_state: pen_ops.PenaltyState | None = None,
                              penalty_new: Tensor | None = None, logprobs: int | None = None,
-                             stop: list | None = None, stop_state: stop_ops.StopState | None = None):
+                             stop: list | None = None, stop_state: stop_ops.StopState | None = None,
+                             logit_bias: dict | None = None, banned_token_ids: list | None = None,
+                             allowed_token_ids: list | None = None, min_tokens: int | None = None,
+                             bias_state: bias_ops.BiasState | None = None, produced: int = 0):
         """``penalty_state``: the generate call's penalty bookkeeping (its values already set, its
         ``begin`` run on the call's prompt); ``penalty_new`` [rows, 1]: the tokens the previous step
         sampled, which this step counts (None on a call's first step). Penalty values without a state
@@ -441,7 +468,18 @@ class NeuralNetworkModel(nn.Module):
         token_logprobs`` of the logits the sampler was given) instead of the tokens alone.
         ``stop_state``: the generate call's stop bookkeeping (ops/stopping.py); the sampled tokens pass
         through its ``observe`` — rows that finished before get their finishing token — before they are
-        returned. ``stop`` without a state: this token is the call's first (the prompt takes no part)."""
+        returned. ``stop`` without a state: this token is the call's first (the prompt takes no part).
+        ``bias_state``: the generate call's logit bias / banned / allowed tokens / ``min_tokens``
+        (ops/logit_bias.py), applied behind the penalties with ``t = produced``, the tokens the call has
+        produced so far. The four values without a state: checked here, the one-token sequences of
+        ``stop`` being the end tokens."""
+        if bias_state is None:
+            bias = self._logit_bias(2 ** 31 - 1, temperature, bias_ops.end_tokens_of(None, stop_ops.check_stop(stop)),
+                                    logit_bias=logit_bias, banned_token_ids=banned_token_ids,
+                                    allowed_token_ids=allowed_token_ids, min_tokens=min_tokens)
+            if bias is not None:
+                bias_state = bias_ops.BiasState(context.device)
+                bias_state.set(bias)
         if stop_state is None and stop_ops.check_stop(stop, self._vocab_size()) is not None:
             stop_state = stop_ops.StopState(context.shape[0], context.device)
             stop_state.set_stop(stop_ops.check_stop(stop))
@@ -470,6 +508,8 @@ class NeuralNetworkModel(nn.Module):
         last = logits[:, -1, :] if logits.ndim == 3 else logits
         if penalty_state is not None:  # between the lm_head and the sampler, as in the captured step
             last = penalty_state.apply(last.contiguous(), penalty_new)
+        if bias_state is not None:  # behind the penalties, as in the captured step
+            last = bias_state.apply(last.contiguous(), produced)
         nxt = samp_ops.sample(last, temperature, top_k, top_p=top_p, min_p=min_p)
         n = lp_ops.check_logprobs(logprobs)
         lps = None if n is None else lp_ops.token_logprobs(last, nxt, n)  # (of the token as sampled)
@@ -484,7 +524,9 @@ class NeuralNetworkModel(nn.Module):
                         weight_quant: str | None = None,
                         repetition_penalty: float | None = None, presence_penalty: float | None = None,
                         frequency_penalty: float | None = None, logprobs: int | None = None,
-                        stop: list | None = None):
+                        stop: list | None = None, logit_bias: dict | None = None,
+                        banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
+                        min_tokens: int | None = None):
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
         "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
@@ -495,12 +537,20 @@ class NeuralNetworkModel(nn.Module):
         ``stop``: up to 16 sequences of up to 8 token ids (ops/stopping.py), checked on the device against
         the generated tokens; generation ends with the first sequence completed, which is kept. Returns
         ``(tokens, info)`` with ``info["finish_reason"]`` "stop" or "length" and ``info["stop_sequence"]``
-        the index into ``stop`` or None (beside the log-probability entries, when both are asked for)."""
+        the index into ``stop`` or None (beside the log-probability entries, when both are asked for).
+        ``logit_bias`` {id: bias in [-100, 100]}, ``banned_token_ids``, ``allowed_token_ids`` and
+        ``min_tokens`` (ops/logit_bias.py) constrain which tokens may come out, for every row alike: the
+        logits are rewritten behind the penalties, in front of temperature and the filters; a banned or
+        not allowed token — and, for the first ``min_tokens`` tokens, ``stop_token`` and the one-token
+        sequences of ``stop`` — gets the finite floor -2^100 (fp16: -2^15) and is never drawn. None, {},
+        [] and 0 are off (``allowed_token_ids=[]`` is an error); the result's shape does not change."""
         return [t for t in self._generate(input_context, block_size, max_new_tokens, temperature, top_k,
                                           stop_token, full_context=True, top_p=top_p, min_p=min_p,
                                           weight_quant=weight_quant, repetition_penalty=repetition_penalty,
                                           presence_penalty=presence_penalty,
-                                          frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop)][-1]
+                                          frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop,
+                                          logit_bias=logit_bias, banned_token_ids=banned_token_ids,
+                                          allowed_token_ids=allowed_token_ids, min_tokens=min_tokens)][-1]
 
     @torch.inference_mode()
     def generate_tokens_stream(self, input_context: list, block_size: int, max_new_tokens: int,
@@ -509,14 +559,19 @@ class NeuralNetworkModel(nn.Module):
                                weight_quant: str | None = None,
                                repetition_penalty: float | None = None, presence_penalty: float | None = None,
                                frequency_penalty: float | None = None, logprobs: int | None = None,
-                               stop: list | None = None):
+                               stop: list | None = None, logit_bias: dict | None = None,
+                               banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
+                               min_tokens: int | None = None):
         """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``. With
-        ``stop`` the stream ends with the token that completes a stop sequence."""
+        ``stop`` the stream ends with the token that completes a stop sequence. ``logit_bias`` /
+        ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in ``generate_tokens``."""
         log.info("Streaming token generation started")
         for tok in self._generate(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
                                   full_context=False, top_p=top_p, min_p=min_p, weight_quant=weight_quant,
                                   repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                                  frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop):
+                                  frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop,
+                                  logit_bias=logit_bias, banned_token_ids=banned_token_ids,
+                                  allowed_token_ids=allowed_token_ids, min_tokens=min_tokens):
             yield tok
         log.info("Streaming token generation completed")
 
@@ -525,7 +580,7 @@ class NeuralNetworkModel(nn.Module):
                       weight_quant: str | None = None,
                       repetition_penalty: float | None = None, presence_penalty: float | None = None,
                       frequency_penalty: float | None = None, logprobs: int | None = None,
-                      stop_run: stop_ops.StopRun | None = None):
+                      stop_run: stop_ops.StopRun | None = None, bias: bias_ops.Canonical | None = None):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
         (cache full) run eagerly, exactly as the per-token path. Logit penalties keep one state per
@@ -540,7 +595,11 @@ class NeuralNetworkModel(nn.Module):
         passes through it where it is made: an eager step's through ``observe`` before it joins the
         context, a graph step's in the step's last kernel; graph bursts are at most PENROZ_STOP_BURST
         steps. The consumer reads ``stop_run.state.read(new)`` after each block and stops asking once
-        every row is done, so no further step, eager or graphed, runs past the finish."""
+        every row is done, so no further step, eager or graphed, runs past the finish.
+        ``bias``: the call's logit bias / banned / allowed tokens / ``min_tokens`` in canonical form
+        (``_prepare_generation``'s, ops/logit_bias.py). The call keeps one ``BiasState`` — the decoder's,
+        where there is one: an eager step applies it with ``t`` = the tokens produced so far, a graph step
+        reads the burst's start from the device and adds its own counter."""
         from penroz.models import graph_decode
         rows = context.shape[0]
         n_lp = lp_ops.check_logprobs(logprobs)
@@ -551,6 +610,12 @@ class NeuralNetworkModel(nn.Module):
             dec.set_penalties(pen)
             dec.set_logprobs(n_lp)
             dec.set_stop(stop_run.seqs if stop_run is not None else None)
+            dec.set_logit_bias(bias)
+        bias_state = None
+        if bias is not None:
+            bias_state = dec.bias if dec is not None else bias_ops.BiasState(context.device)
+            if dec is None:
+                bias_state.set(bias)
         stop_state = None
         if stop_run is not None:
             if dec is not None:
@@ -584,7 +649,8 @@ class NeuralNetworkModel(nn.Module):
                 if dec is None or n == 0 or n >= block_size:
                     new = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache,
                                                     pos, top_p=top_p, min_p=min_p, penalty_state=state,
-                                                    penalty_new=last, logprobs=n_lp, stop_state=stop_state)
+                                                    penalty_new=last, logprobs=n_lp, stop_state=stop_state,
+                                                    bias_state=bias_state, produced=produced)
                     if n_lp is not None:
                         new, lps = new[0], tuple(t.unsqueeze(1) for t in new[1])  # one step: [rows, 1, ...]
                     for p in pos:
@@ -609,18 +675,22 @@ class NeuralNetworkModel(nn.Module):
     def _generate(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token, full_context, *,
                   top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None,
                   repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                  frequency_penalty: float | None = None, logprobs: int | None = None, stop: list | None = None):
+                  frequency_penalty: float | None = None, logprobs: int | None = None, stop: list | None = None,
+                  logit_bias: dict | None = None, banned_token_ids: list | None = None,
+                  allowed_token_ids: list | None = None, min_tokens: int | None = None):
         """Row 0's generation. ``stop`` (ops/stopping.py): every row is checked on the device, the call
         ends once all have finished, row 0's tokens end with its own finish, and the full-context result
         is ``(tokens, info)`` with ``finish_reason`` / ``stop_sequence`` in ``info``. A ``stop_token`` with
         one row and no streaming takes the same device check as the sequence ``[stop_token]`` — long
         bursts instead of one replay and one host read per token — and returns what it always did; with
-        more rows, or streaming, it keeps the per-token host check below."""
+        more rows, or streaming, it keeps the per-token host check below. Either way ``stop_token`` and the
+        one-token sequences of ``stop`` are the end tokens that ``min_tokens`` suppresses (ops/logit_bias.py)."""
         pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                     frequency_penalty=frequency_penalty, logprobs=logprobs)
-        context, softmax_layer = self._prepare_generation(input_context, max_new_tokens, temperature, top_k,
-                                                          top_p, min_p, weight_quant, stop=stop,
-                                                          stop_token=stop_token, **pens)
+        context, softmax_layer, bias = self._prepare_generation(
+            input_context, max_new_tokens, temperature, top_k, top_p, min_p, weight_quant, stop=stop,
+            stop_token=stop_token, logit_bias=logit_bias, banned_token_ids=banned_token_ids,
+            allowed_token_ids=allowed_token_ids, min_tokens=min_tokens, **pens)
         rows = context.shape[0]
         seqs, V = stop_ops.check_stop(stop), self._vocab_size()
         routed = (seqs is None and stop_token is not None and rows == 1 and full_context and V is not None
@@ -635,7 +705,7 @@ class NeuralNetworkModel(nn.Module):
         with torch.inference_mode():
             for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, softmax_layer,
                                           burst, top_p=top_p, min_p=min_p, weight_quant=weight_quant, stop_run=run,
-                                          **pens):
+                                          bias=bias, **pens):
                 if logprobs is not None:  # copied back once per burst, with the tokens
                     new, lps = new
                     lp0, top0 = (r[0] for r in lp_ops.to_lists(*(t[:1] for t in lps), logprobs))
@@ -671,15 +741,24 @@ class NeuralNetworkModel(nn.Module):
                         full_context, *, top_p: float | None = None, min_p: float | None = None,
                         repetition_penalty: float | None = None, presence_penalty: float | None = None,
                         frequency_penalty: float | None = None, logprobs: int | None = None,
-                        stop: list | None = None):
+                        stop: list | None = None, logit_bias: dict | None = None,
+                        banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
+                        min_tokens: int | None = None):
         """Per-token path (kept for A/B and as the reference-shaped loop). ``stop``: every token passes
-        through one ``StopState`` and its finish state is read per token, as everything is here."""
-        context, softmax_layer = self._prepare_generation(
+        through one ``StopState`` and its finish state is read per token, as everything is here. The
+        logit bias / banned / allowed tokens / ``min_tokens`` keep one ``BiasState``, applied per token."""
+        context, softmax_layer, bias = self._prepare_generation(
             input_context, max_new_tokens, temperature, top_k, top_p, min_p,
             repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-            frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop, stop_token=stop_token)
+            frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop, stop_token=stop_token,
+            logit_bias=logit_bias, banned_token_ids=banned_token_ids, allowed_token_ids=allowed_token_ids,
+            min_tokens=min_tokens)
         info = {"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {}
         seqs = stop_ops.check_stop(stop)
+        bias_state = None
+        if bias is not None:
+            bias_state = bias_ops.BiasState(context.device)
+            bias_state.set(bias)
         stop_state = None
         if seqs is not None:
             stop_state = stop_ops.StopState(context.shape[0], context.device)
@@ -699,10 +778,11 @@ class NeuralNetworkModel(nn.Module):
         done = torch.zeros(rows, dtype=torch.bool)
         try:
             with torch.inference_mode():
-                for _ in range(max_new_tokens):
+                for produced in range(max_new_tokens):
                     nxt = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache, pos,
                                                     top_p=top_p, min_p=min_p, penalty_state=state, penalty_new=last,
-                                                    logprobs=logprobs, stop_state=stop_state)
+                                                    logprobs=logprobs, stop_state=stop_state, bias_state=bias_state,
+                                                    produced=produced)
                     if logprobs is not None:
                         nxt, lps = nxt
                     context = torch.cat((context, nxt.to(context.device)), dim=1)
@@ -745,17 +825,23 @@ class NeuralNetworkModel(nn.Module):
                        weight_quant: str | None = None,
                        repetition_penalty: float | None = None, presence_penalty: float | None = None,
                        frequency_penalty: float | None = None, logprobs: int | None = None,
-                       stop: list | None = None):
+                       stop: list | None = None, logit_bias: dict | None = None,
+                       banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
+                       min_tokens: int | None = None):
         """All rows' contexts (the reference returns row 0 only — bug 5). With ``logprobs`` n:
         ``(contexts, [info per row])``, each ``info`` (``generate_tokens``) as long as that row's
         returned continuation. With ``stop`` (ops/stopping.py) every row finishes on its own: the
         contexts are ragged, each cut behind the token that completed a stop sequence, the call ends
         once all rows have finished, and the result is ``(contexts, [info per row])`` with
-        ``finish_reason`` / ``stop_sequence`` per row (and the log-probability lists, cut to match)."""
+        ``finish_reason`` / ``stop_sequence`` per row (and the log-probability lists, cut to match).
+        ``logit_bias`` / ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in
+        ``generate_tokens``, the same values for every row."""
         pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                     frequency_penalty=frequency_penalty, logprobs=logprobs)
-        context, sm = self._prepare_generation(input_context, max_new_tokens, temperature, top_k, top_p, min_p,
-                                               weight_quant, stop=stop, stop_token=stop_token, **pens)
+        context, sm, bias = self._prepare_generation(
+            input_context, max_new_tokens, temperature, top_k, top_p, min_p, weight_quant, stop=stop,
+            stop_token=stop_token, logit_bias=logit_bias, banned_token_ids=banned_token_ids,
+            allowed_token_ids=allowed_token_ids, min_tokens=min_tokens, **pens)
         seqs = stop_ops.check_stop(stop)
         run = stop_ops.StopRun(seqs) if seqs is not None else None
         rows, prompt_len = context.shape
@@ -763,7 +849,8 @@ class NeuralNetworkModel(nn.Module):
         infos = [{"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {} for _ in range(rows)]
         burst = 32 if stop_token is not None else max_new_tokens
         for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, sm, burst,
-                                      top_p=top_p, min_p=min_p, weight_quant=weight_quant, stop_run=run, **pens):
+                                      top_p=top_p, min_p=min_p, weight_quant=weight_quant, stop_run=run, bias=bias,
+                                      **pens):
             if logprobs is not None:
                 new, lps = new
             keep, stopped = new.shape[1], False

@@ -33,10 +33,11 @@ from fastapi.exceptions import RequestValidationError
 from fastapi.params import Query
 from fastapi.responses import HTMLResponse, JSONResponse, RedirectResponse, Response, StreamingResponse
 from fastapi.staticfiles import StaticFiles
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, StrictInt
 
 from penroz.models.mapper import Mapper
 from penroz.models.model import NeuralNetworkModel
+from penroz.ops import logit_bias as bias_ops
 from penroz.ops import stopping as stop_ops
 from penroz.ops import weight_quant as wq_ops
 from penroz.parallel import launcher
@@ -155,6 +156,18 @@ class GenerateRequest(ModelRequest):
                                          description="Stop sequences: up to 16 lists of up to 8 token ids; generation "
                                                      "ends with the first one completed by the generated tokens, "
                                                      "which is kept; null or []: off")
+    logit_bias: dict | None = Field(None, examples=[None],
+                                                description="Added to the logits of these token ids before "
+                                                            "sampling: {\"id\": bias}, each bias in [-100, 100], "
+                                                            "at most 1024 ids; null or {}: off")
+    banned_token_ids: list | None = Field(None, examples=[None],
+                                               description="Token ids that are never generated; null or []: off")
+    allowed_token_ids: list | None = Field(None, examples=[None],
+                                                description="Generate only these token ids (at least one); "
+                                                            "null: no restriction")
+    min_tokens: StrictInt | None = Field(None, examples=[None],
+                                   description="Generate at least this many tokens before stop_token or a one-token "
+                                               "stop sequence may come out; at most max_new_tokens; null or 0: off")
     weight_quant: str | None = Field(None, examples=[None],
                                      description="Decode weight format: \"int8\" (weight-only int8 for batch 1-4 "
                                                  "decode steps), \"\" (bf16), null: PENROZ_DECODE_WEIGHTS")
@@ -459,9 +472,16 @@ def model_generate(body: GenerateRequest = Body(...)):
     stop = stop_ops.check_stop(body.stop)  # (and a malformed stop set; ids beyond the vocabulary: once it is known)
     if stop is not None and body.stop_token is not None:
         raise ValueError("give stop_token or stop, not both (a stop_token s is the stop sequence [s])")
+    # (and a malformed logit bias, banned or allowed set or min_tokens; ids beyond the vocabulary: once it is known)
+    bias_ops.check_logit_bias(body.logit_bias, body.banned_token_ids, body.allowed_token_ids, body.min_tokens,
+                              bias_ops.end_tokens_of(body.stop_token, stop), None, body.max_new_tokens,
+                              body.temperature)
     model = load_for_serving(body.model_id)
     penalties = dict(repetition_penalty=body.repetition_penalty, presence_penalty=body.presence_penalty,
                      frequency_penalty=body.frequency_penalty)
+    for name in ("logit_bias", "banned_token_ids", "allowed_token_ids", "min_tokens"):
+        if getattr(body, name):  # (a keyword of its own only when the request sets it; {}, [] and 0 are off)
+            penalties[name] = getattr(body, name)
     if body.logprobs is not None:  # (a keyword of its own only when asked for: without it the calls are as before)
         penalties["logprobs"] = body.logprobs
     if stop is not None:  # (likewise)
