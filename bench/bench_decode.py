@@ -9,6 +9,7 @@ python bench/bench_decode.py [--model gpt2|gemma3-1b] [--batch 64] [--prompt 64]
                              [--logprobs N[,N...]] [--ab-logprobs ROUNDS]
                              [--stop IDS[/IDS...]] [--ab-stop ROUNDS]
                              [--logit-bias N] [--allowed N] [--ab-bias ROUNDS]
+                             [--ragged ROUNDS]
 Prints one JSON line: generated tokens/s over all rows (BASELINE config 4: batch 64 /generate).
 --weights int8: the batch 1-4 decode steps read int8 weight copies (ops/weight_quant.py). --ab ROUNDS:
 both weight formats on one model in this one process, alternating, ROUNDS timed runs each; the line
@@ -33,6 +34,10 @@ and how many rows finished early (0 is what the comparison needs).
 the decode step. --ab-bias ROUNDS: the same process alternates between runs without, with the entries
 (default 300) and with the allowed set (default 1000) — one decoder, its three captured graphs — ROUNDS timed
 runs each; the line holds every arm, its difference to the run without, and the bytes the mask form stores.
+--ragged ROUNDS: the same process alternates between the uniform batch (every prompt --prompt long) and a ragged
+one (ops/ragged.py) of the same rows whose prompt lengths are spread evenly over [prompt / 4, prompt] — the same
+longest row, so the same padded prefill and capacity — ROUNDS timed runs each; the line holds both arms, their
+difference, and whether a ragged decoder's captured graph served the ragged arm. --block >= prompt + new.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -75,6 +80,8 @@ ap.add_argument("--logit-bias", type=int, default=0, metavar="N", help="N random
 ap.add_argument("--allowed", type=int, default=0, metavar="N", help="an allowed set of N random token ids")
 ap.add_argument("--ab-bias", type=int, default=0, metavar="ROUNDS",
                 help="alternate runs without, with the entries and with the allowed set, ROUNDS runs each")
+ap.add_argument("--ragged", type=int, default=0, metavar="ROUNDS",
+                help="alternate a uniform and a ragged batch (prompt lengths spread over [prompt / 4, prompt]), ROUNDS runs each")
 a = ap.parse_args()
 if a.ab_bias:
     a.logit_bias, a.allowed = a.logit_bias or 300, a.allowed or 1000
@@ -113,11 +120,12 @@ early = 0  # rows of the last timed() run that a stop sequence finished
 
 
 def timed(weights: str, new: int, penalised: bool = True, logprobs: int | None = None, stop=None,
-          logit_bias=None, allowed=None) -> float:
+          logit_bias=None, allowed=None, context=None) -> float:
     """Seconds of one generate_batch of ``new`` tokens with this weight format ("" selects bf16
     whatever PENROZ_DECODE_WEIGHTS says), with the command line's penalties or without any, with
     ``logprobs`` (None: without), with the stop sequences ``stop`` (None: without) and with the logit-bias
-    entries ``logit_bias`` / the allowed ids ``allowed`` (None: without)."""
+    entries ``logit_bias`` / the allowed ids ``allowed`` (None: without). ``context``: the prompts (None: the
+    uniform batch)."""
     global early
     kw = {} if stop is None else {"stop": stop}
     if logit_bias is not None:
@@ -126,7 +134,7 @@ def timed(weights: str, new: int, penalised: bool = True, logprobs: int | None =
         kw["allowed_token_ids"] = allowed
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = m.generate_batch(ctx, a.block, new, weight_quant="int8" if weights == "int8" else "", **samp,
+    out = m.generate_batch(ctx if context is None else context, a.block, new, weight_quant="int8" if weights == "int8" else "", **samp,
                            **(pens if penalised else {}), logprobs=logprobs, **kw)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -259,6 +267,33 @@ if a.ab_bias:
                       "arms": res, "entries": a.logit_bias, "allowed_ids": a.allowed,
                       "mask_bytes_stored_per_step": a.batch * (V - a.allowed) * elem, **pens, "decoders": len(decs),
                       "batch": a.batch, "prompt": a.prompt, "new_tokens": a.new, "block": a.block, "rounds": a.ab_bias,
+                      "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p, "weights": a.weights,
+                      "weights_in_effect": in_effect(), "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
+                      "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
+    sys.exit(0)
+if a.ragged:
+    assert a.block >= a.prompt + a.new, "--ragged: a ragged call never slides its window (--block >= prompt + new)"
+    lo = max(1, a.prompt // 4)
+    lens = [lo + round((a.prompt - lo) * b / max(1, a.batch - 1)) for b in range(a.batch)]
+    arms = {"uniform": ctx, "ragged": [row[:n] for row, n in zip(ctx, lens)]}
+    times = {arm: [] for arm in arms}
+    for arm, rows in arms.items():
+        timed(a.weights, 4, context=rows)  # warmup: each arm's decoder and graph captured
+    for _ in range(a.ragged):
+        for arm, rows in arms.items():  # alternating: both arms see the same drift of clocks and neighbours
+            times[arm].append(timed(a.weights, a.new, context=rows) / a.new * 1e3)
+    res = {}
+    for arm, ms in times.items():
+        med = sorted(ms)[len(ms) // 2]
+        res[arm] = {"ms_per_step": [round(v, 4) for v in ms], "median": round(med, 4), "min": round(min(ms), 4)}
+    decs = list(m.__dict__.get("_graph_decoders", {}).values())
+    print(json.dumps({"metric": "decode ms/step (prefill included), uniform vs ragged batch, alternating in one process",
+                      "arms": res, "ragged_minus_uniform_us": round((res["ragged"]["median"] - res["uniform"]["median"]) * 1e3, 2),
+                      "ragged_minus_uniform_min_us": round((res["ragged"]["min"] - res["uniform"]["min"]) * 1e3, 2),
+                      "ragged_over_uniform_median": round(res["ragged"]["median"] / res["uniform"]["median"], 4),
+                      "prompt_lengths": [min(lens), max(lens)],
+                      "ragged_graph": any(getattr(d, "ragged", False) and d.graph is not None for d in decs), **pens,
+                      "batch": a.batch, "prompt": a.prompt, "new_tokens": a.new, "block": a.block, "rounds": a.ragged,
                       "top_k": a.top_k or None, "top_p": a.top_p, "min_p": a.min_p, "weights": a.weights,
                       "weights_in_effect": in_effect(), "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
                       "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))

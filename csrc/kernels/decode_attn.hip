@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(256) decode_kernel(const TQ* __restrict__ q, c
                                                      float* __restrict__ ws_o, float* __restrict__ ws_ml, int B,
                                                      int Tq, int H, int Hkv, int cap, int S, int q_offset,
                                                      int splits, float scale, const int64_t* __restrict__ S_dev,
-                                                     int64_t q_rs, const TQ* __restrict__ k_new,
+                                                     int S_rs, int64_t q_rs, const TQ* __restrict__ k_new,
                                                      const TQ* __restrict__ v_new, int64_t kv_rs,
                                                      int* __restrict__ cnt, int min_keys) {
   constexpr int GMAX = GC ? GC : kMaxGroup;
@@ -138,7 +138,9 @@ __global__ void __launch_bounds__(256) decode_kernel(const TQ* __restrict__ q, c
     qv[r] = i < G * D ? to_f(q[((size_t)b * Tq + tq) * q_rs + (size_t)(g * G + i / D) * D + i % D]) : 0.f;
   }
   if (S_dev != nullptr) {  // graph-replayed decode: the cache length lives on the device
-    S = (int)min<int64_t>(*S_dev, (int64_t)cap);
+    // (S_rs 0: one length for the launch; 1: row b's own — everything below derives from S, so the
+    // key range, the split count, the merge and the append slot are per row; one load either way)
+    S = (int)min<int64_t>(S_dev[b * S_rs], (int64_t)cap);
     q_offset = S - Tq;
   }
   const int kend_causal = min(S, q_offset + tq + 1);
@@ -422,8 +424,8 @@ template <int D, int GMAX, bool ROPE = false>  // GMAX: the exact query-group si
 __global__ void __launch_bounds__(256) decode_small_kernel(const bf16* __restrict__ q, bf16* __restrict__ kc,
                                                            bf16* __restrict__ vc, bf16* __restrict__ out, int H,
                                                            int Hkv, int cap, int S, float scale,
-                                                           const int64_t* __restrict__ S_dev, int64_t q_rs,
-                                                           const bf16* __restrict__ k_new,
+                                                           const int64_t* __restrict__ S_dev, int S_rs,
+                                                           int64_t q_rs, const bf16* __restrict__ k_new,
                                                            const bf16* __restrict__ v_new, int64_t kv_rs,
                                                            const float* __restrict__ rc,
                                                            const float* __restrict__ rs) {
@@ -440,7 +442,7 @@ __global__ void __launch_bounds__(256) decode_small_kernel(const bf16* __restric
   __shared__ float wm[4][GMAX], wl[4][GMAX];
   __shared__ float wo[4][GMAX][D];
 
-  if (S_dev != nullptr) S = (int)min<int64_t>(*S_dev, (int64_t)cap);
+  if (S_dev != nullptr) S = (int)min<int64_t>(S_dev[b * S_rs], (int64_t)cap);  // S_rs 1: row b's own length
   const size_t head_base = ((size_t)b * Hkv + g) * cap;
   const size_t new_off = (size_t)b * kv_rs + (size_t)g * D;
   const float c = scale * 1.4426950408889634f;
@@ -647,7 +649,8 @@ __global__ void __launch_bounds__(256) decode_combine_kernel(const float* __rest
 }
 
 // Append one token's K and V rows (read straight from the fused QKV projection) into the cache
-// slot `pos` — taken from device memory when pos_dev is given (graph-replayed decode). One wave
+// slot `pos` — taken from device memory when pos_dev is given (graph-replayed decode; [1], or [B]
+// with pos_rs = 1 for a ragged step: each row its own slot). One wave
 // per (batch, KV head, K|V) row; int8 caches quantise per token (absmax / 127, round to nearest
 // even) exactly like kv_quant_kernel.
 template <typename T, typename TK>
@@ -655,14 +658,15 @@ __global__ void __launch_bounds__(256) kv_append_kernel(const T* __restrict__ k,
                                                         int64_t k_rs, int64_t v_rs, TK* __restrict__ kc,
                                                         TK* __restrict__ vc, float* __restrict__ ks,
                                                         float* __restrict__ vs, int B, int Hkv, int D, int cap,
-                                                        const int64_t* __restrict__ pos_dev, int pos_host) {
+                                                        const int64_t* __restrict__ pos_dev, int pos_rs,
+                                                        int pos_host) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);  // over B*Hkv*2
   if (row >= B * Hkv * 2) return;
   const int which = row & 1, bg = row >> 1;
   const int g = bg % Hkv, b = bg / Hkv;
   const T* src = (which ? v + (size_t)b * v_rs : k + (size_t)b * k_rs) + (size_t)g * D;
-  const int pos = pos_dev ? (int)*pos_dev : pos_host;
+  const int pos = pos_dev ? (int)pos_dev[b * pos_rs] : pos_host;  // pos_rs 1: row b's own slot
   const size_t slot = ((size_t)b * Hkv + g) * cap + pos;
   TK* dst = (which ? vc : kc) + slot * D;
   if constexpr (std::is_same<TK, int8_t>::value) {
@@ -710,7 +714,10 @@ std::tuple<bool, int64_t, int64_t, bool> decode_attn_plan(int64_t B, int64_t Tq,
 
 // seq_len_dev (optional int64 [1] on the device): the cache length is read by the kernel at run
 // time (S / q_offset are then only upper bounds used to size the launch) — lets a captured HIP
-// graph replay the same decode step at every position.
+// graph replay the same decode step at every position. int64 [B] (Tq == 1): every batch row its own
+// length (a ragged step) — rows of one launch may then take different split counts; a row's unused
+// splits leave at once (in-launch merge) or write weight-0 partials (combine launch). Not together
+// with the in-kernel RoPE, whose cos / sin are one position's.
 // k_new / v_new (optional, Tq == 1): this step's K / V rows [B, 1, Hkv, D] (views into the fused
 // QKV rows allowed): appended at slot S-1 by the kernel itself (see decode_kernel).
 torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c10::optional<torch::Tensor> k_scale,
@@ -735,7 +742,9 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c
   TORCH_CHECK(S <= cap && q_offset >= 0 && q_offset + Tq <= S, who, ": bad cache extent");
   const float* ksp = quant ? la_f32_shape(who, "k_scale", k_scale, {B, Hkv, cap}) : nullptr;
   const float* vsp = quant ? la_f32_shape(who, "v_scale", v_scale, {B, Hkv, cap}) : nullptr;
-  const int64_t* sdev = la_defined(seq_len_dev) ? la_i64_scalar(who, "seq_len_dev", *seq_len_dev) : nullptr;
+  const I64Rows sl = la_defined(seq_len_dev) ? la_i64_rows(who, "seq_len_dev", *seq_len_dev, B) : I64Rows{};
+  const int64_t* sdev = sl.p;
+  TORCH_CHECK(sl.stride == 0 || Tq == 1, who, ": per-row lengths (seq_len_dev [B]) need Tq == 1");
   const bool fuse = la_defined(k_new);
   int64_t kv_rs = 0;
   if (fuse) {
@@ -752,6 +761,7 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c
   const DecodeAttnPlan p = plan_decode_attn(B, Tq, H, Hkv, D, S, !quant && q.scalar_type() == torch::kBFloat16,
                                             la_defined(counters) ? counters->numel() : 0, decode_env());
   const bool rope = la_defined(rope_cos);
+  TORCH_CHECK(!rope || sl.stride == 0, who, ": in-kernel RoPE takes one position: not with per-row lengths (seq_len_dev [B])");
   TORCH_CHECK(!rope || (p.small && fuse && D <= 256), who, ": in-kernel RoPE: the small decode kernel with the fused "
               "append, head_dim <= 256 only (check decode_small_applies first)");
   const float* rcp = rope ? la_f32_vec(who, "rope cos (one position)", rope_cos, D / 2) : nullptr;
@@ -781,7 +791,7 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c
       if constexpr (std::is_same<TQ, bf16>::value && decode_small_has(DD, GG, RR))
         hipLaunchKernelGGL((decode_small_kernel<DD, GG, RR>), dim3(B * Hkv), dim3(256), 0, stream, qp,
                            reinterpret_cast<bf16*>(kc.data_ptr()), reinterpret_cast<bf16*>(vc.data_ptr()), op, H, Hkv, cap,
-                           (int)S, (float)scale, sdev, q_rs, knp, vnp, kv_rs, rcp, rsp);
+                           (int)S, (float)scale, sdev, sl.stride, q_rs, knp, vnp, kv_rs, rcp, rsp);
       else ok = false;
     };
     auto general = [&](auto ktag) {
@@ -791,7 +801,7 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c
         if constexpr (decode_has(DD, GC))
           hipLaunchKernelGGL((decode_kernel<DD, GC, TQ, TK>), dim3(B * Hkv * Tq * splits), dim3(256), 0, stream, qp,
                              reinterpret_cast<const TK*>(kc.data_ptr()), reinterpret_cast<const TK*>(vc.data_ptr()), ksp, vsp,
-                             op, wo, wm, B, Tq, H, Hkv, cap, (int)S, (int)q_offset, splits, (float)scale, sdev, q_rs, knp,
+                             op, wo, wm, B, Tq, H, Hkv, cap, (int)S, (int)q_offset, splits, (float)scale, sdev, sl.stride, q_rs, knp,
                              vnp, kv_rs, cnt, p.split_keys);
         else ok = false;
       };
@@ -814,7 +824,7 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c
 }
 
 // k, v: [B, 1, Hkv, D] (views into the fused QKV rows allowed); caches [B, Hkv, cap, D]; the slot is
-// *pos_dev (device int64 [1]) when given, else pos
+// *pos_dev (device int64 [1]; or [B]: row b's own slot) when given, else pos
 void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor kc, torch::Tensor vc, c10::optional<torch::Tensor> ks,
                c10::optional<torch::Tensor> vs, c10::optional<torch::Tensor> pos_dev, int64_t pos) {
   const char* who = "kv_append";
@@ -830,7 +840,8 @@ void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor kc, torch::Tensor
                   (quant || kc.scalar_type() == k.scalar_type()),
               who, ": contiguous caches [B, Hkv, cap, D] of k's dtype or int8");
   const int cap = kc.size(2);
-  const int64_t* pd = la_defined(pos_dev) ? la_i64_scalar(who, "pos_dev", *pos_dev) : nullptr;
+  const I64Rows pr = la_defined(pos_dev) ? la_i64_rows(who, "pos_dev", *pos_dev, B) : I64Rows{};
+  const int64_t* pd = pr.p;
   TORCH_CHECK(pd || (pos >= 0 && pos < cap), who, ": cache overflow");
   float* ksp = quant ? la_f32_shape(who, "ks", ks, {B, Hkv, cap}) : nullptr;
   float* vsp = quant ? la_f32_shape(who, "vs", vs, {B, Hkv, cap}) : nullptr;
@@ -842,7 +853,7 @@ void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor kc, torch::Tensor
                          at::hip::getCurrentHIPStream(), reinterpret_cast<const T*>(k.data_ptr()),
                          reinterpret_cast<const T*>(v.data_ptr()), k.stride(0), v.stride(0),
                          reinterpret_cast<TK*>(kc.data_ptr()), reinterpret_cast<TK*>(vc.data_ptr()), ksp, vsp, B, Hkv, D, cap,
-                         pd, (int)pos);
+                         pd, pr.stride, (int)pos);
     };
     if (quant) launch(int8_t{});
     else launch(ttag);

@@ -379,7 +379,8 @@ __global__ void __launch_bounds__(64) decode_gemv_kernel(
     bf16* __restrict__ out, int64_t o_rs, int N, int K, int act, int D = 0, int nrot = 0,
     const float* __restrict__ cosv = nullptr, const float* __restrict__ sinv = nullptr,
     const int64_t* __restrict__ eidx = nullptr, const bf16* __restrict__ ewte = nullptr,
-    const bf16* __restrict__ ewpe = nullptr, const int64_t* __restrict__ epos = nullptr, int eV = 0, int eP = 0) {
+    const bf16* __restrict__ ewpe = nullptr, const int64_t* __restrict__ epos = nullptr, int eV = 0, int eP = 0,
+    int epos_rs = 0) {
   constexpr bool LN = PRO == 1;
   // EPI 3 (PRO 0 only): the whole wave on each of its RP rows — lane l reads chunks l, l + 64, …
   // — twice the workgroups of the half-wave form for the same rows per wave
@@ -426,8 +427,11 @@ __global__ void __launch_bounds__(64) decode_gemv_kernel(
   } else {
     float v[M][CPL][8];
     // embedding mode (ewte): the residual row is wte[token] + wpe[position] (the first block of a
-    // decode step, embed_fwd_kernel's arithmetic: clamped token, position min(*epos, P - 1))
-    const int epos_v = ewte ? min((int)*epos, eP - 1) : 0;
+    // decode step, embed_fwd_kernel's arithmetic: clamped token, position min(epos[m · epos_rs], P - 1):
+    // one position, or row m's own)
+    int epos_v[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) epos_v[m] = ewte ? min((int)epos[m * epos_rs], eP - 1) : 0;
 #pragma unroll
     for (int m = 0; m < M; ++m)
 #pragma unroll
@@ -438,7 +442,7 @@ __global__ void __launch_bounds__(64) decode_gemv_kernel(
           tok = tok < 0 ? 0 : (tok >= eV ? eV - 1 : tok);
           float a[8], b[8];
           Vec8<bf16>::load(ewte + (size_t)tok * K + 8 * c, a);
-          Vec8<bf16>::load(ewpe + (size_t)epos_v * K + 8 * c, b);
+          Vec8<bf16>::load(ewpe + (size_t)epos_v[m] * K + 8 * c, b);
 #pragma unroll
           for (int k = 0; k < 8; ++k) v[m][i][k] = a[k] + b[k];
         } else if (c < nc) {
@@ -674,7 +678,8 @@ std::tuple<int64_t, int64_t, int64_t, int64_t> decode_gemv_limits() {
 
 // out[M, N] = act(x · Wᵀ + bias) for M <= 4 decode rows (decode_gemv_kernel). LN mode (x
 // undefined): x = LayerNorm(resid_in + delta + dbias) with γ / β, resid_out receives the sum; with
-// emb_wte, LayerNorm(wte[idx] + wpe[pos]) and resid_out receives the embedding rows.
+// emb_wte, LayerNorm(wte[idx] + wpe[pos]) and resid_out receives the embedding rows (pos int64 [1], or
+// [M]: row m at its own position).
 // act 0 none, 1 GELU (erf), 2 GELU (tanh). rows_per_wave 2, 4 or 8 (0: by N).
 void decode_gemv(c10::optional<torch::Tensor> x, c10::optional<torch::Tensor> rin, c10::optional<torch::Tensor> delta,
                  c10::optional<torch::Tensor> dbias, c10::optional<torch::Tensor> rout,
@@ -695,7 +700,7 @@ void decode_gemv(c10::optional<torch::Tensor> x, c10::optional<torch::Tensor> ri
   const float *gp = nullptr, *bt = nullptr;
   const int64_t *eip = nullptr, *eps_p = nullptr;
   const bf16 *ewp = nullptr, *epp = nullptr;
-  int eV = 0, eP = 0;
+  int eV = 0, eP = 0, epos_rs = 0;
   if (!ln) {
     xp = la_rows(who, *x, K);
     M = x->size(0);
@@ -709,8 +714,10 @@ void decode_gemv(c10::optional<torch::Tensor> x, c10::optional<torch::Tensor> ri
                   ": embedding mode needs idx / wpe / pos");
       TORCH_CHECK(emb_idx->is_cuda() && emb_idx->scalar_type() == torch::kInt64 && emb_idx->is_contiguous(), who,
                   ": int64 token ids");
-      TORCH_CHECK(emb_pos->is_cuda() && emb_pos->scalar_type() == torch::kInt64 && emb_pos->numel() == 1, who,
-                  ": int64 pos [1]");
+      TORCH_CHECK(emb_pos->is_cuda() && emb_pos->scalar_type() == torch::kInt64 && emb_pos->is_contiguous() &&
+                      (emb_pos->numel() == 1 || (emb_pos->dim() == 1 && emb_pos->numel() == emb_idx->numel())),
+                  who, ": int64 pos [1] or [M]");
+      epos_rs = emb_pos->numel() == 1 ? 0 : 1;
       ewp = la_weight(who, *emb_wte);
       epp = la_weight(who, *emb_wpe);
       TORCH_CHECK(emb_wte->size(1) == K && emb_wpe->size(1) == K, who, ": wte / wpe [*, K]");
@@ -743,7 +750,7 @@ void decode_gemv(c10::optional<torch::Tensor> x, c10::optional<torch::Tensor> ri
                                            decltype(cpl)::value, decltype(epi)::value>),
                        dim3(p.grid), dim3(64), 0, stream, r.rin, r.delta, r.dbias, r.rout, gp, bt, (float)eps, xp, x_rs, wp,
                        bp, op, (int64_t)out.stride(0), N, K, (int)act, 0, 0, (const float*)nullptr, (const float*)nullptr,
-                       eip, ewp, epp, eps_p, eV, eP);
+                       eip, ewp, epp, eps_p, eV, eP, epos_rs);
   };
   // the instantiated (M, PRO, RP, CPL, EPI) per form; EPI 3 is the wave-per-row kernel (one row per wave)
   const bool ok =

@@ -158,19 +158,21 @@ __global__ void __launch_bounds__(256) gated_bwd_packed_kernel(const T* __restri
 }
 
 // ------------------------------------------------------------------------------ embedding
-// out[n, :] = wte[idx[n], :] + wpe[off + n % T, :]   (one wave per token row, 16-B lanes)
+// out[n, :] = wte[idx[n], :] + wpe[off + n % T, :]   (one wave per token row, 16-B lanes); off from
+// the device when off_dev is given: one value, or batch row n / T's own
 template <typename TW>
 __global__ void __launch_bounds__(256) embed_fwd_kernel(const int64_t* __restrict__ idx, const TW* __restrict__ wte,
                                                         const TW* __restrict__ wpe, float* __restrict__ out, int N,
                                                         int T, int C, int off, int V, const int64_t* __restrict__ off_dev,
-                                                        int P, uint64_t dseed, float dp) {
+                                                        int off_rs, int P, uint64_t dseed, float dp) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
   int64_t tok = idx[row];
   PZ_DEVICE_CHECK(tok >= 0 && tok < V);
   tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
-  if (off_dev != nullptr) off = (int)*off_dev;  // graph-replayed decode: position on the device
+  // graph-replayed decode: position on the device (off_rs 1: batch row row / T's own, a ragged step)
+  if (off_dev != nullptr) off = (int)off_dev[(row / T) * off_rs];
   const int pos = min(off + row % T, P - 1);
   for (int c = 8 * lane; c < C; c += 512) {
     float a[8], b[8];
@@ -592,9 +594,13 @@ void embedding_fwd(torch::Tensor idx, torch::Tensor wte, torch::Tensor wpe, int6
   const int B = idx.size(0), T = idx.size(1), C = wte.size(1), V = wte.size(0);
   TORCH_CHECK(C % 8 == 0 && wpe.size(1) == C && wte.scalar_type() == wpe.scalar_type());
   const int64_t* od = nullptr;
+  int od_rs = 0;  // [B]: every batch row its own offset
   if (off_dev.has_value() && off_dev->defined()) {  // device offset: the caller bounds it (clamped here)
-    TORCH_CHECK(off_dev->is_cuda() && off_dev->scalar_type() == torch::kInt64 && off_dev->numel() == 1);
+    TORCH_CHECK(off_dev->is_cuda() && off_dev->scalar_type() == torch::kInt64 && off_dev->is_contiguous() &&
+                    (off_dev->numel() == 1 || (off_dev->dim() == 1 && off_dev->numel() == B)),
+                "embedding_fwd: off_dev must be a device int64 [1] or [B]");
     od = off_dev->data_ptr<int64_t>();
+    od_rs = off_dev->numel() == 1 ? 0 : 1;
   } else {
     TORCH_CHECK(off + T <= wpe.size(0), "positions exceed the position table");
   }
@@ -605,7 +611,7 @@ void embedding_fwd(torch::Tensor idx, torch::Tensor wte, torch::Tensor wpe, int6
   FOR_FLOAT_TYPES(wte.scalar_type(), TW,
     hipLaunchKernelGGL(embed_fwd_kernel<TW>, dim3((N + 3) / 4), dim3(256), 0, stream, idxc.data_ptr<int64_t>(),
                        reinterpret_cast<const TW*>(wte.data_ptr()), reinterpret_cast<const TW*>(wpe.data_ptr()),
-                       out.data_ptr<float>(), N, T, C, (int)off, V, od, (int)wpe.size(0), (uint64_t)dropout_seed,
+                       out.data_ptr<float>(), N, T, C, (int)off, V, od, od_rs, (int)wpe.size(0), (uint64_t)dropout_seed,
                        (float)dropout_p))
 }
 

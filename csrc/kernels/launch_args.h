@@ -49,6 +49,20 @@ inline int64_t* la_i64_scalar(const char* who, const char* what, const torch::Te
   return t.data_ptr<int64_t>();
 }
 
+// int64 [1] or contiguous [rows]: one value for every row, or each row's own (a ragged decode step's
+// positions and cache lengths). The kernel reads entry row · stride; the stride is 0 or 1.
+struct I64Rows {
+  int64_t* p = nullptr;
+  int stride = 0;
+};
+
+inline I64Rows la_i64_rows(const char* who, const char* what, const torch::Tensor& t, int64_t rows) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.scalar_type() == torch::kInt64 && t.is_contiguous() &&
+                  (t.numel() == 1 || (t.dim() == 1 && t.numel() == rows)),
+              who, ": ", what, " must be a device int64 [1] or contiguous [rows = ", rows, "]");
+  return {t.data_ptr<int64_t>(), t.dim() == 1 && t.numel() == rows && rows > 1 ? 1 : 0};
+}
+
 // int32 contiguous tensor of exactly this shape (the stop check's sequences and per-row state)
 inline int* la_i32_shape(const char* who, const char* what, const torch::Tensor& t, at::IntArrayRef shape) {
   TORCH_CHECK(t.defined() && t.is_cuda() && t.scalar_type() == torch::kInt32 && t.is_contiguous() && t.sizes() == shape,

@@ -36,11 +36,14 @@ struct SampleIO {
   int64_t out2_stride;
   // graph decode (sample_step with advance): the writer of the LAST row to finish also advances
   // the step counters (+1 on *adv_a, *adv_b, *step) — every row has read *step by then — and
-  // re-arms the arrival counter: one launch less per decoded token
+  // re-arms the arrival counter: one launch less per decoded token. adv_rows (a ragged step: adv_a /
+  // adv_b hold one entry per row): every row's writer advances its own two entries — nothing in this
+  // launch reads them — and the last one advances *step alone
   int64_t* adv_a = nullptr;
   int64_t* adv_b = nullptr;
   unsigned* done = nullptr;
   int nrows = 0;
+  bool adv_rows = false;
   __device__ __forceinline__ float uniform(int row) const {
     if (uni) return uni[row];
     uint64_t z = (uint64_t)*seed + 0x9E3779B97F4A7C15ull * (uint64_t)(*step + 1) + 0xD1B54A32D192ED03ull * (uint64_t)(row + 1);
@@ -53,10 +56,16 @@ struct SampleIO {
     out[row] = tok;
     if (out2) out2[(size_t)row * out2_stride + *step] = tok;
     if (done) {
+      if (adv_rows) {
+        ++adv_a[row];
+        ++adv_b[row];
+      }
       __threadfence();  // this row's reads of *step and its stores come before its arrival
       if (atomicAdd(done, 1u) == (unsigned)nrows - 1u) {
-        ++*adv_a;
-        ++*adv_b;
+        if (!adv_rows) {
+          ++*adv_a;
+          ++*adv_b;
+        }
         ++*const_cast<int64_t*>(step);
         *done = 0u;
         __threadfence();
@@ -1131,7 +1140,8 @@ torch::Tensor sample_tokens(torch::Tensor logits, c10::optional<torch::Tensor> u
 
 // Graph-replayed decode: token of row r -> idx_out[r] and out_buf[r, *step]; uniforms hashed from
 // (seed, *step, r) on the device. With adv_a / adv_b / done (int32 [1], zero) the last row's writer
-// also advances the step counters (see SampleIO).
+// also advances the step counters (see SampleIO); adv_a / adv_b are int64 [1], or both [B]: one
+// position and one cache length per row, each advanced by 1.
 void sample_step(torch::Tensor logits, double temperature, int64_t top_k, torch::Tensor seed, torch::Tensor step,
                  torch::Tensor idx_out, torch::Tensor out_buf, c10::optional<torch::Tensor> adv_a,
                  c10::optional<torch::Tensor> adv_b, c10::optional<torch::Tensor> done, double top_p, double min_p) {
@@ -1146,26 +1156,31 @@ void sample_step(torch::Tensor logits, double temperature, int64_t top_k, torch:
   if (la_defined(done)) {
     TORCH_CHECK(adv_a.has_value() && adv_b.has_value(), who, ": advance needs both counters");
     TORCH_CHECK(done->scalar_type() == torch::kInt32 && done->numel() == 1, who, ": done must be int32 [1]");
-    io.adv_a = la_i64_scalar(who, "adv_a", *adv_a);
-    io.adv_b = la_i64_scalar(who, "adv_b", *adv_b);
+    const I64Rows ra = la_i64_rows(who, "adv_a", *adv_a, B), rb = la_i64_rows(who, "adv_b", *adv_b, B);
+    TORCH_CHECK(ra.stride == rb.stride, who, ": adv_a and adv_b must both be [1] or both [B]");
+    io.adv_a = ra.p;
+    io.adv_b = rb.p;
+    io.adv_rows = ra.stride == 1;
     io.done = reinterpret_cast<unsigned*>(done->data_ptr<int>());
     io.nrows = B;
   }
   launch_sample(who, logits, {seed, step, idx_out, out_buf, adv_a, adv_b, done}, io, temperature, top_k, top_p, min_p);
 }
 
-__global__ void decode_advance_kernel(int64_t* a, int64_t* b, int64_t* c) {
-  if (threadIdx.x == 0) {
-    ++*a;
-    ++*b;
-    ++*c;
+__global__ void decode_advance_kernel(int64_t* a, int64_t* b, int64_t* c, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    ++a[i];
+    ++b[i];
   }
+  if (threadIdx.x == 0) ++*c;
 }
 
-// +1 on three device int64 scalars (cache position, cache length, burst step) in one launch
+// +1 on the cache position and the cache length (device int64 [1] each, or [n] each: per row) and on
+// the burst step (int64 [1]) in one launch
 void decode_advance(torch::Tensor a, torch::Tensor b, torch::Tensor c) {
   const char* who = "decode_advance";
   la_one_device(who, a, {b, c});
-  hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, at::hip::getCurrentHIPStream(),
-                     la_i64_scalar(who, "a", a), la_i64_scalar(who, "b", b), la_i64_scalar(who, "c", c));
+  const I64Rows ra = la_i64_rows(who, "a", a, a.numel()), rb = la_i64_rows(who, "b", b, a.numel());
+  hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(64), 0, at::hip::getCurrentHIPStream(), ra.p, rb.p,
+                     la_i64_scalar(who, "c", c), (int)a.numel());
 }

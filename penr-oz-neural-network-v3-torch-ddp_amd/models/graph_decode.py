@@ -48,6 +48,16 @@ between steps lives on the device:
   graph mode gains a fourth element (``GraphDecoder.set_logit_bias``): off, entries, or entries + mask —
   the last two differ in their grid, so they are separate graphs.
 
+* ragged batches (``ops/ragged.py``): a ``GraphDecoder`` with ``ragged=True`` keeps ``pos_t`` / ``len_t`` as
+  ``[rows]`` — every row's own slot and cache length. The decode-attention kernel's workgroups read their
+  batch row's entry (key range, split count, in-launch merge and append slot per row), the embedding
+  gathers each row's own position, the RoPE table is ``[rows, D/2]`` (Gemma then runs the plain QKV linear
+  and the separate RoPE pass over the rows viewed as ``[1, rows, W]``: the QKV epilogues take one
+  position's table), and the sampler's fused advance adds 1 to every row's two entries: the same number
+  of launches as the uniform step for GPT, one more per block for Gemma where the uniform step rotates in
+  the QKV epilogue. The host tracks the longest row for the capacity check; the prompt lengths come from
+  ``set_lengths`` once per call. Graph modes and their lazily captured graphs are as above.
+
 The host only tracks the cache length (one per replay) to switch to the reference's
 sliding-window re-prefill when the window is full, and copies each burst of tokens back once
 (stop-token checks per burst). Prefill and re-prefill run eagerly. RoPE models (Gemma) rotate
@@ -134,9 +144,12 @@ class _GraphMode:
 
     graph_mode = False
 
-    def init_graph_state(self, device):
-        self.pos_t = torch.zeros(1, dtype=torch.long, device=device)  # slot written by the step
-        self.len_t = torch.ones(1, dtype=torch.long, device=device)   # cache length after it
+    def init_graph_state(self, device, rows: int | None = None):
+        """``rows``: a ragged decoder's row count — one slot and one length per row instead of one."""
+        self.ragged = rows is not None
+        n = rows if self.ragged else 1
+        self.pos_t = torch.zeros(n, dtype=torch.long, device=device)  # slot written by the step
+        self.len_t = torch.ones(n, dtype=torch.long, device=device)   # cache length after it
         self._rope_tables: dict = {}
 
     def begin_step(self):
@@ -144,7 +157,8 @@ class _GraphMode:
 
     def rope_table(self, key, inv_freq: Tensor, T: int):
         """cos / sin for positions pos_t..pos_t+T-1, computed on the device once per step and
-        ``key`` = (theta, head_dim): layers with the same rotary setup share it."""
+        ``key`` = (theta, head_dim): layers with the same rotary setup share it. Ragged (T == 1):
+        [rows, D/2], every row at its own position."""
         key = (*key, T)
         tab = self._rope_tables.get(key)
         if tab is None:
@@ -174,7 +188,7 @@ class StaticKVCache(_GraphMode, kvc.KVCache):
         the separate RoPE pass (profiles/negative_r6_rope_in_decode_attn.log)."""
         kc = self._k[0]
         return (os.environ.get("PENROZ_DECODE_ROPE_IN_ATTN", "0") == "1" and self.graph_mode and FUSED_APPEND
-                and _ext.available()
+                and not self.ragged and _ext.available()  # (the in-kernel rotation takes one position)
                 and attn_ops.decode_rope_fusable(B, H, Hkv, D, kc.shape[2], kc.dtype))
 
     def attend_rope(self, l: int, q: Tensor, k: Tensor, v: Tensor, cos: Tensor, sin: Tensor) -> Tensor:
@@ -578,6 +592,11 @@ class GemmaDecodeProgram:
             return self._lin(y, b["qkv"], gemv, b["qkv_q8"] if self.q8 else None), None
         inv = a._inv_freq(D, y.device)
         cos, sin = cache.rope_table((a.rope_theta, D), inv, 1)
+        if getattr(cache, "ragged", False):
+            # a ragged step: cos / sin are [rows, D/2] and the RoPE epilogues take one position's table, so
+            # the plain QKV linear, then the RoPE pass over the rows viewed as [1, rows, W]
+            qkv = self._lin(y, b["qkv"], gemv, b["qkv_q8"] if self.q8 else None)
+            return rope_ops.apply_rope_qkv(qkv.view(1, rows, -1), H, Hkv, D, inv, 0, table=(cos, sin)).view(rows, -1), None
         if self.q8:
             return gemm_ops.decode_gemv_q8_rope(y.contiguous(), b["qkv_q8"], cos, sin, D, H + Hkv), None
         if gemv and DECODE_EPILOGUES and D % 2 == 0:
@@ -697,7 +716,8 @@ class GraphDecoder:
     """Static decode state + the captured step graph for ``rows`` sequences."""
 
     def __init__(self, model, rows: int, capacity: int, temperature: float, top_k: int | None,
-                 top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None):
+                 top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None,
+                 ragged: bool = False):
         # weak: the model caches its decoders (model.__dict__), so a strong reference would make a
         # cycle that only the cyclic GC frees — and a collection that runs while ANOTHER graph is
         # being captured destroys this one's graph mid-capture (a hard abort)
@@ -707,7 +727,11 @@ class GraphDecoder:
         self.pos_layers = model._find_position_embeddings()
         cls = StaticTurboKVCache if kvc.TURBO_QUANT_ENABLED else StaticKVCache
         self.cache = cls(len(self.attn), capacity)
-        self.cache.init_graph_state(self.device)
+        # ragged (ops/ragged.py): every row at its own position and cache length — pos_t / len_t are [rows]
+        self.ragged = bool(ragged)
+        self.cache.init_graph_state(self.device, rows if self.ragged else None)
+        self._lens_t: Tensor | None = None  # the call's prompt lengths [rows] (device) and the longest
+        self._lmax = 0
         self.rows, self.capacity = rows, capacity
         self.temperature, self.top_k = float(temperature), top_k
         self.top_p, self.min_p = _normalise_filters(temperature, top_p, min_p)
@@ -721,6 +745,8 @@ class GraphDecoder:
         attn_ops.decode_counters(self.device)  # (the decode attention's split-merge counters too)
         gemm_ops.load_tuned_gemms()  # measured hipBLASLt solutions for the decode-shaped GEMMs too
         self.program = GPTDecodeProgram.build(model) or GemmaDecodeProgram.build(model)
+        if self.ragged and self.program is None:
+            raise ValueError("a ragged decoder needs a decode program (bf16 GPT-2-pattern or Gemma-family model)")
         # the weight format in effect: "int8" when asked for AND this decoder's step qualifies (a
         # decode program at 1-4 rows whose linears all fit the int8 GEMV); the quantised copies exist
         # from here on, before the warm-up step and the capture
@@ -896,16 +922,37 @@ class GraphDecoder:
         v = (self.run_seed + self._HASH_STEP * int(start)) & (2 ** 64 - 1)
         return v - 2 ** 64 if v >= 2 ** 63 else v
 
-    def _set_state(self, last_tok: Tensor, cache_len: int, start: int = 0):
+    def set_lengths(self, lens: list[int]):
+        """Once per ragged generate call, before its first ``run()``: the rows' prompt lengths. The
+        eager prefill pads to the longest, so the host-side cache length counts from there; row ``b``'s
+        own is that minus ``max(lens) - lens[b]``."""
+        assert self.ragged and len(lens) == self.rows and min(lens) >= 1, (self.ragged, len(lens), self.rows)
+        self._lens_t = torch.tensor(lens, dtype=torch.long, device=self.device)
+        self._lmax = max(lens)
+
+    def _row_lengths(self, cache_len: int):
+        """What ``_set_state`` takes for a host-side cache length (the longest row's): the number itself,
+        or, ragged, every row's own length [rows] on the device."""
+        if not self.ragged:
+            return cache_len
+        assert self._lens_t is not None, "ragged decoder: set_lengths() comes before run()"
+        return self._lens_t + (cache_len - self._lmax)
+
+    def _set_state(self, last_tok: Tensor, cache_len, start: int = 0):
+        """``cache_len``: the cache length every row is at — or, ragged, int64 [rows]: each row's own."""
         self.seed_t.fill_(self._burst_seed(start))
         self.idx.copy_(last_tok)
-        self.cache.pos_t.fill_(cache_len)
-        self.cache.len_t.fill_(cache_len + 1)
+        if self.ragged:
+            self.cache.pos_t.copy_(cache_len)
+            torch.add(cache_len, 1, out=self.cache.len_t)
+        else:
+            self.cache.pos_t.fill_(cache_len)
+            self.cache.len_t.fill_(cache_len + 1)
         self.step_t.zero_()
         if self._bias_form != "off":
             self.bias.base_t.fill_(int(start))  # the step's t = start + step_t
 
-    def _capture(self, last_tok: Tensor, cache_len: int, start: int = 0):
+    def _capture(self, last_tok: Tensor, cache_len, start: int = 0):
         # warm-up run on a side stream (lazy allocations, kernel loading), then capture. The
         # warm-up really executes a step, so it must start from the true state: it then writes
         # exactly the cache slot the first real step rewrites.
@@ -937,7 +984,7 @@ class GraphDecoder:
                 gc.enable()
         self.graph = g
         self._set_state(last_tok, cache_len, start)  # capture does not execute; state is as before
-        log.info(f"captured decode graph: rows={self.rows} block={self.capacity} "
+        log.info(f"captured decode graph: rows={self.rows}{' ragged' if self.ragged else ''} block={self.capacity} "
                  f"temperature={self.temperature} top_k={self.top_k} top_p={self.top_p} min_p={self.min_p} "
                  f"penalties={'on' if self._penalised else 'off'} logprobs={'on' if self._lp_on else 'off'} "
                  f"stop={'on' if self._stop_on else 'off'} logit_bias={self._bias_form}")
@@ -947,13 +994,17 @@ class GraphDecoder:
         """Decode ``n_steps`` tokens after ``last_tok`` [rows, 1] from the current cache; returns
         the [rows, n_steps] new tokens (device). ``start``: absolute index (within this generate
         call) of the first of them. The cache must have room for n_steps more. With log-probabilities
-        on, ``last_logprobs`` then holds this burst's (views of the burst buffers, like the tokens)."""
+        on, ``last_logprobs`` then holds this burst's (views of the burst buffers, like the tokens).
+        Ragged: the host-side cache length is the longest row's (the capacity check is against it);
+        the rows' own come from ``set_lengths``."""
         cache_len = self.cache.seq_len()
         assert 0 < cache_len and cache_len + n_steps <= self.capacity, (cache_len, n_steps, self.capacity)
+        assert not self.ragged or cache_len >= self._lmax, (cache_len, self._lmax)
+        lens = self._row_lengths(cache_len)
         if self.graph is None:
-            self._capture(last_tok, cache_len, start)
+            self._capture(last_tok, lens, start)
         else:
-            self._set_state(last_tok, cache_len, start)
+            self._set_state(last_tok, lens, start)
         for _ in range(n_steps):
             self.graph.replay()
         self.cache._len = [cache_len + n_steps] * self.cache.num_layers
@@ -975,6 +1026,17 @@ def _log_q8_unused(rows: int, program) -> None:
     log.info(f"int8 decode weights requested, but the step keeps bf16 weights: {why}")
 
 
+def ragged_program_ok(model) -> bool:
+    """A ragged step is an explicit decode program's (the module forward has one position for all rows)."""
+    p = next(model.parameters())
+    key = (p.data_ptr(), p.dtype, DECODE_PROGRAM)
+    hit = model.__dict__.get("_ragged_program_ok")
+    if hit is None or hit[0] != key:  # (asked once per generate call: remembered per weights)
+        hit = (key, (GPTDecodeProgram.build(model) or GemmaDecodeProgram.build(model)) is not None)
+        model.__dict__["_ragged_program_ok"] = hit
+    return hit[1]
+
+
 def _normalise_filters(temperature: float, top_p: float | None, min_p: float | None):
     """(top_p, min_p) with the values that mean "no filter" — and both at temperature 0, which
     ignores them — folded to None, so equal behaviour shares one captured graph."""
@@ -986,18 +1048,22 @@ def _normalise_filters(temperature: float, top_p: float | None, min_p: float | N
 
 def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: int | None,
                 top_p: float | None = None, min_p: float | None = None,
-                weight_quant: str | None = None) -> GraphDecoder | None:
-    """Cached per model and (rows, block size, sampling settings, weights identity, weight format in
-    effect for ``weight_quant`` — as ``ops.weight_quant.resolve`` returned it); None when the
-    model does not qualify (CPU, no attention, RoPE head_dim without a decode kernel) or ``PENROZ_GRAPH_DECODE=0``."""
+                weight_quant: str | None = None, ragged: bool = False) -> GraphDecoder | None:
+    """Cached per model and (rows, block size, sampling settings, weights identity, ragged or not, weight
+    format in effect for ``weight_quant`` — as ``ops.weight_quant.resolve`` returned it); None when the
+    model does not qualify (CPU, no attention, RoPE head_dim without a decode kernel) or ``PENROZ_GRAPH_DECODE=0``
+    — and, for a ragged decoder, when the model has no decode program or the kernels are not built."""
     if not applicable(model):
+        return None
+    if ragged and not (_ext.available() and ragged_program_ok(model)):
         return None
     p = next(model.parameters())
     # weights identity AND version: in-place updates (training) re-capture, so nothing captured
     # (e.g. LayerNorm's cached fp32 weight copies for bf16 models) can go stale
     version = sum(q._version for q in model.parameters())
     base = (rows, block_size, float(temperature), top_k if temperature else None,
-            *_normalise_filters(temperature, top_p, min_p), kvc.TURBO_QUANT_ENABLED, p.data_ptr(), p.dtype, version)
+            *_normalise_filters(temperature, top_p, min_p), kvc.TURBO_QUANT_ENABLED, p.data_ptr(), p.dtype, version,
+            bool(ragged))
     cache = model.__dict__.setdefault("_graph_decoders", {})
     # the key holds the weight format IN EFFECT: a request for int8 that this step cannot honour
     # (more than 4 rows, no decode program, a K that does not fit) shares the bf16 decoder instead of
@@ -1007,7 +1073,7 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
         weight_quant = None
     dec = cache.get(base + (weight_quant,))
     if dec is None:
-        dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p, weight_quant)
+        dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p, weight_quant, ragged=ragged)
         if dec.weight_quant != weight_quant:  # asked for int8, runs bf16
             if len(unused) >= 64:
                 unused.clear()

@@ -46,6 +46,7 @@ from penroz.models.mapper import Mapper
 from penroz.ops import logit_bias as bias_ops
 from penroz.ops import logprobs as lp_ops
 from penroz.ops import penalties as pen_ops
+from penroz.ops import ragged as ragged_ops
 from penroz.ops import sampling as samp_ops
 from penroz.ops import stopping as stop_ops
 from penroz.ops import fused as fused_ops
@@ -460,8 +461,11 @@ class NeuralNetworkModel(nn.Module):
                              stop: list | None = None, stop_state: stop_ops.StopState | None = None,
                              logit_bias: dict | None = None, banned_token_ids: list | None = None,
                              allowed_token_ids: list | None = None, min_tokens: int | None = None,
-                             bias_state: bias_ops.BiasState | None = None, produced: int = 0):
-        """``penalty_state``: the generate call's penalty bookkeeping (its values already set, its
+                             bias_state: bias_ops.BiasState | None = None, produced: int = 0,
+                             last_index: Tensor | None = None):
+        """``last_index`` (int64 [rows], a ragged call's padded prefill): the position whose logits are
+        row b's — its last real prompt token — instead of the last position.
+        ``penalty_state``: the generate call's penalty bookkeeping (its values already set, its
         ``begin`` run on the call's prompt); ``penalty_new`` [rows, 1]: the tokens the previous step
         sampled, which this step counts (None on a call's first step). Penalty values without a state
         take the whole ``context`` as the prompt. ``logprobs`` n: returns (tokens, ``ops.logprobs.
@@ -505,7 +509,10 @@ class NeuralNetworkModel(nn.Module):
             model_input = context[:, -block_size:]
         activations, _ = self(model_input, skip_softmax=True)
         logits = activations[-1]
-        last = logits[:, -1, :] if logits.ndim == 3 else logits
+        if last_index is not None:
+            last = logits[torch.arange(logits.shape[0], device=logits.device), last_index]
+        else:
+            last = logits[:, -1, :] if logits.ndim == 3 else logits
         if penalty_state is not None:  # between the lm_head and the sampler, as in the captured step
             last = penalty_state.apply(last.contiguous(), penalty_new)
         if bias_state is not None:  # behind the penalties, as in the captured step
@@ -580,7 +587,8 @@ class NeuralNetworkModel(nn.Module):
                       weight_quant: str | None = None,
                       repetition_penalty: float | None = None, presence_penalty: float | None = None,
                       frequency_penalty: float | None = None, logprobs: int | None = None,
-                      stop_run: stop_ops.StopRun | None = None, bias: bias_ops.Canonical | None = None):
+                      stop_run: stop_ops.StopRun | None = None, bias: bias_ops.Canonical | None = None,
+                      lens: list[int] | None = None):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
         (cache full) run eagerly, exactly as the per-token path. Logit penalties keep one state per
@@ -599,13 +607,24 @@ class NeuralNetworkModel(nn.Module):
         ``bias``: the call's logit bias / banned / allowed tokens / ``min_tokens`` in canonical form
         (``_prepare_generation``'s, ops/logit_bias.py). The call keeps one ``BiasState`` — the decoder's,
         where there is one: an eager step applies it with ``t`` = the tokens produced so far, a graph step
-        reads the burst's start from the device and adds its own counter."""
+        reads the burst's start from the device and adds its own counter.
+        ``lens`` (a ragged call, ops/ragged.py): the rows' prompt lengths; ``context`` is then the prompts
+        right-padded to the longest, the decoder is a ragged one (the caller made sure there is one), row
+        b's first token comes from the prefill's logits at ``lens[b] - 1`` and every graph step runs row b
+        at its own position; the generated tokens are appended behind the padded prompts, and the window
+        never slides (``check_prompts``)."""
         from penroz.models import graph_decode
         rows = context.shape[0]
         n_lp = lp_ops.check_logprobs(logprobs)
         pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        ragged = {} if lens is None else {"ragged": True}  # (a rectangular call's lookup is what it was)
         dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k, top_p, min_p,
-                                       wq_ops.resolve(weight_quant))
+                                       wq_ops.resolve(weight_quant), **ragged)
+        last_index = None
+        if lens is not None:
+            assert dec is not None, "a ragged call needs the ragged decoder (generate_batch falls back before this)"
+            dec.set_lengths(lens)
+            last_index = torch.tensor(lens, dtype=torch.long, device=context.device) - 1
         if dec is not None:
             dec.set_penalties(pen)
             dec.set_logprobs(n_lp)
@@ -650,7 +669,8 @@ class NeuralNetworkModel(nn.Module):
                     new = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache,
                                                     pos, top_p=top_p, min_p=min_p, penalty_state=state,
                                                     penalty_new=last, logprobs=n_lp, stop_state=stop_state,
-                                                    bias_state=bias_state, produced=produced)
+                                                    bias_state=bias_state, produced=produced,
+                                                    last_index=last_index if n == 0 else None)
                     if n_lp is not None:
                         new, lps = new[0], tuple(t.unsqueeze(1) for t in new[1])  # one step: [rows, 1, ...]
                     for p in pos:
@@ -685,6 +705,9 @@ class NeuralNetworkModel(nn.Module):
         bursts instead of one replay and one host read per token — and returns what it always did; with
         more rows, or streaming, it keeps the per-token host check below. Either way ``stop_token`` and the
         one-token sequences of ``stop`` are the end tokens that ``min_tokens`` suppresses (ops/logit_bias.py)."""
+        if ragged_ops.ragged_lengths(input_context) is not None:
+            raise ValueError("prompts of different lengths: generate_tokens and generate_tokens_stream return row 0 "
+                             "of a rectangular batch; use generate_batch for a ragged one")
         pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                     frequency_penalty=frequency_penalty, logprobs=logprobs)
         context, softmax_layer, bias = self._prepare_generation(
@@ -835,9 +858,28 @@ class NeuralNetworkModel(nn.Module):
         once all rows have finished, and the result is ``(contexts, [info per row])`` with
         ``finish_reason`` / ``stop_sequence`` per row (and the log-probability lists, cut to match).
         ``logit_bias`` / ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in
-        ``generate_tokens``, the same values for every row."""
+        ``generate_tokens``, the same values for every row.
+        Prompts of different lengths (ops/ragged.py) are a ragged call: row b is the generation a one-row
+        call makes from prompt b alone, the contexts returned are each row's own prompt plus its tokens, and
+        ``max(len_b) + max_new_tokens <= block_size`` is required — a ragged call never slides its window
+        (rows would reach it at different steps; the re-prefill is a whole-batch operation). On the GPU the
+        rows share one captured step, each at its own position (models/graph_decode.py); elsewhere they run
+        one at a time (``ops.ragged.reference_generate``). Rows of one length take the rectangular path."""
         pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
                     frequency_penalty=frequency_penalty, logprobs=logprobs)
+        lens = ragged_ops.ragged_lengths(input_context)
+        prompts = None
+        if lens is not None:
+            prompts = ragged_ops.check_prompts(input_context, block_size, max_new_tokens, self._vocab_size())
+            why = self._ragged_fallback(len(prompts), block_size, temperature, top_k, top_p, min_p, weight_quant)
+            if why is not None:
+                ragged_ops.log_fallback(why)
+                return ragged_ops.reference_generate(
+                    self, prompts, block_size, max_new_tokens, temperature, top_k, stop_token, top_p=top_p,
+                    min_p=min_p, weight_quant=weight_quant, stop=stop, logit_bias=logit_bias,
+                    banned_token_ids=banned_token_ids, allowed_token_ids=allowed_token_ids, min_tokens=min_tokens,
+                    **pens)
+            input_context = ragged_ops.pad_prompts(prompts)  # (its K/V behind a row's length are never read)
         context, sm, bias = self._prepare_generation(
             input_context, max_new_tokens, temperature, top_k, top_p, min_p, weight_quant, stop=stop,
             stop_token=stop_token, logit_bias=logit_bias, banned_token_ids=banned_token_ids,
@@ -850,7 +892,7 @@ class NeuralNetworkModel(nn.Module):
         burst = 32 if stop_token is not None else max_new_tokens
         for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, sm, burst,
                                       top_p=top_p, min_p=min_p, weight_quant=weight_quant, stop_run=run, bias=bias,
-                                      **pens):
+                                      lens=lens, **pens):
             if logprobs is not None:
                 new, lps = new
             keep, stopped = new.shape[1], False
@@ -868,17 +910,32 @@ class NeuralNetworkModel(nn.Module):
                 stopped = all(s_done)
             if stopped:
                 break
-        if run is None:
-            return context.tolist() if logprobs is None else (context.tolist(), infos)
         contexts = context.tolist()
+        if prompts is not None:  # a ragged call: each row's own prompt in front of its tokens
+            contexts = ragged_ops.assemble(prompts, [c[prompt_len:] for c in contexts])
+        if run is None:
+            return contexts if logprobs is None else (contexts, infos)
+        produced = context.shape[1] - prompt_len
         for b, info in enumerate(infos):  # ragged: each row ends with its own finish
-            keep, fin = stop_ops.finish_info(s_done[b], context.shape[1] - prompt_len, s_fin[b])
-            contexts[b] = contexts[b][:prompt_len + keep]
+            keep, fin = stop_ops.finish_info(s_done[b], produced, s_fin[b])
+            contexts[b] = contexts[b][:len(contexts[b]) - produced + keep]
             for key in ("token_logprobs", "top_logprobs"):
                 if key in info:
                     del info[key][keep:]
             info.update(fin)
         return contexts, infos
+
+    def _ragged_fallback(self, rows: int, block_size: int, temperature, top_k, top_p, min_p, weight_quant) -> str | None:
+        """Why a ragged call runs its rows one at a time (ops/ragged.py), or None: the ragged captured
+        step serves it."""
+        from penroz.models import graph_decode
+        dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k, top_p, min_p,
+                                       wq_ops.resolve(weight_quant), ragged=True)
+        if dec is not None:
+            return None
+        if not graph_decode.applicable(self):
+            return "no captured decode step here: CPU, PENROZ_GRAPH_DECODE=0 or a model it does not take"
+        return "the model has no decode program (bf16 GPT-2-pattern or Gemma-family, PENROZ_DECODE_PROGRAM=1)"
 
     # ------------------------------------------------------------------ training
     @classmethod

@@ -234,7 +234,9 @@ def decode_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, seq_len: int,
     ``[B, Hkv, cap]`` — TurboQuant; dequantisation fused into the kernel).
     GPU: split-K decode kernel (``csrc/kernels/decode_attn.hip``). ``seq_len_dev`` (device int64
     [1], GPU only): the kernel reads the cache length at run time (``seq_len`` is then the
-    capacity bound) — the form a captured HIP graph replays at every position.
+    capacity bound) — the form a captured HIP graph replays at every position. int64 [B] (Tq == 1): every
+    batch row its own cache length (a ragged decode step, ops/ragged.py): row b attends its first
+    ``seq_len_dev[b]`` slots, and a fused append writes its slot ``seq_len_dev[b] - 1``; not with ``rope``.
     ``k_new`` / ``v_new`` ([B, 1, Hkv, D], GPU kernel only): this step's K / V, appended at slot
     ``seq_len - 1`` by the attention kernel itself (int8 caches: quantised as ``kv_quantize_into``).
     ``rope`` (fp32 cos / sin [D/2] of this step's single position; with ``k_new`` / ``v_new``): q and
@@ -255,6 +257,8 @@ def decode_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, seq_len: int,
     if k_new is not None:
         raise ValueError("fused KV append needs the decode kernel")
     if seq_len_dev is not None:
+        if seq_len_dev.numel() != 1:
+            raise ValueError("per-row cache lengths need the decode kernel")
         seq_len = int(seq_len_dev.item())
     k = k_cache[:, :, :seq_len]
     v = v_cache[:, :, :seq_len]

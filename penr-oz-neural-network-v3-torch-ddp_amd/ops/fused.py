@@ -34,8 +34,8 @@ def reference_embedding_fwd(idx: Tensor, wte: Tensor, wpe: Tensor, pos_offset: i
 def embedding_fwd(idx: Tensor, wte: Tensor, wpe: Tensor, pos_offset: int = 0, out: Tensor | None = None,
                   pos_dev: Tensor | None = None, dropout_p: float = 0.0, dropout_seed: int = 0) -> Tensor:
     """idx [B,T] int64 -> fp32 [B*T, C] = drop(wte[idx] + wpe[offset + t]); ``pos_dev`` (device
-    int64 [1]) supplies the offset at run time instead (graph-replayed decode; clamped to the
-    table). ``dropout_p``: inverted dropout, mask hashed from (``dropout_seed``, element index)."""
+    int64 [1], or [B]: every batch row its own) supplies the offset at run time instead (graph-replayed
+    decode; clamped to the table). ``dropout_p``: inverted dropout, mask hashed from (``dropout_seed``, element index)."""
     B, T = idx.shape
     out = torch.empty(B * T, wte.shape[1], dtype=torch.float32, device=idx.device) if out is None else out
     kernels().embedding_fwd(idx, wte, wpe, int(pos_offset), out, pos_dev, float(dropout_p), int(dropout_seed))

@@ -261,7 +261,7 @@ def decode_gemv_emb(idx: Tensor, pos: Tensor, wte: Tensor, wpe: Tensor, resid_ou
                     bias: Tensor | None, act: int = 0) -> Tensor:
     """``decode_gemv`` with the embedding gather + LayerNorm as its prologue:
     act(LN(wte[idx] + wpe[pos])·wᵀ + bias), the fp32 embedding rows written to ``resid_out``; ``pos``
-    is the device position."""
+    is the device position (int64 [1], or [rows]: every row its own)."""
     out = _decode_out(resid_out, w.shape[0])
     kernels().decode_gemv(x=None, resid_in=None, delta=None, dbias=None, resid_out=resid_out, gamma=ln[0],
                           beta=ln[1], eps=ln[2], w=w, bias=bias, out=out, act=act, emb_idx=idx, emb_wte=wte,

@@ -16,8 +16,13 @@ from penroz.ops._ext import use_kernels, kernels
 
 def rope_table(inv_freq: Tensor, offset: int, T: int, device, offset_dev: Tensor | None = None) -> tuple[Tensor, Tensor]:
     """cos / sin [T, D/2] for positions offset..offset+T-1; ``offset_dev`` (device int64 [1])
-    supplies the offset at run time instead (graph-replayed decode)."""
-    if offset_dev is not None:
+    supplies the offset at run time instead (graph-replayed decode). An ``offset_dev`` of shape
+    [rows] (T == 1: a ragged decode step) gives [rows, D/2], row r at its own position."""
+    if offset_dev is not None and offset_dev.numel() > 1:
+        if T != 1 or offset_dev.dim() != 1:
+            raise ValueError("a per-row RoPE offset must be [rows] and takes one position per row (T == 1)")
+        t = offset_dev.to(torch.float32)
+    elif offset_dev is not None:
         t = offset_dev.to(torch.float32) + torch.arange(T, device=device, dtype=torch.float32)
     else:
         t = torch.arange(offset, offset + T, device=device, dtype=torch.float32)

@@ -172,6 +172,10 @@ class GenerateRequest(ModelRequest):
                                      description="Decode weight format: \"int8\" (weight-only int8 for batch 1-4 "
                                                  "decode steps), \"\" (bf16), null: PENROZ_DECODE_WEIGHTS")
     stream: bool = Field(False, examples=[False], description="Stream tokens as text/plain lines")
+    batch: bool = Field(False, examples=[False],
+                        description="Return every row: {\"sequences\": [[...], ...]}, each row's prompt plus its "
+                                    "tokens; the prompts may differ in length (max length + max_new_tokens <= "
+                                    "block_size then); not together with stream")
 
 
 class DecodeTokensRequest(TokenizerRequest):
@@ -469,6 +473,8 @@ def evaluate_model(body: EvaluateRequest = Body(...)):
 def model_generate(body: GenerateRequest = Body(...)):
     if body.weight_quant is not None:  # an unknown format is a 400 before the model is touched (streams too)
         wq_ops.resolve(body.weight_quant)
+    if body.batch and body.stream:  # (likewise)
+        raise ValueError("batch returns every row at once: not together with stream")
     stop = stop_ops.check_stop(body.stop)  # (and a malformed stop set; ids beyond the vocabulary: once it is known)
     if stop is not None and body.stop_token is not None:
         raise ValueError("give stop_token or stop, not both (a stop_token s is the stop sequence [s])")
@@ -486,6 +492,22 @@ def model_generate(body: GenerateRequest = Body(...)):
         penalties["logprobs"] = body.logprobs
     if stop is not None:  # (likewise)
         penalties["stop"] = stop
+    if body.batch:
+        # every row of the batch, ragged or not (ops/ragged.py): generate_batch's result, row for row
+        with _Held(model):
+            res = model.generate_batch(body.input, body.block_size, body.max_new_tokens, body.temperature,
+                                       body.top_k, body.stop_token, top_p=body.top_p, min_p=body.min_p,
+                                       weight_quant=body.weight_quant, **penalties)
+        if body.logprobs is None and stop is None:
+            return {"sequences": res}
+        sequences, infos = res
+        out = {"sequences": sequences}
+        if stop is not None:
+            out["finish_reason"] = [info.pop("finish_reason") for info in infos]
+            out["stop_sequence"] = [info.pop("stop_sequence") for info in infos]
+        if body.logprobs is not None:
+            out["logprobs"] = infos
+        return out
     if body.stream:
         # the lock is held for the stream's whole lifetime (the KV cache stays attached between
         # chunks) and released by the background task even when the client goes away mid-stream
