@@ -50,9 +50,11 @@ torch::Tensor cross_entropy_fwd_bwd(torch::Tensor logits, torch::Tensor targets,
                                     c10::optional<torch::Tensor> grad_out);
 // adamw.hip
 void adamw_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow,
-                double lr, double b1, double b2, double eps, double wd, int64_t step, double grad_scale, bool maximize);
+                double lr, double b1, double b2, double eps, double wd, int64_t step, double grad_scale, bool maximize,
+                c10::optional<torch::Tensor> scale_dev);
 void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow,
-               double lr, double b1, double b2, double eps, double wd, int64_t step, double grad_scale, bool maximize);
+               double lr, double b1, double b2, double eps, double wd, int64_t step, double grad_scale, bool maximize,
+               c10::optional<torch::Tensor> scale_dev);
 void multi_tensor_adam(std::vector<torch::Tensor> ps, std::vector<torch::Tensor> gs, std::vector<torch::Tensor> ms,
                        std::vector<torch::Tensor> vs, double lr, double b1, double b2, double eps, double wd,
                        int64_t step, double grad_scale, bool maximize, bool decoupled);
@@ -145,6 +147,10 @@ void logit_bias_apply(torch::Tensor logits, torch::Tensor ids, torch::Tensor bia
                       torch::Tensor n_entries, c10::optional<torch::Tensor> allow, bool allow_on, torch::Tensor base_t,
                       c10::optional<torch::Tensor> step_t);
 std::tuple<int64_t, int64_t, int64_t> logit_bias_plan(int64_t B, int64_t V, bool allow_on);
+// grad_norm.hip
+int64_t grad_sumsq_chunks(int64_t n);
+int64_t grad_sumsq(torch::Tensor g, torch::Tensor part);
+void grad_clip_finish(torch::Tensor part, int64_t chunks, double max_norm, torch::Tensor out);
 // adamw.hip
 torch::Tensor update_moments(std::vector<torch::Tensor> ws, std::vector<torch::Tensor> ps);
 // gemm_nt.hip
@@ -237,8 +243,16 @@ PYBIND11_MODULE(penroz_kernels, m) {
   m.def("tensor_stats", &tensor_stats);
   m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd, pybind11::arg("logits"), pybind11::arg("targets"),
         pybind11::arg("scale"), pybind11::arg("ignore_index"), pybind11::arg("grad_out") = pybind11::none());
-  m.def("adamw_step", &adamw_step);
-  m.def("adam_step", &adam_step);
+  m.def("adamw_step", &adamw_step, pybind11::arg("p"), pybind11::arg("g"), pybind11::arg("m"), pybind11::arg("v"),
+        pybind11::arg("shadow"), pybind11::arg("lr"), pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"),
+        pybind11::arg("wd"), pybind11::arg("step"), pybind11::arg("grad_scale"), pybind11::arg("maximize"),
+        pybind11::arg("scale_dev") = pybind11::none(),
+        "flat fused AdamW step; scale_dev: fp32 [1] device tensor multiplied into grad_scale at run time");
+  m.def("adam_step", &adam_step, pybind11::arg("p"), pybind11::arg("g"), pybind11::arg("m"), pybind11::arg("v"),
+        pybind11::arg("shadow"), pybind11::arg("lr"), pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"),
+        pybind11::arg("wd"), pybind11::arg("step"), pybind11::arg("grad_scale"), pybind11::arg("maximize"),
+        pybind11::arg("scale_dev") = pybind11::none(),
+        "flat fused Adam step; scale_dev: fp32 [1] device tensor multiplied into grad_scale at run time");
   m.def("adam_rows_step", &adam_rows_step, "row-split Adam/AdamW step of an embedding table (mode 0: untouched rows, 1: touched rows)");
   m.def("multi_tensor_adam", &multi_tensor_adam);
   m.def("sample_tokens", &sample_tokens, "one token per row of logits [B, V]; top_p / min_p: nucleus and min-p filters "
@@ -371,6 +385,11 @@ PYBIND11_MODULE(penroz_kernels, m) {
   m.def("decode_gemv_q8_pair_plan", &decode_gemv_q8_pair_plan, pybind11::arg("N"), pybind11::arg("K"),
         pybind11::arg("pairs_per_wave") = 0,
         "decode_gemv_q8_pair's launch plan: (pairs per wave, chunks per lane, grid) (host only)");
+  m.def("grad_sumsq_chunks", &grad_sumsq_chunks, "chunks of 16384 floats grad_sumsq writes for n elements (host only)");
+  m.def("grad_sumsq", &grad_sumsq, pybind11::arg("g"), pybind11::arg("part"),
+        "part[c] = fp64 sum of squares of chunk c of the flat fp32 gradient; returns the number of chunks");
+  m.def("grad_clip_finish", &grad_clip_finish, pybind11::arg("part"), pybind11::arg("chunks"), pybind11::arg("max_norm"),
+        pybind11::arg("out"), "out = (norm, min(1, max_norm / (norm + 1e-6))) fp32 [2] from grad_sumsq's partial sums");
   m.def("update_moments", &update_moments, "per-epoch weight-update diagnostics: [n, 2] (std(w - prev), std(w))");
   m.def("gemm_nt_supported", &gemm_nt_supported, "shapes the native NT GEMM takes (M % 256, N % 128, K % 32, K >= 160)");
   m.def("gemm_nt", &gemm_nt, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("bias"), pybind11::arg("out"),

@@ -12,7 +12,9 @@
 // 1 − β2, 1 − lr·wd come from the host in double precision, rounded once: formed in fp32, 1 − β2
 // at β2 = 0.999 is off by 3e-5 relative, which showed as up to 7x the single-step rounding bound
 // against an fp64 step (tests/test_optimizer_kernels_gpu.py).
-// ``grad_scale`` multiplies the gradient first (micro-step averaging).
+// ``grad_scale`` multiplies the gradient first (micro-step averaging). The flat kernel also takes
+// ``scale_dev``, an fp32 [1] device tensor read at run time (the gradient-clipping coefficient of
+// grad_norm.hip): the gradient scale is then grad_scale · *scale_dev, one fp32 multiply.
 #include "common.h"
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -58,7 +60,9 @@ __device__ __forceinline__ void st(V* a, V x) {
 template <int NT>
 __global__ void __launch_bounds__(256) adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v,
-                                                        bf16* __restrict__ shadow, int64_t n, AdamHyper h) {
+                                                        bf16* __restrict__ shadow, int64_t n, AdamHyper h,
+                                                        const float* __restrict__ scale_dev) {
+  if (scale_dev) h.grad_scale *= *scale_dev;  // (null: the host's scale alone, bitwise as before)
   const int64_t n4 = n / 4;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     float4_t pv = ld4<NT>(reinterpret_cast<float4_t*>(p) + i);
@@ -199,7 +203,15 @@ static AdamHyper make_hyper(double lr, double b1, double b2, double eps, double 
 }
 
 static void flat_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v,
-                      c10::optional<torch::Tensor> shadow, const AdamHyper& h) {
+                      c10::optional<torch::Tensor> shadow, const AdamHyper& h,
+                      const c10::optional<torch::Tensor>& scale_dev) {
+  const float* sd = nullptr;
+  if (scale_dev.has_value() && scale_dev->defined()) {
+    TORCH_CHECK(scale_dev->is_cuda() && scale_dev->device() == p.device() && scale_dev->scalar_type() == torch::kFloat32 &&
+                    scale_dev->numel() == 1,
+                "scale_dev must be an fp32 [1] tensor on the parameters' device");
+    sd = scale_dev->data_ptr<float>();
+  }
   for (auto* t : {&p, &g, &m, &v}) {
     TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == torch::kFloat32, "flat buffers must be fp32");
     TORCH_CHECK(t->numel() == p.numel(), "flat buffer sizes differ");
@@ -224,17 +236,19 @@ static void flat_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::
   const int nt = ne && *ne ? std::atoi(ne) : 1;
   auto kern = nt == 1 ? adam_flat_kernel<1> : (nt == 2 ? adam_flat_kernel<2> : adam_flat_kernel<0>);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, at::hip::getCurrentHIPStream(), p.data_ptr<float>(),
-                     g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sp, n, h);
+                     g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), sp, n, h, sd);
 }
 
 void adamw_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow,
-                double lr, double b1, double b2, double eps, double wd, int64_t step, double grad_scale, bool maximize) {
-  flat_step(p, g, m, v, shadow, make_hyper(lr, b1, b2, eps, wd, step, grad_scale, maximize, true));
+                double lr, double b1, double b2, double eps, double wd, int64_t step, double grad_scale, bool maximize,
+                c10::optional<torch::Tensor> scale_dev) {
+  flat_step(p, g, m, v, shadow, make_hyper(lr, b1, b2, eps, wd, step, grad_scale, maximize, true), scale_dev);
 }
 
 void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow,
-               double lr, double b1, double b2, double eps, double wd, int64_t step, double grad_scale, bool maximize) {
-  flat_step(p, g, m, v, shadow, make_hyper(lr, b1, b2, eps, wd, step, grad_scale, maximize, false));
+               double lr, double b1, double b2, double eps, double wd, int64_t step, double grad_scale, bool maximize,
+               c10::optional<torch::Tensor> scale_dev) {
+  flat_step(p, g, m, v, shadow, make_hyper(lr, b1, b2, eps, wd, step, grad_scale, maximize, false), scale_dev);
 }
 
 // mode 0: rows with mask == 0 as for a zero gradient; mode 1: the rows of `rows` whose mask is 1

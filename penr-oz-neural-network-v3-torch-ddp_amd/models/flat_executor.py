@@ -11,7 +11,7 @@ block structure of the model:
   of the backward;
 * the weight-gradient side stream and its buffer-reuse events, the gradient ranges ``zero_grad``
   may leave alone, the per-segment / per-bucket optimizer inside the backward, the gradient
-  reducer's tail and ``optimizer_step``.
+  reducer's tail, ``optimizer_step`` and gradient clipping by global norm (``set_grad_clip``).
 
 A subclass supplies the model: ``PATTERN`` and ``match`` (layer list → spec, or None; the spec has
 ``V``, ``C``, ``head``, ``blocks`` and ``param_dtype``), ``_param_order`` (the parameters per
@@ -32,6 +32,7 @@ from torch import Tensor
 
 from penroz.ops import fused as fused_ops
 from penroz.ops import gemm as gemm_ops
+from penroz.ops import grad_clip as grad_clip_ops
 from penroz.utils.profiling import trace_range
 from penroz.ops import _ext
 
@@ -187,6 +188,9 @@ class FlatExecutor:
         # drawn at first use: which hardware queue a stream gets depends on how many came before
         self._opt_stream = None
         self._hp_stream = None
+        # gradient clipping by global norm (set_grad_clip): the bound, and (norm, coef) on the device
+        self._clip = None
+        self._clip_out = None
 
     def _init_model_state(self):
         """The subclass's own state (Gemma: rope tables, the row-split embedding step)."""
@@ -460,7 +464,41 @@ class FlatExecutor:
 
     def opt_overlap_mode(self) -> str:
         """How the optimizer step overlaps the backward (reported by bench.py in ``comm``)."""
+        if self._clip is not None:
+            return "after-backward-clipped"
         return self._opt_mode or "none"
+
+    def set_grad_clip(self, max_norm: float | None):
+        """Clip the gradients by their global L2 norm in every following step (``ops/grad_clip.py``
+        has the definition; None: off, the schedule and the results of the unclipped executor).
+
+        The norm exists only once every gradient is final and all-reduced, so with a bound the
+        optimizer does not run inside the backward: ``train_micro_step(fuse_optimizer=True)`` starts
+        no per-segment, per-bucket or row-split step, and ``optimizer_step`` waits for the
+        outstanding buckets, computes (norm, coef) over the whole flat gradient buffer on the
+        device, and applies the flat fused step with the coefficient read from the device; the
+        transposed dgrad copies are rebuilt at the next step's start. Without a flat fused optimizer
+        the gradient buffer is multiplied by the coefficient in place before ``opt.step()``.
+
+        Unlike torch's, the flat fused step does not write the gradient: ``flat_grad`` (and the
+        dashboard's gradient statistics) keep the unclipped values. ``last_grad_norm`` /
+        ``last_clip_coef`` are device views of the last step's result; nothing here reads them on
+        the host."""
+        self._clip = grad_clip_ops.check_max_grad_norm(max_norm)
+        if self._clip is None:
+            self._clip_out = None
+        elif self._clip_out is None:
+            self._clip_out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=self.device)
+
+    @property
+    def last_grad_norm(self) -> Tensor | None:
+        """The last clipped step's pre-clip gradient norm, fp32 [] on the device (None: off)."""
+        return None if self._clip_out is None else self._clip_out[0]
+
+    @property
+    def last_clip_coef(self) -> Tensor | None:
+        """The last clipped step's coefficient min(1, max_norm / (norm + 1e-6)), fp32 [] on the device."""
+        return None if self._clip_out is None else self._clip_out[1]
 
     def end_training(self):
         if self.reducer is not None:
@@ -684,10 +722,11 @@ class FlatExecutor:
         process): the fused AdamW updates each parameter segment inside the backward, on the side
         stream, as soon as that segment's gradients are final — the optimizer pass overlaps the
         rest of the backward instead of running after it (``optimizer_step`` then has nothing left
-        to do). ``PENROZ_OPT_IN_BWD=0`` keeps the separate step."""
+        to do). ``PENROZ_OPT_IN_BWD=0`` keeps the separate step, and so does gradient clipping
+        (``set_grad_clip``): the global norm needs every gradient first."""
         self._opt_apply = None
         self._opt_bucketed = False
-        if (fuse_optimizer and sync and not capture and self._opt_flat
+        if (fuse_optimizer and sync and not capture and self._opt_flat and self._clip is None
                 and os.environ.get("PENROZ_OPT_IN_BWD", "1") != "0"):
             if self.reducer is None:
                 self._opt_apply = self.model.optimizer.begin_flat_ranges()
@@ -762,6 +801,17 @@ class FlatExecutor:
         opt = self.model.optimizer
         if self._opt_done:  # applied segment by segment inside the backward
             self._opt_done = False
+            return
+        if self._clip is not None:
+            with trace_range("optimizer"):
+                self.wait_gradients()  # every outstanding bucket: the norm is over the averaged gradient
+                out = grad_clip_ops.grad_clip_coef(self.flat_grad, self._clip, out=self._clip_out)
+                if self._opt_flat:
+                    opt.step(scale_dev=out[1:2])
+                else:
+                    self.flat_grad.mul_(out[1])
+                    opt.step()
+                    self.refresh_shadow()
             return
         with trace_range("optimizer"):
             if self._reduce_pending:

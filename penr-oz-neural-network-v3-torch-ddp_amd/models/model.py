@@ -50,6 +50,7 @@ from penroz.ops import ragged as ragged_ops
 from penroz.ops import sampling as samp_ops
 from penroz.ops import stopping as stop_ops
 from penroz.ops import fused as fused_ops
+from penroz.ops import grad_clip as grad_clip_ops
 from penroz.ops import weight_quant as wq_ops
 from penroz.parallel import dist as ddp
 from penroz.parallel.launcher import maybe_inject_fault
@@ -940,7 +941,8 @@ class NeuralNetworkModel(nn.Module):
     # ------------------------------------------------------------------ training
     @classmethod
     def train_model_on_device(cls, model_id: str, device: str, dataset_id: str, shard: int,
-                              epochs: int, batch_size: int, block_size: int, step_size: int):
+                              epochs: int, batch_size: int, block_size: int, step_size: int,
+                              max_grad_norm: float | None = None):
         if ddp.is_ddp():
             ddp.reconfig_logging()
             log.info(f"DDP local rank {ddp.ddp_local_rank()} - training model {model_id} on device {device} "
@@ -956,7 +958,8 @@ class NeuralNetworkModel(nn.Module):
                 if isinstance(v, Tensor) and k != "step":
                     state[k] = v.to(actual)
         try:
-            model.train_model(dataset_id, shard, epochs, batch_size, block_size, step_size)
+            model.train_model(dataset_id, shard, epochs, batch_size, block_size, step_size,
+                              max_grad_norm=max_grad_norm)
         finally:
             ckpt.wait_flushes()
             if ddp.is_ddp() and dist.is_initialized():
@@ -1012,8 +1015,13 @@ class NeuralNetworkModel(nn.Module):
         return self._executor
 
     def train_model(self, dataset_id: str, shard: int, epochs: int, batch_size: int, block_size: int,
-                    step_size: int):
+                    step_size: int, max_grad_norm: float | None = None):
+        """``max_grad_norm``: clip the gradients of every optimizer step by their global L2 norm
+        (``ops/grad_clip.py``; None: off, or the process default ``PENROZ_MAX_GRAD_NORM``). It
+        belongs to this call — neither the model nor the checkpoint keeps it. With clipping on,
+        each progress record carries ``grad_norm``, the pre-clip norm."""
         from penroz.utils.loaders import Loader
+        max_grad_norm = grad_clip_ops.check_max_grad_norm(max_grad_norm)
         device = next(self.parameters()).device
         engine = self._engine(device)
         if ddp.master_proc():
@@ -1035,7 +1043,7 @@ class NeuralNetworkModel(nn.Module):
             last_serialized = time.time()
 
         distributed = ddp.use_ddp(device.type) and dist.is_initialized()
-        runner = _make_runner(self, engine, device, distributed)
+        runner = _make_runner(self, engine, device, distributed, max_grad_norm)
         self.train()
 
         copy_stream = None
@@ -1086,7 +1094,7 @@ class NeuralNetworkModel(nn.Module):
 
         def finish(pd):
             """Record one finished epoch (waits for that epoch's events only)."""
-            ep, ev0, ev1, cost_h, rat, t_host = pd
+            ep, ev0, ev1, cost_h, rat, t_host, norm_h = pd
             if ev1 is not None:
                 ev1.synchronize()
                 secs = max(ev0.elapsed_time(ev1) / 1e3, 1e-9)
@@ -1101,6 +1109,8 @@ class NeuralNetworkModel(nn.Module):
                     "cost": progress_cost,
                     "weight_upd_ratio": diagnostics.finish_update_ratios(rat) if rat is not None else [],
                 })
+                if norm_h is not None:  # gradient clipping on: the pre-clip global norm
+                    self.progress[-1]["grad_norm"] = float(norm_h.item())
             log.info(f"Model {self.model_id}: Training Epoch {ep + 1}, Cost: {progress_cost:.4f}, "
                      f"Duration: {secs:.2f} secs, Speed: {buffer_size / secs:.2f} tokens/sec")
 
@@ -1141,6 +1151,7 @@ class NeuralNetworkModel(nn.Module):
             if distributed:
                 ddp.ddp_all_reduce(cost)
             runner.step()
+            norm = runner.grad_norm()  # a device scalar (None: clipping off), read like the cost
             if lazy:
                 if ddp.master_proc():
                     # the ratios of this epoch's update, on the device behind its step; host copies
@@ -1148,17 +1159,22 @@ class NeuralNetworkModel(nn.Module):
                     rat = diagnostics.start_update_ratios(prev, self._weights) if record and prev else None
                     cost_h = torch.empty((), dtype=torch.float32, pin_memory=True)
                     cost_h.copy_(cost, non_blocking=True)
+                    norm_h = None
+                    if norm is not None:
+                        norm_h = torch.empty((), dtype=torch.float32, pin_memory=True)
+                        norm_h.copy_(norm.detach(), non_blocking=True)
                     ev1 = torch.cuda.Event(enable_timing=True)
                     ev1.record()
                     if pend is not None:
                         finish(pend)
-                    pend = (epoch, ev0, ev1, cost_h, rat, None)
+                    pend = (epoch, ev0, ev1, cost_h, rat, None, norm_h)
             else:
                 if device.type == "cuda":
                     torch.cuda.synchronize()
                 if ddp.master_proc():
                     rat = diagnostics.start_update_ratios(prev, self._weights) if record and prev else None
-                    finish((epoch, None, None, cost.detach().cpu(), rat, time.time() - t0))
+                    finish((epoch, None, None, cost.detach().cpu(), rat, time.time() - t0,
+                            norm.detach().float().cpu() if norm is not None else None))
             if ddp.master_proc() and long_training:
                 if pend is not None:
                     finish(pend)
@@ -1201,10 +1217,13 @@ def _optim_state_to_cpu(sd: dict) -> dict:
 class _GenericRunner:
     """Module forward + autograd backward (+ our bucketed reducer under DDP)."""
 
-    def __init__(self, model: NeuralNetworkModel, device, distributed: bool, reference: bool = False):
+    def __init__(self, model: NeuralNetworkModel, device, distributed: bool, reference: bool = False,
+                 max_grad_norm: float | None = None):
         self.model = model
         self.device = device
         self.reference = reference
+        self.max_grad_norm = max_grad_norm
+        self._grad_norm = None  # the last step's pre-clip norm (torch's own tensor)
         self.amp = NeuralNetworkModel._autocast(device)
         # fp16 autocast needs loss scaling (reference neural_net_model.py:573-575, 650-675)
         self.scaler = torch.amp.GradScaler("cuda") if NeuralNetworkModel.amp_dtype(device) == torch.float16 else None
@@ -1250,12 +1269,23 @@ class _GenericRunner:
             self.reducer.finish()
         return scaled.detach().float()
 
+    def _clip(self):
+        self._grad_norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm)
+
+    def grad_norm(self):
+        return self._grad_norm if self.max_grad_norm is not None else None
+
     def step(self):
         if self.scaler is None:
+            if self.max_grad_norm is not None:
+                self._clip()
             self.model.optimizer.step()
             return
         # unscale + inf/nan check, skipped step on overflow; the captured activation gradients
         # (dashboard stats) were scaled too: unscale them with the scale of this step
+        if self.max_grad_norm is not None:  # the norm is of the unscaled gradients
+            self.scaler.unscale_(self.model.optimizer)
+            self._clip()
         self.scaler.step(self.model.optimizer)
         inv = 1.0 / self.scaler.get_scale()
         for a in self._acts:
@@ -1276,9 +1306,11 @@ class _GenericRunner:
 
 
 class _FusedRunner:
-    def __init__(self, model: NeuralNetworkModel, device, distributed: bool):
+    def __init__(self, model: NeuralNetworkModel, device, distributed: bool, max_grad_norm: float | None = None):
         self.model = model
+        self.max_grad_norm = max_grad_norm
         self.exec = model._get_executor(device)
+        self.exec.set_grad_clip(max_grad_norm)
         self.exec.setup_training(distributed)
 
     def zero_grad(self):
@@ -1292,6 +1324,9 @@ class _FusedRunner:
     def step(self):
         self.exec.optimizer_step()
 
+    def grad_norm(self):
+        return self.exec.last_grad_norm
+
     def grad_of(self, p):
         return self.exec.grad(p)
 
@@ -1302,9 +1337,19 @@ class _FusedRunner:
         self.exec.end_training()
 
 
-def _make_runner(model, engine, device, distributed):
+def _make_runner(model, engine, device, distributed, max_grad_norm=None):
+    """The step runner of ``engine``. ``max_grad_norm`` None takes the process default
+    ``PENROZ_MAX_GRAD_NORM`` (unset or empty: no clipping), checked like the argument."""
     from penroz.ops import _ext
+    if max_grad_norm is None:
+        env = os.environ.get("PENROZ_MAX_GRAD_NORM", "").strip()
+        if env:
+            try:
+                max_grad_norm = float(env)
+            except ValueError:
+                raise ValueError(f"PENROZ_MAX_GRAD_NORM must be a finite number > 0, got {env!r}") from None
+    max_grad_norm = grad_clip_ops.check_max_grad_norm(max_grad_norm)
     _ext.FORCE_TORCH = engine == "reference"
     if engine == "fused":
-        return _FusedRunner(model, device, distributed)
-    return _GenericRunner(model, device, distributed, reference=(engine == "reference"))
+        return _FusedRunner(model, device, distributed, max_grad_norm)
+    return _GenericRunner(model, device, distributed, reference=(engine == "reference"), max_grad_norm=max_grad_norm)

@@ -85,16 +85,20 @@ class _FusedMixin:
                                 and p.dtype in (torch.float32, torch.float64, torch.bfloat16) for p in ps)
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0):
-        """One optimizer step; ``grad_scale`` multiplies every gradient (e.g. 1/num_steps)."""
+    def step(self, closure=None, grad_scale: float = 1.0, scale_dev: Tensor | None = None):
+        """One optimizer step; ``grad_scale`` multiplies every gradient (e.g. 1/num_steps).
+        ``scale_dev`` (fp32 [1] on the device, e.g. a clipping coefficient) multiplies it once more,
+        read by the kernel at run time: flat mode only, any other path raises."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         if len(self.param_groups) == 1 and self._flat is not None and \
                 {id(p) for p in self.param_groups[0]["params"]} == self._flat["ids"]:
-            self._step_flat(self.param_groups[0], grad_scale)
+            self._step_flat(self.param_groups[0], grad_scale, scale_dev=scale_dev)
             return loss
+        if scale_dev is not None:
+            raise RuntimeError("scale_dev needs the flat fused step (attach_flat, one parameter group)")
         fallback = []
         for group in self.param_groups:
             if self._group_fused_ok(group):
@@ -129,7 +133,7 @@ class _FusedMixin:
         return lr, float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), \
             bool(group.get("maximize", False))
 
-    def _step_flat(self, group, grad_scale, ranges=None):
+    def _step_flat(self, group, grad_scale, ranges=None, scale_dev=None):
         f = self._flat
         lr, b1, b2, eps, wd, maximize = self._hyper(group)
         step = None
@@ -139,19 +143,21 @@ class _FusedMixin:
             step = int(st["step"].item()) if step is None else step
         fn = fused_ops.adamw_step if self._decoupled else fused_ops.adam_step
         if ranges is None:
-            fn(f["param"], f["grad"], f["m"], f["v"], f["shadow"], lr, b1, b2, eps, wd, step, grad_scale, maximize)
+            fn(f["param"], f["grad"], f["m"], f["v"], f["shadow"], lr, b1, b2, eps, wd, step, grad_scale, maximize,
+               scale_dev)
             return
         sh = f["shadow"]
         for r in ranges:  # (s, e) pairs, or a callable returning one (it may wait for the range first)
             s, e = r() if callable(r) else r
             fn(f["param"][s:e], f["grad"][s:e], f["m"][s:e], f["v"][s:e], sh[s:e] if sh is not None else None,
-               lr, b1, b2, eps, wd, step, grad_scale, maximize)
+               lr, b1, b2, eps, wd, step, grad_scale, maximize, scale_dev)
 
-    def begin_flat_ranges(self, grad_scale: float = 1.0):
+    def begin_flat_ranges(self, grad_scale: float = 1.0, scale_dev: Tensor | None = None):
         """Start a flat step whose ranges are applied later, one call per range, e.g. each
         parameter segment as soon as its gradients are final inside the backward. Returns
         ``apply(s, e)`` or None when the flat path does not apply. The step counter advances now,
-        once; the caller must cover the flat buffer exactly once before the next step."""
+        once; the caller must cover the flat buffer exactly once before the next step. With a
+        ``scale_dev`` (see :meth:`step`) the row-split ``apply.rows`` raises: its kernel has none."""
         if not (len(self.param_groups) == 1 and self._flat is not None
                 and {id(p) for p in self.param_groups[0]["params"]} == self._flat["ids"]):
             return None
@@ -167,23 +173,25 @@ class _FusedMixin:
 
         def apply(s: int, e: int):
             fn(f["param"][s:e], f["grad"][s:e], f["m"][s:e], f["v"][s:e], sh[s:e] if sh is not None else None,
-               lr, b1, b2, eps, wd, step, grad_scale, maximize)
+               lr, b1, b2, eps, wd, step, grad_scale, maximize, scale_dev)
 
         def apply_rows(s: int, e: int, C: int, mask, rows, mode: int):
             """[s, e) as an embedding table of width C: fused_ops.adam_rows_step (same math)."""
+            if scale_dev is not None:
+                raise RuntimeError("the row-split Adam step takes no scale_dev")
             fused_ops.adam_rows_step(f["param"][s:e], f["grad"][s:e], f["m"][s:e], f["v"][s:e],
                                      sh[s:e] if sh is not None else None, C, mask, rows, mode, lr, b1, b2, eps, wd,
                                      step, grad_scale, maximize, self._decoupled)
         apply.rows = apply_rows
         return apply
 
-    def flat_step_ranges(self, ranges, grad_scale: float = 1.0) -> bool:
+    def flat_step_ranges(self, ranges, grad_scale: float = 1.0, scale_dev: Tensor | None = None) -> bool:
         """Flat step applied range by range (``ranges`` must cover the flat buffer exactly once);
         False (nothing done) when the flat path does not apply."""
         if not (len(self.param_groups) == 1 and self._flat is not None
                 and {id(p) for p in self.param_groups[0]["params"]} == self._flat["ids"]):
             return False
-        self._step_flat(self.param_groups[0], grad_scale, ranges)
+        self._step_flat(self.param_groups[0], grad_scale, ranges, scale_dev)
         return True
 
     def _step_list(self, group, grad_scale):

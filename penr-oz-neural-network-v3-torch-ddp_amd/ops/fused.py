@@ -118,11 +118,14 @@ def reference_adamw(p, g, m, v, lr, b1, b2, eps, wd, step):
 
 def adamw_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor,
                shadow: Tensor | None, lr: float, beta1: float, beta2: float, eps: float,
-               weight_decay: float, step: int, grad_scale: float = 1.0, maximize: bool = False):
-    """Flat-buffer AdamW (all fp32 [numel]); ``shadow`` (bf16 [numel]) refreshed when given."""
+               weight_decay: float, step: int, grad_scale: float = 1.0, maximize: bool = False,
+               scale_dev: Tensor | None = None):
+    """Flat-buffer AdamW (all fp32 [numel]); ``shadow`` (bf16 [numel]) refreshed when given.
+    ``scale_dev`` (fp32 [1] on the device, e.g. the clipping coefficient of ``ops/grad_clip.py``)
+    is read by the kernel when it runs and multiplied into ``grad_scale``."""
     kernels().adamw_step(params, grads, exp_avg, exp_avg_sq, shadow, float(lr), float(beta1),
                          float(beta2), float(eps), float(weight_decay), int(step), float(grad_scale),
-                         bool(maximize))
+                         bool(maximize), scale_dev)
 
 
 def adam_rows_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, shadow: Tensor | None,
@@ -138,11 +141,12 @@ def adam_rows_step(params: Tensor, grads: Tensor, exp_avg: Tensor, exp_avg_sq: T
 
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, shadow, lr, beta1, beta2, eps, weight_decay, step,
-              grad_scale: float = 1.0, maximize: bool = False):
-    """Flat-buffer Adam (L2 weight decay added to the gradient, torch ``Adam`` semantics)."""
+              grad_scale: float = 1.0, maximize: bool = False, scale_dev: Tensor | None = None):
+    """Flat-buffer Adam (L2 weight decay added to the gradient, torch ``Adam`` semantics);
+    ``scale_dev`` as in :func:`adamw_step`."""
     kernels().adam_step(params, grads, exp_avg, exp_avg_sq, shadow, float(lr), float(beta1),
                         float(beta2), float(eps), float(weight_decay), int(step), float(grad_scale),
-                        bool(maximize))
+                        bool(maximize), scale_dev)
 
 
 # --------------------------------------------------------------------------- reductions

@@ -13,6 +13,8 @@ MI355X-first differences:
     every request (``/generate`` uses the preallocated KV cache + decode-attention kernel);
   * ``/train/`` runs the launcher (one worker per GPU, RCCL) and checks its exit code: a failed
     run marks the model ``Error`` instead of leaving it ``Training`` (reference bug 9);
+    ``max_grad_norm`` clips the gradients by global norm (``ops/grad_clip.py``; invalid values
+    are a 400 before any worker starts) and adds ``grad_norm`` to the progress records;
   * ``/progress/`` reads a small sidecar JSON instead of ``torch.load``-ing the checkpoint.
 """
 from __future__ import annotations
@@ -37,6 +39,7 @@ from pydantic import BaseModel, Field, StrictInt
 
 from penroz.models.mapper import Mapper
 from penroz.models.model import NeuralNetworkModel
+from penroz.ops import grad_clip as grad_clip_ops
 from penroz.ops import logit_bias as bias_ops
 from penroz.ops import stopping as stop_ops
 from penroz.ops import weight_quant as wq_ops
@@ -106,7 +109,7 @@ class DownloadDatasetRequest(DatasetRequest, TokenizerRequest):
     shard_size: int = Field(..., examples=[100000], description="Tokens per shard")
 
 
-class TrainingRequest(ModelOnDeviceRequest, DatasetRequest):
+class BatchedRunRequest(ModelOnDeviceRequest, DatasetRequest):
     shard: int = Field(..., examples=[1], description="Dataset shard to begin from")
     epochs: int = Field(..., examples=[4], description="Number of training epochs")
     batch_size: int = Field(..., examples=[2], description="Sequences per rank per micro-step")
@@ -114,7 +117,16 @@ class TrainingRequest(ModelOnDeviceRequest, DatasetRequest):
     step_size: int = Field(..., examples=[2], description="Sequences per accumulation step")
 
 
-class EvaluateRequest(TrainingRequest):
+class TrainingRequest(BatchedRunRequest):
+    # (bool listed so that ``true`` reaches the check below as a bool and gets its 400, not a silent 1.0)
+    max_grad_norm: float | bool | None = Field(
+        None, examples=[1.0], json_schema_extra={"anyOf": [{"type": "number", "exclusiveMinimum": 0}, {"type": "null"}]},
+        description="Clip the gradients of every optimizer step by their global L2 norm "
+                    "(torch.nn.utils.clip_grad_norm_): a finite number > 0; null: off. With a value, every "
+                    "progress record carries grad_norm, the pre-clip norm")
+
+
+class EvaluateRequest(BatchedRunRequest):
     target_dataset_id: str | None = Field(None, examples=[None], description="Separate target dataset (optional)")
     shard: int = Field(..., examples=[0])
     epochs: int = Field(..., examples=[2])
@@ -546,11 +558,14 @@ def _mark_failed(model_id: str, rank: int, code: int):
 
 
 def run_training_job(model_id: str, device: str, dataset_id: str, shard: int, epochs: int, batch_size: int,
-                     block_size: int, step_size: int) -> int:
+                     block_size: int, step_size: int, max_grad_norm: float | None = None) -> int:
     """Blocking: launch the distributed workers and return the launcher's exit code."""
+    args = (model_id, device, dataset_id, shard, epochs, batch_size, block_size, step_size)
+    if max_grad_norm is not None:  # (absent: the workers get exactly the arguments they always got)
+        args += (max_grad_norm,)
     code = launcher.launch_single_node_ddp(
-        model_id, device, NeuralNetworkModel.train_model_on_device, model_id, device, dataset_id, shard, epochs,
-        batch_size, block_size, step_size, on_failure=lambda r, c: _mark_failed(model_id, r, c))
+        model_id, device, NeuralNetworkModel.train_model_on_device, *args,
+        on_failure=lambda r, c: _mark_failed(model_id, r, c))
     _evict(model_id)
     return code
 
@@ -558,6 +573,10 @@ def run_training_job(model_id: str, device: str, dataset_id: str, shard: int, ep
 @app.put("/train/")
 async def train_model(body: TrainingRequest = Body(...)):
     model_id = body.model_id
+    try:  # before any worker is launched
+        max_grad_norm = grad_clip_ops.check_max_grad_norm(body.max_grad_norm)
+    except ValueError as e:
+        raise HTTPException(status_code=400, detail=f"Value error occurred: {e}")
     lock = model_locks.setdefault(model_id, Lock())
     if lock.locked():
         raise HTTPException(status_code=409, detail=f"Training already in progress for model {model_id}.")
@@ -565,7 +584,8 @@ async def train_model(body: TrainingRequest = Body(...)):
     async def _launch():
         async with lock:
             code = await run_in_threadpool(run_training_job, model_id, body.device, body.dataset_id, body.shard,
-                                           body.epochs, body.batch_size, body.block_size, body.step_size)
+                                           body.epochs, body.batch_size, body.block_size, body.step_size,
+                                           max_grad_norm)
             log.info(f"Distributed training for model {model_id} finished with exit code {code}")
 
     create_task(_launch())
