@@ -32,20 +32,20 @@ between steps lives on the device:
 * repetition / presence / frequency penalties (``ops/penalties.py``, ``csrc/kernels/logit_penalty.hip``)
   act on the logits between the lm_head and the sampler, from count tables the decoder owns; their
   values are read from the device. The step with that kernel and the step without it are two graphs
-  of one decoder (``GraphDecoder.set_penalties``): same KV cache, same program.
+  of one decoder (``GraphDecoder.configure``, ``StepMode``): same KV cache, same program.
 * per-token log-probabilities (``ops/logprobs.py``, ``csrc/kernels/token_logprobs.hip``) are computed
   behind the sampler from the logits it read and the token it wrote, into burst buffers the decoder
-  owns; ``n`` is read from the device. With them the step is another graph of the same decoder
-  (``GraphDecoder.set_logprobs``): by (penalised, log-probabilities on).
+  owns; ``n`` is read from the device. With them the step is another graph of the same decoder: by
+  (penalised, log-probabilities on).
 * stop sequences (``ops/stopping.py``, ``csrc/kernels/stop_check.hip``) are checked by the step's last
   kernel against the token just chosen: per-row finish state on the device, finished rows frozen on
   their finishing token in the next step's input and the burst buffer. The stop set is read from the
-  device; the step with the check is a further graph of the decoder (``GraphDecoder.set_stop``): up to
-  eight, by (penalised, log-probabilities on, stop check on).
+  device; the step with the check is a further graph of the decoder: up to eight, by (penalised,
+  log-probabilities on, stop check on).
 * logit bias, banned and allowed tokens and ``min_tokens`` (``ops/logit_bias.py``,
   ``csrc/kernels/logit_bias.hip``) rewrite the logits behind the penalties, in front of the sampler and
   the log-probabilities, in one launch that reads its entries, its mask and ``t`` from the device. The
-  graph mode gains a fourth element (``GraphDecoder.set_logit_bias``): off, entries, or entries + mask —
+  graph mode gains a fourth element: off, entries, or entries + mask —
   the last two differ in their grid, so they are separate graphs.
 
 * ragged batches (``ops/ragged.py``): a ``GraphDecoder`` with ``ragged=True`` keeps ``pos_t`` / ``len_t`` as
@@ -70,6 +70,7 @@ import gc
 import logging
 import os
 import weakref
+from typing import NamedTuple
 
 import torch
 from torch import Tensor
@@ -712,6 +713,14 @@ def applicable(model) -> bool:
     return True
 
 
+class StepMode(NamedTuple):
+    """Which optional kernels a decoder's step runs; one captured graph per mode, captured on first use."""
+    penalised: bool = False
+    logprobs: bool = False
+    stop: bool = False
+    bias_form: str = "off"  # the logit-bias rewrite: "off", "entries" or "mask" (entries and the allowed mask)
+
+
 class GraphDecoder:
     """Static decode state + the captured step graph for ``rows`` sequences."""
 
@@ -757,25 +766,24 @@ class GraphDecoder:
             else:
                 _log_q8_unused(rows, self.program)
         self._done_t = torch.zeros(1, dtype=torch.int32, device=self.device)  # sample_step's arrival counter
-        # logit penalties: the state (made when first asked for; its buffers are static), whether the
-        # step applies them, and the captured graph of the mode ``graph`` does not hold right now
+        # the options' states, each made by the first ``configure`` that asks for it (their buffers are
+        # static): logit penalties, per-token log-probabilities, stop sequences, logit bias / banned /
+        # allowed tokens / min_tokens
         self.penalties: pen_ops.PenaltyState | None = None
-        self._penalised = False
-        self._count_new = True  # (False during a capture's warm-up step: its token is not a real one)
-        # per-token log-probabilities: the buffers (made when first asked for), whether the step computes
-        # them, and what the last run() left: (lp [rows, n_steps], top_id, top_lp [rows, n_steps, 20]) or None
         self.logprobs: lp_ops.LogprobState | None = None
-        self._lp_on = False
-        self.last_logprobs: tuple[Tensor, Tensor, Tensor] | None = None
-        # stop sequences: the state (made when first asked for) and whether the step ends with the check
         self.stop: stop_ops.StopState | None = None
-        self._stop_on = False
-        # logit bias / banned / allowed tokens / min_tokens: the state (made when first asked for) and the
-        # form of the step's rewrite: "off", "entries" or "mask" (entries and the allowed mask)
         self.bias: bias_ops.BiasState | None = None
-        self._bias_form = "off"
-        # (penalised, log-probabilities on, stop check on, bias form) -> the captured graphs ``graph`` is not
-        self._graphs: dict = {}
+        self._count_new = True  # (False during a capture's warm-up step: its token is not a real one)
+        # what the last run() left: (lp [rows, n_steps], top_id, top_lp [rows, n_steps, 20]) or None
+        self.last_logprobs: tuple[Tensor, Tensor, Tensor] | None = None
+        # which of them the step runs — ``graph`` is this mode's — and the other modes' captured graphs
+        self.mode = StepMode()
+        self._graphs: dict[StepMode, torch.cuda.CUDAGraph | None] = {}
+
+    _penalised = property(lambda self: self.mode.penalised)
+    _lp_on = property(lambda self: self.mode.logprobs)
+    _stop_on = property(lambda self: self.mode.stop)
+    _bias_form = property(lambda self: self.mode.bias_form)
 
     # ------------------------------------------------------------------ cache attachment
     def attach(self):
@@ -861,62 +869,37 @@ class GraphDecoder:
         """Once per generate call: the seed every burst of this call derives from."""
         self.run_seed = int(run_seed) & (2 ** 64 - 1)
 
-    def set_penalties(self, values: tuple[float, float, float] | None):
-        """Once per generate call: ``ops.penalties.check_penalties``' result. None: ``run()`` replays
-        the step without the penalty kernel; values: the step with it, which reads them from the
-        device — other values replay the same graph. Each of the two graphs is captured on first use."""
-        on = values is not None
-        if on:
+    def configure(self, opts):
+        """Once per generate call, with its checked options (``ops.decode_options.DecodeOptions``): makes
+        the states the call needs and this decoder does not have yet, loads the call's values into them,
+        and makes ``graph`` the captured step of the call's ``StepMode`` (None: captured on first use).
+        An option that is off costs the step no kernel. The step reads every value from the device, so
+        other penalty values, another n, another stop set, other bias entries, another allowed set and
+        another ``min_tokens`` replay the same graph; with and without an allowed set are two modes (their
+        grids differ). The caller begins ``penalties`` / ``stop`` once per call and reads ``stop.read()``
+        after a burst."""
+        if opts.penalties is not None:
             if self.penalties is None:
                 self.penalties = pen_ops.PenaltyState()
-            self.penalties.set_params(*values)
-        self._select(on, self._lp_on, self._stop_on)
-
-    def set_logprobs(self, n: int | None):
-        """Once per generate call: ``ops.logprobs.check_logprobs``' result. None: ``run()`` replays the
-        step as it is without them, no kernel more; a number: the step with the two log-probability
-        kernels, which read ``n`` from the device — other values replay the same graph."""
-        on = n is not None
-        if on:
+            self.penalties.set_params(*opts.penalties)
+        if opts.logprobs is not None:
             if self.logprobs is None:
                 self.logprobs = lp_ops.LogprobState(self.rows, self.capacity, self.device)
-            self.logprobs.set_n(n)
-        self._select(self._penalised, on, self._stop_on)
-
-    def set_stop(self, stop: list[list[int]] | None):
-        """Once per generate call: ``ops.stopping.check_stop``'s result. None: ``run()`` replays the step
-        as it is without the check, no kernel more; sequences: the step that ends with the stop check,
-        which reads them from the device — another set replays the same graph. The caller runs
-        ``stop.begin()`` once per call and reads ``stop.read()`` after a burst."""
-        on = stop is not None
-        if on:
+            self.logprobs.set_n(opts.logprobs)
+        if opts.stop is not None:
             if self.stop is None:
                 self.stop = stop_ops.StopState(self.rows, self.device)
-            self.stop.set_stop(stop)
-        self._select(self._penalised, self._lp_on, on)
-
-    def set_logit_bias(self, canonical: bias_ops.Canonical | None):
-        """Once per generate call: ``ops.logit_bias.check_logit_bias``' result. None: ``run()`` replays the
-        step as it is without the rewrite, no kernel more; a canonical form: the step with the rewrite, which
-        reads the entries, the allowed mask and ``min_tokens`` from the device — other values, another set
-        and another ``min_tokens`` replay the same graph. With and without an allowed set are two graphs
-        (their grids differ), each captured on first use."""
-        if canonical is not None:
+            self.stop.set_stop(opts.stop)
+        if opts.bias is not None:
             if self.bias is None:
                 self.bias = bias_ops.BiasState(self.device)
-            self.bias.set(canonical)
-        self._select(self._penalised, self._lp_on, self._stop_on,
-                     "off" if canonical is None else self.bias.form)
-
-    def _select(self, penalised: bool, lp_on: bool, stop_on: bool, bias_form: str | None = None):
-        """Make ``graph`` the captured step of this mode (None: captured on first use). ``bias_form``
-        None: as it is."""
-        bias_form = self._bias_form if bias_form is None else bias_form
-        mode = (self._penalised, self._lp_on, self._stop_on, self._bias_form)
-        if (penalised, lp_on, stop_on, bias_form) != mode:
-            self._graphs[mode] = self.graph
-            self.graph = self._graphs.pop((penalised, lp_on, stop_on, bias_form), None)
-            self._penalised, self._lp_on, self._stop_on, self._bias_form = penalised, lp_on, stop_on, bias_form
+            self.bias.set(opts.bias)
+        mode = StepMode(opts.penalties is not None, opts.logprobs is not None, opts.stop is not None,
+                        "off" if opts.bias is None else self.bias.form)
+        if mode != self.mode:
+            self._graphs[self.mode] = self.graph
+            self.graph = self._graphs.pop(mode, None)
+            self.mode = mode
 
     def _burst_seed(self, start: int) -> int:
         v = (self.run_seed + self._HASH_STEP * int(start)) & (2 ** 64 - 1)
@@ -1027,7 +1010,10 @@ def _log_q8_unused(rows: int, program) -> None:
 
 
 def ragged_program_ok(model) -> bool:
-    """A ragged step is an explicit decode program's (the module forward has one position for all rows)."""
+    """A ragged step is an explicit decode program's (the module forward has one position for all rows),
+    which the built kernels run."""
+    if not _ext.available():
+        return False
     p = next(model.parameters())
     key = (p.data_ptr(), p.dtype, DECODE_PROGRAM)
     hit = model.__dict__.get("_ragged_program_ok")
@@ -1053,9 +1039,11 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
     format in effect for ``weight_quant`` — as ``ops.weight_quant.resolve`` returned it); None when the
     model does not qualify (CPU, no attention, RoPE head_dim without a decode kernel) or ``PENROZ_GRAPH_DECODE=0``
     — and, for a ragged decoder, when the model has no decode program or the kernels are not built."""
+    # (these two are the only ways to None; ``NeuralNetworkModel._ragged_fallback`` names them to a ragged call
+    # before its options are checked, so a third belongs there too: tests/test_ragged.py ties the two together)
     if not applicable(model):
         return None
-    if ragged and not (_ext.available() and ragged_program_ok(model)):
+    if ragged and not ragged_program_ok(model):
         return None
     p = next(model.parameters())
     # weights identity AND version: in-place updates (training) re-capture, so nothing captured
@@ -1085,3 +1073,10 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
             cache.pop(next(iter(cache)))
         cache[base + (dec.weight_quant,)] = dec
     return dec
+
+
+def decoder_for(model, rows: int, block_size: int, opts, ragged: bool = False) -> GraphDecoder | None:
+    """``get_decoder`` for a generate call's checked options (``ops.decode_options.DecodeOptions``)."""
+    ragged = {"ragged": True} if ragged else {}  # (a rectangular call's lookup is what it always was)
+    return get_decoder(model, rows, block_size, opts.temperature, opts.top_k, opts.top_p, opts.min_p,
+                       opts.weight_quant, **ragged)

@@ -31,6 +31,7 @@ import os
 import random
 import time
 from contextlib import nullcontext
+from dataclasses import replace
 from datetime import datetime as dt
 from typing import Optional, Tuple
 
@@ -43,15 +44,12 @@ import torch.distributed as dist
 from penroz.models.kv_cache import KVCache, create_kv_cache
 from penroz.models.layers import CausalSelfAttention, PositionEmbedding, SoftmaxOnLast
 from penroz.models.mapper import Mapper
-from penroz.ops import logit_bias as bias_ops
 from penroz.ops import logprobs as lp_ops
-from penroz.ops import penalties as pen_ops
 from penroz.ops import ragged as ragged_ops
-from penroz.ops import sampling as samp_ops
 from penroz.ops import stopping as stop_ops
+from penroz.ops.decode_options import KEYWORDS, DecodeCall, DecodeOptions, check_options
 from penroz.ops import fused as fused_ops
 from penroz.ops import grad_clip as grad_clip_ops
-from penroz.ops import weight_quant as wq_ops
 from penroz.parallel import dist as ddp
 from penroz.parallel.launcher import maybe_inject_fault
 from penroz.utils import checkpoint as ckpt
@@ -66,6 +64,20 @@ def _stop_burst() -> int:
     host reads the rows' finish state (with the tokens). A row that finishes inside a burst costs the
     rest of it in frozen steps; a short burst costs a host round trip more often. Read per call."""
     return max(1, int(os.environ.get("PENROZ_STOP_BURST", "16")))
+
+
+def _keywords(scope: dict) -> dict:
+    """The option keywords (``ops.decode_options.KEYWORDS``) out of a public generate method's ``locals()``,
+    taken on the method's first line, while its locals are its arguments."""
+    return {name: scope[name] for name in KEYWORDS}
+
+
+def _rectangular(input_context: list) -> list:
+    """``input_context`` itself, for the methods that return row 0; ValueError for a ragged one."""
+    if ragged_ops.ragged_lengths(input_context) is not None:
+        raise ValueError("prompts of different lengths: generate_tokens and generate_tokens_stream return row 0 "
+                         "of a rectangular batch; use generate_batch for a ragged one")
+    return input_context
 
 
 def _status(code: str, message: str) -> dict:
@@ -397,104 +409,40 @@ class NeuralNetworkModel(nn.Module):
                 return None
         return None
 
-    def _logit_bias(self, max_new_tokens: int, temperature: float, end_tokens, *, logit_bias=None,
-                    banned_token_ids=None, allowed_token_ids=None, min_tokens=None) -> bias_ops.Canonical | None:
-        """``ops.logit_bias.check_logit_bias`` against this model's vocabulary: the canonical form, None
-        when everything is neutral, ValueError for a malformed value."""
-        V = self._vocab_size()
-        bias = bias_ops.check_logit_bias(logit_bias, banned_token_ids, allowed_token_ids, min_tokens, end_tokens, V,
-                                         max_new_tokens, temperature)
-        if bias is not None and V is None:
-            raise ValueError("logit_bias / banned_token_ids / allowed_token_ids / min_tokens need a model whose "
-                             "layer list ends with the vocabulary projection")
-        return bias
-
     def _prepare_generation(self, input_context: list, max_new_tokens: int, temperature: float, top_k: int | None,
-                            top_p: float | None = None, min_p: float | None = None,
-                            weight_quant: str | None = None,
-                            *, repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                            frequency_penalty: float | None = None, logprobs: int | None = None,
-                            stop: list | None = None, stop_token: int | None = None,
-                            logit_bias: dict | None = None, banned_token_ids: list | None = None,
-                            allowed_token_ids: list | None = None, min_tokens: int | None = None):
-        samp_ops._check_filters(top_p, min_p)  # a bad range fails before any forward pass
-        wq_ops.resolve(weight_quant)  # (and an unknown decode weight format)
-        pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)  # (and a bad penalty)
-        lp_ops.check_logprobs(logprobs)  # (and a bad number of log-probabilities)
-        seqs = stop_ops.check_stop(stop, self._vocab_size())
-        if seqs is not None and stop_token is not None:  # (and a bad stop set)
-            raise ValueError("give stop_token or stop, not both (a stop_token s is the stop sequence [s])")
-        # (and a bad logit bias, banned or allowed set or min_tokens, ids checked against the vocabulary)
-        bias = self._logit_bias(max_new_tokens, temperature, bias_ops.end_tokens_of(stop_token, seqs),
-                                logit_bias=logit_bias, banned_token_ids=banned_token_ids,
-                                allowed_token_ids=allowed_token_ids, min_tokens=min_tokens)
+                            stop_token: int | None = None, **options):
+        """(context [rows, T] on the model's device, the softmax layer, the call's checked options): a
+        malformed option fails here, before any forward pass."""
+        opts = check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options)
         self.eval()
         device = next(self.parameters()).device
         context = torch.tensor(input_context, dtype=torch.long, device=device)
         if context.ndim == 1:
             context = context.unsqueeze(0)
-        top_k_msg = "" if top_k is None else f" top {top_k}"
-        top_k_msg += "" if top_p is None else f" top_p {top_p}"
-        top_k_msg += "" if min_p is None else f" min_p {min_p}"
-        for name, v in (("repetition", repetition_penalty), ("presence", presence_penalty),
-                        ("frequency", frequency_penalty)):
-            top_k_msg += "" if v is None else f" {name}_penalty {v}"
-        top_k_msg += "" if logprobs is None else f" logprobs {logprobs}"
-        top_k_msg += "" if not stop else f" stop {len(stop)} sequences"
-        if bias is not None:
-            top_k_msg += f" logit bias {len(bias.ids)} entries"
-            top_k_msg += "" if bias.allowed is None else f" {len(bias.allowed)} allowed ids"
-            top_k_msg += "" if not min_tokens else f" min_tokens {min_tokens}"
-        log.info(f"Generating at most {max_new_tokens}{top_k_msg} tokens with {temperature} temperature "
+        log.info(f"Generating at most {max_new_tokens}{opts.describe()} tokens with {temperature} temperature "
                  f"using device {device}")
         softmax_layer = self.layers[-1] if self._is_softmax_last else SoftmaxOnLast(dim=-1)
-        return context, softmax_layer, bias  # (bias: ops.logit_bias' canonical form, None when it is off)
+        return context, softmax_layer, opts
 
     @torch.inference_mode()
     def _generate_next_token(self, context: Tensor, block_size: int, temperature: float, top_k: int | None,
                              softmax_layer=None, kv_cache: KVCache | None = None,
                              pos_embeddings: list[PositionEmbedding] | None = None, *,
-                             top_p: float | None = None, min_p: float | None = None,
-                             repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                             frequency_penalty: float | None = None,
-                             penalty_state: pen_ops.PenaltyState | None = None,
-                             penalty_new: Tensor | None = None, logprobs: int | None = None,
-                             stop: list | None = None, stop_state: stop_ops.StopState | None = None,
-                             logit_bias: dict | None = None, banned_token_ids: list | None = None,
-                             allowed_token_ids: list | None = None, min_tokens: int | None = None,
-                             bias_state: bias_ops.BiasState | None = None, produced: int = 0,
-                             last_index: Tensor | None = None):
-        """``last_index`` (int64 [rows], a ragged call's padded prefill): the position whose logits are
-        row b's — its last real prompt token — instead of the last position.
-        ``penalty_state``: the generate call's penalty bookkeeping (its values already set, its
-        ``begin`` run on the call's prompt); ``penalty_new`` [rows, 1]: the tokens the previous step
-        sampled, which this step counts (None on a call's first step). Penalty values without a state
-        take the whole ``context`` as the prompt. ``logprobs`` n: returns (tokens, ``ops.logprobs.
-        token_logprobs`` of the logits the sampler was given) instead of the tokens alone.
-        ``stop_state``: the generate call's stop bookkeeping (ops/stopping.py); the sampled tokens pass
-        through its ``observe`` — rows that finished before get their finishing token — before they are
-        returned. ``stop`` without a state: this token is the call's first (the prompt takes no part).
-        ``bias_state``: the generate call's logit bias / banned / allowed tokens / ``min_tokens``
-        (ops/logit_bias.py), applied behind the penalties with ``t = produced``, the tokens the call has
-        produced so far. The four values without a state: checked here, the one-token sequences of
-        ``stop`` being the end tokens."""
-        if bias_state is None:
-            bias = self._logit_bias(2 ** 31 - 1, temperature, bias_ops.end_tokens_of(None, stop_ops.check_stop(stop)),
-                                    logit_bias=logit_bias, banned_token_ids=banned_token_ids,
-                                    allowed_token_ids=allowed_token_ids, min_tokens=min_tokens)
-            if bias is not None:
-                bias_state = bias_ops.BiasState(context.device)
-                bias_state.set(bias)
-        if stop_state is None and stop_ops.check_stop(stop, self._vocab_size()) is not None:
-            stop_state = stop_ops.StopState(context.shape[0], context.device)
-            stop_state.set_stop(stop_ops.check_stop(stop))
-            stop_state.begin()
-        if penalty_state is None:
-            pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-            if pen is not None:
-                penalty_state, penalty_new = pen_ops.PenaltyState(), None
-                penalty_state.set_params(*pen)
-                penalty_state.begin(context)
+                             call: DecodeCall | None = None, penalty_new: Tensor | None = None,
+                             last_index: Tensor | None = None, **options):
+        """One forward pass and ``call.apply`` on its last logits (ops/decode_options.py).
+        ``call``: the generate call's state, begun on the call's prompt; ``penalty_new`` [rows, 1]: the
+        tokens the previous step sampled, which this step counts (None on a call's first step). Without a
+        ``call`` the ``options`` (the public methods' keywords) are checked here and this token is a call's
+        first: the penalties take the whole ``context`` as the prompt, the stop sequences start with this
+        token, the one-token sequences of ``stop`` (or ``stop_token``) are the end tokens of ``min_tokens``;
+        ``weight_quant`` is checked and has no effect on one eager step.
+        ``last_index`` (int64 [rows], a ragged call's padded prefill): the position whose logits are
+        row b's — its last real prompt token — instead of the last position."""
+        if call is None:
+            opts = check_options(self._vocab_size(), 2 ** 31 - 1, temperature, top_k, **options)
+            call, penalty_new = DecodeCall(opts, context.shape[0], context.device), None
+            call.begin(context)
         if kv_cache is not None and kv_cache.seq_len() > 0:
             if kv_cache.seq_len() >= block_size:
                 # sliding window: clear and re-prefill the last block_size tokens
@@ -514,16 +462,7 @@ class NeuralNetworkModel(nn.Module):
             last = logits[torch.arange(logits.shape[0], device=logits.device), last_index]
         else:
             last = logits[:, -1, :] if logits.ndim == 3 else logits
-        if penalty_state is not None:  # between the lm_head and the sampler, as in the captured step
-            last = penalty_state.apply(last.contiguous(), penalty_new)
-        if bias_state is not None:  # behind the penalties, as in the captured step
-            last = bias_state.apply(last.contiguous(), produced)
-        nxt = samp_ops.sample(last, temperature, top_k, top_p=top_p, min_p=min_p)
-        n = lp_ops.check_logprobs(logprobs)
-        lps = None if n is None else lp_ops.token_logprobs(last, nxt, n)  # (of the token as sampled)
-        if stop_state is not None:
-            nxt = stop_state.observe(nxt)
-        return nxt if n is None else (nxt, lps)
+        return call.apply(last, penalty_new)  # between the lm_head and the next step's input, as in the captured step
 
     @torch.inference_mode()
     def generate_tokens(self, input_context: list, block_size: int, max_new_tokens: int,
@@ -552,13 +491,10 @@ class NeuralNetworkModel(nn.Module):
         not allowed token — and, for the first ``min_tokens`` tokens, ``stop_token`` and the one-token
         sequences of ``stop`` — gets the finite floor -2^100 (fp16: -2^15) and is never drawn. None, {},
         [] and 0 are off (``allowed_token_ids=[]`` is an error); the result's shape does not change."""
-        return [t for t in self._generate(input_context, block_size, max_new_tokens, temperature, top_k,
-                                          stop_token, full_context=True, top_p=top_p, min_p=min_p,
-                                          weight_quant=weight_quant, repetition_penalty=repetition_penalty,
-                                          presence_penalty=presence_penalty,
-                                          frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop,
-                                          logit_bias=logit_bias, banned_token_ids=banned_token_ids,
-                                          allowed_token_ids=allowed_token_ids, min_tokens=min_tokens)][-1]
+        options = _keywords(locals())
+        prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
+                                            stop_token, **options)
+        return [t for t in self._generate(*prepared, block_size, max_new_tokens, full_context=True)][-1]
 
     @torch.inference_mode()
     def generate_tokens_stream(self, input_context: list, block_size: int, max_new_tokens: int,
@@ -573,42 +509,34 @@ class NeuralNetworkModel(nn.Module):
         """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``. With
         ``stop`` the stream ends with the token that completes a stop sequence. ``logit_bias`` /
         ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in ``generate_tokens``."""
+        options = _keywords(locals())
         log.info("Streaming token generation started")
-        for tok in self._generate(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
-                                  full_context=False, top_p=top_p, min_p=min_p, weight_quant=weight_quant,
-                                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                                  frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop,
-                                  logit_bias=logit_bias, banned_token_ids=banned_token_ids,
-                                  allowed_token_ids=allowed_token_ids, min_tokens=min_tokens):
-            yield tok
+        prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
+                                            stop_token, **options)
+        yield from self._generate(*prepared, block_size, max_new_tokens, full_context=False)
         log.info("Streaming token generation completed")
 
-    def _token_bursts(self, context: Tensor, block_size: int, max_new_tokens: int, temperature, top_k,
-                      softmax_layer, burst: int, *, top_p: float | None = None, min_p: float | None = None,
-                      weight_quant: str | None = None,
-                      repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                      frequency_penalty: float | None = None, logprobs: int | None = None,
-                      stop_run: stop_ops.StopRun | None = None, bias: bias_ops.Canonical | None = None,
+    def _token_bursts(self, context: Tensor, block_size: int, max_new_tokens: int, softmax_layer,
+                      opts: DecodeOptions, burst: int, stop_run: stop_ops.StopRun | None = None,
                       lens: list[int] | None = None):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
-        (cache full) run eagerly, exactly as the per-token path. Logit penalties keep one state per
-        call — the decoder's, where there is one, so the counts carry across bursts and re-prefills:
-        ``begin`` on the whole prompt, the first sampling counts nothing, every later one counts the
-        token sampled before it (eager steps: ``last``; graph steps: the decoder's ``idx``).
-        With ``logprobs`` n every item is ``(new, (lp [rows, k], top_id, top_lp [rows, k, >= min(n, V)]))``
+        (cache full) run eagerly, exactly as the per-token path. The call keeps one ``DecodeCall``
+        (ops/decode_options.py) — over the decoder's states, where there is one, so the penalty counts,
+        the stop check and the bias carry across bursts and re-prefills. Penalties: ``begin`` on the whole
+        prompt, the first sampling counts nothing, every later one counts the token sampled before it
+        (eager steps: ``last``; graph steps: the decoder's ``idx``). Logit bias: an eager step applies it
+        with ``t`` = the tokens produced so far, a graph step reads the burst's start from the device and
+        adds its own counter.
+        With ``opts.logprobs`` n every item is ``(new, (lp [rows, k], top_id, top_lp [rows, k, >= min(n, V)]))``
         (device; ``ops.logprobs.to_lists`` reads them): a burst's from the decoder's buffers, an eager
         step's from ``ops.logprobs.token_logprobs``, in generation order.
-        With ``stop_run`` (stop sequences, ops/stopping.py) the call keeps one ``StopState`` — the
-        decoder's, where there is one — left in ``stop_run.state`` and begun here, once. Every token
-        passes through it where it is made: an eager step's through ``observe`` before it joins the
-        context, a graph step's in the step's last kernel; graph bursts are at most PENROZ_STOP_BURST
-        steps. The consumer reads ``stop_run.state.read(new)`` after each block and stops asking once
-        every row is done, so no further step, eager or graphed, runs past the finish.
-        ``bias``: the call's logit bias / banned / allowed tokens / ``min_tokens`` in canonical form
-        (``_prepare_generation``'s, ops/logit_bias.py). The call keeps one ``BiasState`` — the decoder's,
-        where there is one: an eager step applies it with ``t`` = the tokens produced so far, a graph step
-        reads the burst's start from the device and adds its own counter.
+        With ``stop_run`` (``opts.stop`` is its sequences, ops/stopping.py) the call's ``StopState`` is left
+        in ``stop_run.state``. Every token passes through it where it is made: an eager step's through
+        ``observe`` before it joins the context, a graph step's in the step's last kernel; graph bursts
+        are at most PENROZ_STOP_BURST steps. The consumer reads ``stop_run.state.read(new)`` after each
+        block and stops asking once every row is done, so no further step, eager or graphed, runs past
+        the finish.
         ``lens`` (a ragged call, ops/ragged.py): the rows' prompt lengths; ``context`` is then the prompts
         right-padded to the longest, the decoder is a ragged one (the caller made sure there is one), row
         b's first token comes from the prefill's logits at ``lens[b] - 1`` and every graph step runs row b
@@ -616,75 +544,50 @@ class NeuralNetworkModel(nn.Module):
         never slides (``check_prompts``)."""
         from penroz.models import graph_decode
         rows = context.shape[0]
-        n_lp = lp_ops.check_logprobs(logprobs)
-        pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        ragged = {} if lens is None else {"ragged": True}  # (a rectangular call's lookup is what it was)
-        dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k, top_p, min_p,
-                                       wq_ops.resolve(weight_quant), **ragged)
+        dec = graph_decode.decoder_for(self, rows, block_size, opts, ragged=lens is not None)
         last_index = None
         if lens is not None:
             assert dec is not None, "a ragged call needs the ragged decoder (generate_batch falls back before this)"
             dec.set_lengths(lens)
             last_index = torch.tensor(lens, dtype=torch.long, device=context.device) - 1
         if dec is not None:
-            dec.set_penalties(pen)
-            dec.set_logprobs(n_lp)
-            dec.set_stop(stop_run.seqs if stop_run is not None else None)
-            dec.set_logit_bias(bias)
-        bias_state = None
-        if bias is not None:
-            bias_state = dec.bias if dec is not None else bias_ops.BiasState(context.device)
-            if dec is None:
-                bias_state.set(bias)
-        stop_state = None
+            dec.configure(opts)
+        call = DecodeCall(opts, rows, context.device, dec)
+        call.begin(context)
         if stop_run is not None:
-            if dec is not None:
-                stop_state = dec.stop
-            else:
-                stop_state = stop_ops.StopState(rows, context.device)
-                stop_state.set_stop(stop_run.seqs)
-            stop_state.begin()
-            stop_run.state = stop_state
+            stop_run.state = call.stop
             burst = min(burst, _stop_burst())
-        state = None
-        if pen is not None:
-            state = dec.penalties if dec is not None else pen_ops.PenaltyState()
-            state.set_params(*pen)
-            state.begin(context)
         if dec is None:
             cache, pos = self._attach_kv_cache(capacity=block_size)
         else:
             # one seed per generate call, drawn from torch's generator before any token: graph-
             # sampled tokens depend on (seed, absolute index, row) only (graph_decode.begin)
-            dec.begin(int(torch.randint(0, 2 ** 62, (1,)).item()) if temperature else 0)
+            dec.begin(int(torch.randint(0, 2 ** 62, (1,)).item()) if opts.temperature else 0)
             dec.attach()
             cache, pos = dec.cache, dec.pos_layers
             cache.clear()
         try:
             remaining = max_new_tokens
-            produced = 0
             last = None
             while remaining > 0:
                 n = cache.seq_len() if cache is not None else 0
                 if dec is None or n == 0 or n >= block_size:
-                    new = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache,
-                                                    pos, top_p=top_p, min_p=min_p, penalty_state=state,
-                                                    penalty_new=last, logprobs=n_lp, stop_state=stop_state,
-                                                    bias_state=bias_state, produced=produced,
+                    new = self._generate_next_token(context, block_size, opts.temperature, opts.top_k, softmax_layer,
+                                                    cache, pos, call=call, penalty_new=last,
                                                     last_index=last_index if n == 0 else None)
-                    if n_lp is not None:
+                    if opts.logprobs is not None:
                         new, lps = new[0], tuple(t.unsqueeze(1) for t in new[1])  # one step: [rows, 1, ...]
                     for p in pos:
                         p.position_offset = 0
                 else:
                     k = min(remaining, block_size - n, burst)
-                    new = dec.run(last, k, start=produced)
+                    new = dec.run(last, k, start=call.produced)
                     lps = dec.last_logprobs
+                    call.produced += k
                 context = torch.cat((context, new.to(context.device)), dim=1)
                 last = context[:, -1:]
                 remaining -= new.shape[1]
-                produced += new.shape[1]
-                yield new if n_lp is None else (new, lps)
+                yield new if opts.logprobs is None else (new, lps)
         finally:
             if cache is not None:
                 cache.log_metrics()
@@ -693,33 +596,22 @@ class NeuralNetworkModel(nn.Module):
             else:
                 dec.detach()
 
-    def _generate(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token, full_context, *,
-                  top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None,
-                  repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                  frequency_penalty: float | None = None, logprobs: int | None = None, stop: list | None = None,
-                  logit_bias: dict | None = None, banned_token_ids: list | None = None,
-                  allowed_token_ids: list | None = None, min_tokens: int | None = None):
-        """Row 0's generation. ``stop`` (ops/stopping.py): every row is checked on the device, the call
-        ends once all have finished, row 0's tokens end with its own finish, and the full-context result
-        is ``(tokens, info)`` with ``finish_reason`` / ``stop_sequence`` in ``info``. A ``stop_token`` with
-        one row and no streaming takes the same device check as the sequence ``[stop_token]`` — long
-        bursts instead of one replay and one host read per token — and returns what it always did; with
-        more rows, or streaming, it keeps the per-token host check below. Either way ``stop_token`` and the
-        one-token sequences of ``stop`` are the end tokens that ``min_tokens`` suppresses (ops/logit_bias.py)."""
-        if ragged_ops.ragged_lengths(input_context) is not None:
-            raise ValueError("prompts of different lengths: generate_tokens and generate_tokens_stream return row 0 "
-                             "of a rectangular batch; use generate_batch for a ragged one")
-        pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                    frequency_penalty=frequency_penalty, logprobs=logprobs)
-        context, softmax_layer, bias = self._prepare_generation(
-            input_context, max_new_tokens, temperature, top_k, top_p, min_p, weight_quant, stop=stop,
-            stop_token=stop_token, logit_bias=logit_bias, banned_token_ids=banned_token_ids,
-            allowed_token_ids=allowed_token_ids, min_tokens=min_tokens, **pens)
+    def _generate(self, context: Tensor, softmax_layer, opts: DecodeOptions, block_size, max_new_tokens, full_context):
+        """Row 0's generation, from what ``_prepare_generation`` returned. ``opts.stop`` (ops/stopping.py):
+        every row is checked on the device, the call ends once all have finished, row 0's tokens end with
+        its own finish, and the full-context result is ``(tokens, info)`` with ``finish_reason`` /
+        ``stop_sequence`` in ``info``. A ``stop_token`` with one row and no streaming takes the same device
+        check as the sequence ``[stop_token]`` — long bursts instead of one replay and one host read per
+        token — and returns what it always did; with more rows, or streaming, it keeps the per-token host
+        check below. Either way ``stop_token`` and the one-token sequences of ``stop`` are the end tokens
+        that ``min_tokens`` suppresses (ops/logit_bias.py)."""
         rows = context.shape[0]
-        seqs, V = stop_ops.check_stop(stop), self._vocab_size()
-        routed = (seqs is None and stop_token is not None and rows == 1 and full_context and V is not None
+        stop_token, logprobs, V = opts.stop_token, opts.logprobs, self._vocab_size()
+        routed = (opts.stop is None and stop_token is not None and rows == 1 and full_context and V is not None
                   and isinstance(stop_token, int) and 0 <= stop_token < V)
-        run = stop_ops.StopRun([[stop_token]] if routed else seqs) if (routed or seqs is not None) else None
+        if routed:  # (the bias' end tokens hold stop_token already)
+            opts = replace(opts, stop=[[stop_token]])
+        run = stop_ops.StopRun(opts.stop) if opts.stop is not None else None
         generated = []
         info = {"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {}  # row 0's, when asked for
         done = torch.zeros(rows, dtype=torch.bool)
@@ -727,9 +619,7 @@ class NeuralNetworkModel(nn.Module):
         burst = 1 if (not full_context or (stop_token is not None and not routed)) else max_new_tokens
         stopped = False
         with torch.inference_mode():
-            for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, softmax_layer,
-                                          burst, top_p=top_p, min_p=min_p, weight_quant=weight_quant, stop_run=run,
-                                          bias=bias, **pens):
+            for new in self._token_bursts(context, block_size, max_new_tokens, softmax_layer, opts, burst, run):
                 if logprobs is not None:  # copied back once per burst, with the tokens
                     new, lps = new
                     lp0, top0 = (r[0] for r in lp_ops.to_lists(*(t[:1] for t in lps), logprobs))
@@ -762,51 +652,27 @@ class NeuralNetworkModel(nn.Module):
             yield context[0].tolist() if plain else (context[0].tolist(), info)
 
     def _generate_eager(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
-                        full_context, *, top_p: float | None = None, min_p: float | None = None,
-                        repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                        frequency_penalty: float | None = None, logprobs: int | None = None,
-                        stop: list | None = None, logit_bias: dict | None = None,
-                        banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
-                        min_tokens: int | None = None):
-        """Per-token path (kept for A/B and as the reference-shaped loop). ``stop``: every token passes
-        through one ``StopState`` and its finish state is read per token, as everything is here. The
-        logit bias / banned / allowed tokens / ``min_tokens`` keep one ``BiasState``, applied per token."""
-        context, softmax_layer, bias = self._prepare_generation(
-            input_context, max_new_tokens, temperature, top_k, top_p, min_p,
-            repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-            frequency_penalty=frequency_penalty, logprobs=logprobs, stop=stop, stop_token=stop_token,
-            logit_bias=logit_bias, banned_token_ids=banned_token_ids, allowed_token_ids=allowed_token_ids,
-            min_tokens=min_tokens)
+                        full_context, **options):
+        """Per-token path (kept for A/B and as the reference-shaped loop), with the public methods' option
+        keywords. Every token passes through one ``DecodeCall`` (ops/decode_options.py) and, with ``stop``,
+        the finish state is read per token, as everything is here."""
+        context, softmax_layer, opts = self._prepare_generation(input_context, max_new_tokens, temperature, top_k,
+                                                                stop_token, **options)
+        logprobs = opts.logprobs
         info = {"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {}
-        seqs = stop_ops.check_stop(stop)
-        bias_state = None
-        if bias is not None:
-            bias_state = bias_ops.BiasState(context.device)
-            bias_state.set(bias)
-        stop_state = None
-        if seqs is not None:
-            stop_state = stop_ops.StopState(context.shape[0], context.device)
-            stop_state.set_stop(seqs)
-            stop_state.begin()
-        s_done, s_fin = [0] * context.shape[0], [0] * context.shape[0]
-        prompt_len = context.shape[1]
-        pen = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        state = last = None
-        if pen is not None:
-            state = pen_ops.PenaltyState()
-            state.set_params(*pen)
-            state.begin(context)
+        rows, prompt_len = context.shape
+        call = DecodeCall(opts, rows, context.device)
+        call.begin(context)
+        stop_state, last = call.stop, None
+        s_done, s_fin = [0] * rows, [0] * rows
         cache, pos = self._attach_kv_cache(capacity=block_size)
-        rows = context.shape[0]
         generated = []
         done = torch.zeros(rows, dtype=torch.bool)
         try:
             with torch.inference_mode():
-                for produced in range(max_new_tokens):
+                for _ in range(max_new_tokens):
                     nxt = self._generate_next_token(context, block_size, temperature, top_k, softmax_layer, cache, pos,
-                                                    top_p=top_p, min_p=min_p, penalty_state=state, penalty_new=last,
-                                                    logprobs=logprobs, stop_state=stop_state, bias_state=bias_state,
-                                                    produced=produced)
+                                                    call=call, penalty_new=last)
                     if logprobs is not None:
                         nxt, lps = nxt
                     context = torch.cat((context, nxt.to(context.device)), dim=1)
@@ -866,34 +732,26 @@ class NeuralNetworkModel(nn.Module):
         (rows would reach it at different steps; the re-prefill is a whole-batch operation). On the GPU the
         rows share one captured step, each at its own position (models/graph_decode.py); elsewhere they run
         one at a time (``ops.ragged.reference_generate``). Rows of one length take the rectangular path."""
-        pens = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
-                    frequency_penalty=frequency_penalty, logprobs=logprobs)
+        options = _keywords(locals())
         lens = ragged_ops.ragged_lengths(input_context)
         prompts = None
         if lens is not None:
             prompts = ragged_ops.check_prompts(input_context, block_size, max_new_tokens, self._vocab_size())
-            why = self._ragged_fallback(len(prompts), block_size, temperature, top_k, top_p, min_p, weight_quant)
+            why = self._ragged_fallback()
             if why is not None:
                 ragged_ops.log_fallback(why)
-                return ragged_ops.reference_generate(
-                    self, prompts, block_size, max_new_tokens, temperature, top_k, stop_token, top_p=top_p,
-                    min_p=min_p, weight_quant=weight_quant, stop=stop, logit_bias=logit_bias,
-                    banned_token_ids=banned_token_ids, allowed_token_ids=allowed_token_ids, min_tokens=min_tokens,
-                    **pens)
+                return ragged_ops.reference_generate(self, prompts, block_size, max_new_tokens, temperature, top_k,
+                                                     stop_token, **options)
             input_context = ragged_ops.pad_prompts(prompts)  # (its K/V behind a row's length are never read)
-        context, sm, bias = self._prepare_generation(
-            input_context, max_new_tokens, temperature, top_k, top_p, min_p, weight_quant, stop=stop,
-            stop_token=stop_token, logit_bias=logit_bias, banned_token_ids=banned_token_ids,
-            allowed_token_ids=allowed_token_ids, min_tokens=min_tokens, **pens)
-        seqs = stop_ops.check_stop(stop)
-        run = stop_ops.StopRun(seqs) if seqs is not None else None
+        context, sm, opts = self._prepare_generation(input_context, max_new_tokens, temperature, top_k, stop_token,
+                                                     **options)
+        logprobs = opts.logprobs
+        run = stop_ops.StopRun(opts.stop) if opts.stop is not None else None
         rows, prompt_len = context.shape
         s_done, s_fin = [0] * rows, [0] * rows
         infos = [{"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {} for _ in range(rows)]
         burst = 32 if stop_token is not None else max_new_tokens
-        for new in self._token_bursts(context, block_size, max_new_tokens, temperature, top_k, sm, burst,
-                                      top_p=top_p, min_p=min_p, weight_quant=weight_quant, stop_run=run, bias=bias,
-                                      lens=lens, **pens):
+        for new in self._token_bursts(context, block_size, max_new_tokens, sm, opts, burst, run, lens):
             if logprobs is not None:
                 new, lps = new
             keep, stopped = new.shape[1], False
@@ -926,17 +784,15 @@ class NeuralNetworkModel(nn.Module):
             info.update(fin)
         return contexts, infos
 
-    def _ragged_fallback(self, rows: int, block_size: int, temperature, top_k, top_p, min_p, weight_quant) -> str | None:
+    def _ragged_fallback(self) -> str | None:
         """Why a ragged call runs its rows one at a time (ops/ragged.py), or None: the ragged captured
-        step serves it."""
+        step serves it — ``graph_decode.get_decoder``'s own two conditions, which no option changes."""
         from penroz.models import graph_decode
-        dec = graph_decode.get_decoder(self, rows, block_size, temperature, top_k, top_p, min_p,
-                                       wq_ops.resolve(weight_quant), ragged=True)
-        if dec is not None:
-            return None
         if not graph_decode.applicable(self):
             return "no captured decode step here: CPU, PENROZ_GRAPH_DECODE=0 or a model it does not take"
-        return "the model has no decode program (bf16 GPT-2-pattern or Gemma-family, PENROZ_DECODE_PROGRAM=1)"
+        if not graph_decode.ragged_program_ok(self):
+            return "the model has no decode program (bf16 GPT-2-pattern or Gemma-family, PENROZ_DECODE_PROGRAM=1)"
+        return None
 
     # ------------------------------------------------------------------ training
     @classmethod

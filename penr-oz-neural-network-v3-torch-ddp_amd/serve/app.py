@@ -40,9 +40,8 @@ from pydantic import BaseModel, Field, StrictInt
 from penroz.models.mapper import Mapper
 from penroz.models.model import NeuralNetworkModel
 from penroz.ops import grad_clip as grad_clip_ops
-from penroz.ops import logit_bias as bias_ops
-from penroz.ops import stopping as stop_ops
 from penroz.ops import weight_quant as wq_ops
+from penroz.ops.decode_options import KEYWORDS, NOT_LOADED, check_options
 from penroz.parallel import launcher
 from penroz.utils.loaders import Downloader, Loader
 from penroz.utils.tokenizers import Tokenizer
@@ -483,17 +482,12 @@ def evaluate_model(body: EvaluateRequest = Body(...)):
 
 @app.post("/generate/")
 def model_generate(body: GenerateRequest = Body(...)):
-    if body.weight_quant is not None:  # an unknown format is a 400 before the model is touched (streams too)
-        wq_ops.resolve(body.weight_quant)
-    if body.batch and body.stream:  # (likewise)
+    if body.batch and body.stream:  # a 400 before the model is touched
         raise ValueError("batch returns every row at once: not together with stream")
-    stop = stop_ops.check_stop(body.stop)  # (and a malformed stop set; ids beyond the vocabulary: once it is known)
-    if stop is not None and body.stop_token is not None:
-        raise ValueError("give stop_token or stop, not both (a stop_token s is the stop sequence [s])")
-    # (and a malformed logit bias, banned or allowed set or min_tokens; ids beyond the vocabulary: once it is known)
-    bias_ops.check_logit_bias(body.logit_bias, body.banned_token_ids, body.allowed_token_ids, body.min_tokens,
-                              bias_ops.end_tokens_of(body.stop_token, stop), None, body.max_new_tokens,
-                              body.temperature)
+    # (likewise, streams too: an unknown weight format, a malformed stop set, logit bias, banned or allowed set or
+    # min_tokens, stop_token together with stop; ids beyond the vocabulary: once the model is loaded and it is known)
+    stop = check_options(NOT_LOADED, body.max_new_tokens, body.temperature, body.top_k, body.stop_token,
+                         **{name: getattr(body, name) for name in KEYWORDS}).stop
     model = load_for_serving(body.model_id)
     penalties = dict(repetition_penalty=body.repetition_penalty, presence_penalty=body.presence_penalty,
                      frequency_penalty=body.frequency_penalty)

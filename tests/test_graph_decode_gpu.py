@@ -280,3 +280,44 @@ def test_seeded_stream_equals_non_stream_with_sampling(dtype, top_k):
     torch.manual_seed(43)
     other = m.generate_tokens(ctx, 16, 40, temperature=1.0, top_k=top_k)
     assert other != full  # the seed matters
+
+
+@pytest.mark.parametrize("rows", [1, 6])
+def test_one_step_mode_per_call_and_one_captured_graph_per_mode(monkeypatch, rows):
+    """``GraphDecoder.configure``: a call reaches its mode in one swap, every mode is captured once, a return
+    to a mode takes its graph again, and other values of the same options replay it."""
+    m = _model(torch.bfloat16)
+    captured, capture = [], gd.GraphDecoder._capture
+
+    def recording_capture(self, *a, **k):
+        captured.append(self.mode)
+        return capture(self, *a, **k)
+
+    monkeypatch.setattr(gd.GraphDecoder, "_capture", recording_capture)
+    ctx = torch.randint(0, 256, (rows, 6), generator=torch.Generator().manual_seed(2)).tolist()
+
+    def gen(**kw):
+        return m.generate_batch(ctx, 32, 8, temperature=0.0, **kw)
+
+    plain = gen()
+    (dec,) = m._graph_decoders.values()
+    g_plain = dec.graph
+    assert dec.mode == gd.StepMode(False, False, False, "off") == (False, False, False, "off")
+    all_on = dict(repetition_penalty=1.3, logprobs=2, stop=[[255, 254, 253]], logit_bias={5: 3.0},
+                  banned_token_ids=[plain[0][6]])
+    first = gen(**all_on)
+    g_all = dec.graph
+    assert dec.mode == (True, True, True, "entries") and g_all is not g_plain and first[0] != plain
+    assert (dec._penalised, dec._lp_on, dec._stop_on, dec._bias_form) == dec.mode
+    assert gen() == plain and dec.graph is g_plain and dec._graphs == {(True, True, True, "entries"): g_all}
+    other = gen(repetition_penalty=2.0, frequency_penalty=0.5, logprobs=5, stop=[[250], [251, 252]],
+                logit_bias={9: -4.0, 200: 1.5}, min_tokens=3)
+    assert dec.graph is g_all and dec.mode == (True, True, True, "entries") and other != first
+    assert dec.penalties.params.tolist() == [2.0, 0.0, 0.5] and dec.stop.stop == [[250], [251, 252]]
+    assert dec.bias.n_entries.tolist() == [3] and all(len(t) == 5 for t in other[1][0]["top_logprobs"])
+    masked = gen(allowed_token_ids=list(range(0, 256, 3)))
+    assert dec.mode == (False, False, False, "mask") and all(t % 3 == 0 for r in masked for t in r[6:])
+    assert captured == [(False, False, False, "off"), (True, True, True, "entries"), (False, False, False, "mask")]
+    assert gen() == plain and dec.graph is g_plain
+    assert gen(**all_on) == first and dec.graph is g_all
+    assert len(captured) == 3 and list(m._graph_decoders.values()) == [dec]

@@ -136,6 +136,15 @@ def test_the_fallback_is_logged_once(monkeypatch, tiny, caplog):
     assert sum("one at a time" in r.getMessage() for r in caplog.records) == 1
 
 
+def test_the_fallback_is_decided_as_the_decoder_lookup_decides(tiny):
+    """``_ragged_fallback`` names ``get_decoder``'s reasons for None before the call's options are checked:
+    it gives a reason exactly where the lookup gives no ragged decoder (here: no GPU)."""
+    from penroz.models import graph_decode as gd
+    m, _ = tiny
+    assert gd.get_decoder(m, len(PROMPTS), BLOCK, 0.0, None, ragged=True) is None
+    assert "no captured decode step here" in m._ragged_fallback()
+
+
 # ------------------------------------------------------------------ API
 client = TestClient(main.app, raise_server_exceptions=False)
 BODY = {"model_id": "t", "input": PROMPTS, "block_size": BLOCK, "max_new_tokens": NEW, "temperature": 0.0}

@@ -272,6 +272,17 @@ def test_ragged_falls_back_without_a_decode_program(monkeypatch):
     assert out == [m.generate_tokens([p], 32, 6, temperature=0.0) for p in prompts]
 
 
+def test_the_fallback_is_decided_as_the_decoder_lookup_decides(monkeypatch):
+    """``_ragged_fallback`` gives a reason exactly where ``get_decoder`` gives no ragged decoder: with a
+    decode program neither does, without the program or without the captured step both do."""
+    m = _model("gpt")
+    assert m._ragged_fallback() is None and gd.get_decoder(m, 3, 32, 0.0, None, ragged=True) is not None
+    monkeypatch.setattr(gd, "DECODE_PROGRAM", False)
+    assert "no decode program" in m._ragged_fallback() and gd.get_decoder(m, 3, 32, 0.0, None, ragged=True) is None
+    monkeypatch.setattr(gd, "GRAPH_DECODE", False)
+    assert "no captured decode step" in m._ragged_fallback() and gd.get_decoder(m, 3, 32, 0.0, None, ragged=True) is None
+
+
 def test_everything_composed_in_one_ragged_call(monkeypatch):
     monkeypatch.setattr(kvc, "TURBO_QUANT_ENABLED", True)  # the int8 KV cache
     m = _model("gpt")
