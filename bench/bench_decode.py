@@ -10,6 +10,7 @@ python bench/bench_decode.py [--model gpt2|gemma3-1b] [--batch 64] [--prompt 64]
                              [--stop IDS[/IDS...]] [--ab-stop ROUNDS]
                              [--logit-bias N] [--allowed N] [--ab-bias ROUNDS]
                              [--ragged ROUNDS]
+                             [--speculate K[,K...]] [--rounds ROUNDS] [--copy-model]
 Prints one JSON line: generated tokens/s over all rows (BASELINE config 4: batch 64 /generate).
 --weights int8: the batch 1-4 decode steps read int8 weight copies (ops/weight_quant.py). --ab ROUNDS:
 both weight formats on one model in this one process, alternating, ROUNDS timed runs each; the line
@@ -38,6 +39,13 @@ runs each; the line holds every arm, its difference to the run without, and the 
 one (ops/ragged.py) of the same rows whose prompt lengths are spread evenly over [prompt / 4, prompt] — the same
 longest row, so the same padded prefill and capacity — ROUNDS timed runs each; the line holds both arms, their
 difference, and whether a ragged decoder's captured graph served the ragged arm. --block >= prompt + new.
+--speculate K[,K...]: prompt-lookup speculative decoding (ops/speculative.py) of ONE greedy sequence (--batch is
+ignored): the same process alternates between the plain greedy call and a speculative one per K, --rounds timed
+pairs of runs each. A run's prefill and fixed costs are taken out by difference: every arm generates --new and
+--new / 4 tokens, and ms/step is the time between the two over the steps between the two (greedy: the longer
+run repeats the shorter one's steps). Per arm: ms/step, tokens/step and ms/token. --copy-model (gpt2): the
+best case — position table, attention output projections and fc2 weights zeroed, vocabulary projection = the
+token table, so the argmax is the token fed and every draft is accepted. --block >= prompt + new + K.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -82,6 +90,9 @@ ap.add_argument("--ab-bias", type=int, default=0, metavar="ROUNDS",
                 help="alternate runs without, with the entries and with the allowed set, ROUNDS runs each")
 ap.add_argument("--ragged", type=int, default=0, metavar="ROUNDS",
                 help="alternate a uniform and a ragged batch (prompt lengths spread over [prompt / 4, prompt]), ROUNDS runs each")
+ap.add_argument("--speculate", default=None, metavar="K[,K...]", help="speculative arms (1-3) beside the plain greedy call")
+ap.add_argument("--rounds", type=int, default=5, help="--speculate: timed pairs of runs per arm")
+ap.add_argument("--copy-model", action="store_true", help="--speculate, gpt2: a model whose argmax is the token it was fed")
 a = ap.parse_args()
 if a.ab_bias:
     a.logit_bias, a.allowed = a.logit_bias or 300, a.allowed or 1000
@@ -105,6 +116,16 @@ else:  # google/gemma-3-1b-pt text config (shapes only; no checkpoint)
 m = NeuralNetworkModel("dec", Mapper(layers, {"adamw": {"lr": 6e-4}})).to("cuda")
 if a.dtype == "bf16":
     m.to(dtype=torch.bfloat16)
+if a.copy_model:
+    assert a.model == "gpt2", "--copy-model: gpt2 only"
+    from penroz.models.executor import GPTExecutor
+    sp = GPTExecutor.match(m)
+    with torch.no_grad():
+        sp.wpe.weight.zero_()
+        for b in sp.blocks:
+            b.proj.weight.zero_()
+            b.fc2.weight.zero_()
+        sp.head.weight.copy_(sp.wte.weight)
 ctx = torch.randint(0, V, (a.batch, a.prompt)).tolist()
 samp = dict(temperature=1.0, top_k=a.top_k or None, top_p=a.top_p, min_p=a.min_p)
 pens = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
@@ -155,6 +176,56 @@ def in_effect() -> list:
     return sorted({d.weight_quant or "bf16" for d in m.__dict__.get("_graph_decoders", {}).values()})
 
 
+if a.speculate:
+    ks = [int(v) for v in a.speculate.split(",")]
+    assert a.block >= a.prompt + a.new + max(ks), "--speculate: --block >= prompt + new + K"
+    short = max(1, a.new // 4)
+    wq = "int8" if a.weights == "int8" else ""
+
+    def spec_run(k: int, new: int):
+        """(seconds, decode steps, tokens) of one greedy one-row call; k = 0: the plain call."""
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = m.generate_tokens(ctx[:1], a.block, new, temperature=0.0, weight_quant=wq, speculate=k or None)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, (m.last_speculation["steps"] if k else new), out
+
+    arms = {k: [] for k in [0] + ks}
+    ref = None
+    for k in arms:  # warmup: every arm's decoder and graph captured (the cache keeps two decoders: re-captured per switch)
+        out = spec_run(k, a.new)[2]
+        ref = out if ref is None else ref
+        diff = next((i for i, (x, y) in enumerate(zip(out, ref)) if x != y), None)  # (a near-tie, flipped: random weights)
+        arms[k] = {"same_tokens_as_plain": out == ref, "first_difference_at": diff, "ms_per_step": [], "tokens_per_step": [], "ms_per_token": [],
+                   "run_ms": []}
+    for _ in range(a.rounds):
+        for k, res in arms.items():  # alternating: every arm sees the same drift of clocks and neighbours
+            spec_run(k, short)  # (this arm's decoder is the cached one again: its capture is not timed below)
+            t1, s1, _ = spec_run(k, short)
+            t2, s2, _ = spec_run(k, a.new)
+            res["ms_per_step"].append((t2 - t1) / (s2 - s1) * 1e3)
+            res["tokens_per_step"].append((a.new - short) / (s2 - s1))
+            res["ms_per_token"].append((t2 - t1) / (a.new - short) * 1e3)
+            res["run_ms"].append(t2 * 1e3)
+        stats = dict(m.last_speculation or {})
+    out = {}
+    for k, res in arms.items():
+        o = {"same_tokens_as_plain": res["same_tokens_as_plain"], "first_difference_at": res["first_difference_at"]}
+        for key in ("ms_per_step", "tokens_per_step", "ms_per_token", "run_ms"):
+            v = sorted(res[key])
+            o[key] = {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
+        out["plain" if k == 0 else f"k={k}"] = o
+    base = out["plain"]["ms_per_step"]["median"]
+    for name, o in out.items():
+        # extra tokens per step at which the arm's step costs what that many plain steps cost
+        o["break_even_extra_tokens_per_step"] = round(o["ms_per_step"]["median"] / base - 1, 4)
+    print(json.dumps({"metric": "greedy one-row decode, plain vs speculative, alternating in one process; prefill and "
+                                "fixed costs removed by differencing runs of --new and --new / 4 tokens",
+                      "arms": out, "last_arm_speculation": stats, "copy_model": a.copy_model, "prompt": a.prompt,
+                      "new_tokens": a.new, "short_run": short, "block": a.block, "rounds": a.rounds, "weights": a.weights,
+                      "weights_in_effect": in_effect(), "kv_cache": "int8-turboquant" if a.turbo else a.dtype,
+                      "model": "gpt2-124m" if a.model == "gpt2" else "gemma3-1b-shape", "data": "random weights"}))
+    sys.exit(0)
 if a.ab:
     arms = {"bf16": [], "int8": []}
     for w in arms:

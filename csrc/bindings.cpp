@@ -142,6 +142,10 @@ void stop_observe(torch::Tensor seqs, torch::Tensor seq_len, torch::Tensor n_seq
 void stop_step(torch::Tensor seqs, torch::Tensor seq_len, torch::Tensor n_seqs, torch::Tensor tail,
                torch::Tensor n_gen, torch::Tensor done, torch::Tensor finish_at, torch::Tensor idx,
                torch::Tensor out_buf, torch::Tensor step);
+// spec_decode.hip
+void spec_advance(torch::Tensor hist, torch::Tensor n_t, torch::Tensor cand, torch::Tensor idx, torch::Tensor pos_t,
+                  torch::Tensor len_t, torch::Tensor emitted_t, torch::Tensor limit_t, torch::Tensor steps_t,
+                  torch::Tensor accepted_t, int64_t k, bool draft_only);
 // logit_bias.hip
 void logit_bias_apply(torch::Tensor logits, torch::Tensor ids, torch::Tensor bias, torch::Tensor until,
                       torch::Tensor n_entries, c10::optional<torch::Tensor> allow, bool allow_on, torch::Tensor base_t,
@@ -300,6 +304,13 @@ PYBIND11_MODULE(penroz_kernels, m) {
         pybind11::arg("n_uniq"), pybind11::arg("params"), pybind11::arg("new_tok") = pybind11::none(),
         "logit penalties, one sampling: count new_tok (int64 [B]), then repetition / presence / frequency "
         "(params fp32 [3]) on the listed tokens of logits [B, V], in place");
+  m.def("spec_advance", &spec_advance, pybind11::arg("hist"), pybind11::arg("n_t"), pybind11::arg("cand"),
+        pybind11::arg("idx"), pybind11::arg("pos_t"), pybind11::arg("len_t"), pybind11::arg("emitted_t"),
+        pybind11::arg("limit_t"), pybind11::arg("steps_t"), pybind11::arg("accepted_t"), pybind11::arg("k"),
+        pybind11::arg("draft_only") = false,
+        "prompt-lookup speculative decoding, last kernel of a step of k + 1 rows: accepts the confirmed drafts "
+        "(idx [R, 1] against cand [R]) into hist int32 [cap], advances the int32 [1] counters, drafts the next k "
+        "tokens and writes idx, pos_t int64 [R] and len_t int64 [1]; draft_only: the draft half alone");
   m.def("logit_bias_apply", &logit_bias_apply, pybind11::arg("logits"), pybind11::arg("ids"), pybind11::arg("bias"),
         pybind11::arg("until"), pybind11::arg("n_entries"), pybind11::arg("allow"), pybind11::arg("allow_on"),
         pybind11::arg("base_t"), pybind11::arg("step_t") = pybind11::none(),

@@ -659,7 +659,7 @@ __global__ void __launch_bounds__(256) kv_append_kernel(const T* __restrict__ k,
                                                         TK* __restrict__ vc, float* __restrict__ ks,
                                                         float* __restrict__ vs, int B, int Hkv, int D, int cap,
                                                         const int64_t* __restrict__ pos_dev, int pos_rs,
-                                                        int pos_host) {
+                                                        int pos_host, int cache_bs) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);  // over B*Hkv*2
   if (row >= B * Hkv * 2) return;
@@ -667,7 +667,10 @@ __global__ void __launch_bounds__(256) kv_append_kernel(const T* __restrict__ k,
   const int g = bg % Hkv, b = bg / Hkv;
   const T* src = (which ? v + (size_t)b * v_rs : k + (size_t)b * k_rs) + (size_t)g * D;
   const int pos = pos_dev ? (int)pos_dev[b * pos_rs] : pos_host;  // pos_rs 1: row b's own slot
-  const size_t slot = ((size_t)b * Hkv + g) * cap + pos;
+  PZ_DEVICE_CHECK(pos >= 0 && pos < cap);
+  if (pos < 0 || pos >= cap) return;  // (a device-side slot is data: never a store outside the cache)
+  // cache_bs 0: the shared-cache form — the rows are positions of one sequence, cache batch index 0 for all
+  const size_t slot = ((size_t)(b * cache_bs) * Hkv + g) * cap + pos;
   TK* dst = (which ? vc : kc) + slot * D;
   if constexpr (std::is_same<TK, int8_t>::value) {
     float m = 0.f;
@@ -824,7 +827,9 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c
 }
 
 // k, v: [B, 1, Hkv, D] (views into the fused QKV rows allowed); caches [B, Hkv, cap, D]; the slot is
-// *pos_dev (device int64 [1]; or [B]: row b's own slot) when given, else pos
+// *pos_dev (device int64 [1]; or [B]: row b's own slot) when given, else pos.
+// Shared-cache form (a speculative step, ops/speculative.py): caches [1, Hkv, cap, D] with B > 1 rows and
+// pos_dev [B] — the rows are B positions of one sequence, each written to its own slot of cache batch 0.
 void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor kc, torch::Tensor vc, c10::optional<torch::Tensor> ks,
                c10::optional<torch::Tensor> vs, c10::optional<torch::Tensor> pos_dev, int64_t pos) {
   const char* who = "kv_append";
@@ -835,16 +840,18 @@ void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor kc, torch::Tensor
               ": k / v rows must be packed");
   const int B = k.size(0), Hkv = k.size(2), D = k.size(3);
   const bool quant = kc.scalar_type() == torch::kInt8;
-  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous() && kc.dim() == 4 && kc.sizes() == vc.sizes() && kc.size(0) == B &&
-                  kc.size(1) == Hkv && kc.size(3) == D && vc.scalar_type() == kc.scalar_type() &&
-                  (quant || kc.scalar_type() == k.scalar_type()),
-              who, ": contiguous caches [B, Hkv, cap, D] of k's dtype or int8");
-  const int cap = kc.size(2);
+  const bool shared = kc.dim() == 4 && kc.size(0) == 1 && B > 1;
+  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous() && kc.dim() == 4 && kc.sizes() == vc.sizes() &&
+                  (kc.size(0) == B || shared) && kc.size(1) == Hkv && kc.size(3) == D &&
+                  vc.scalar_type() == kc.scalar_type() && (quant || kc.scalar_type() == k.scalar_type()),
+              who, ": contiguous caches [B, Hkv, cap, D] (or [1, Hkv, cap, D], shared by the rows) of k's dtype or int8");
+  const int cap = kc.size(2), CB = kc.size(0);
   const I64Rows pr = la_defined(pos_dev) ? la_i64_rows(who, "pos_dev", *pos_dev, B) : I64Rows{};
   const int64_t* pd = pr.p;
   TORCH_CHECK(pd || (pos >= 0 && pos < cap), who, ": cache overflow");
-  float* ksp = quant ? la_f32_shape(who, "ks", ks, {B, Hkv, cap}) : nullptr;
-  float* vsp = quant ? la_f32_shape(who, "vs", vs, {B, Hkv, cap}) : nullptr;
+  TORCH_CHECK(!shared || pr.stride == 1, who, ": rows sharing one cache need a slot each: pos_dev [B]");
+  float* ksp = quant ? la_f32_shape(who, "ks", ks, {CB, Hkv, cap}) : nullptr;
+  float* vsp = quant ? la_f32_shape(who, "vs", vs, {CB, Hkv, cap}) : nullptr;
   la_by_elem(who, k.scalar_type(), [&](auto ttag) {
     using T = decltype(ttag);
     auto launch = [&](auto ktag) {
@@ -853,7 +860,7 @@ void kv_append(torch::Tensor k, torch::Tensor v, torch::Tensor kc, torch::Tensor
                          at::hip::getCurrentHIPStream(), reinterpret_cast<const T*>(k.data_ptr()),
                          reinterpret_cast<const T*>(v.data_ptr()), k.stride(0), v.stride(0),
                          reinterpret_cast<TK*>(kc.data_ptr()), reinterpret_cast<TK*>(vc.data_ptr()), ksp, vsp, B, Hkv, D, cap,
-                         pd, pr.stride, (int)pos);
+                         pd, pr.stride, (int)pos, shared ? 0 : 1);
     };
     if (quant) launch(int8_t{});
     else launch(ttag);

@@ -1,5 +1,5 @@
 // Operand checks of the decode-step launch wrappers (decode_linear.hip, skinny_gemm.hip,
-// decode_gemv_q8.hip, decode_attn.hip, sampling.hip, logit_penalty.hip, logit_bias.hip, token_logprobs.hip, stop_check.hip), written once. Each checks one operand and
+// decode_gemv_q8.hip, decode_attn.hip, sampling.hip, logit_penalty.hip, logit_bias.hip, token_logprobs.hip, stop_check.hip, spec_decode.hip), written once. Each checks one operand and
 // returns its typed pointer; `who` is the entry point's name for the message. Where the entry
 // points differ, the difference is a parameter. Also the wrappers' dtype -> element type dispatch
 // and their read of an integer environment switch. Host only.

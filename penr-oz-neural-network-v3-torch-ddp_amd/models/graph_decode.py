@@ -58,6 +58,15 @@ between steps lives on the device:
   the QKV epilogue. The host tracks the longest row for the capacity check; the prompt lengths come from
   ``set_lengths`` once per call. Graph modes and their lazily captured graphs are as above.
 
+* speculative decoding (``ops/speculative.py``, ``csrc/kernels/spec_decode.hip``): a ``GraphDecoder`` with
+  ``speculate=k`` runs ``k + 1`` rows — consecutive positions of ONE greedy sequence — against a batch-1 cache:
+  ``pos_t`` is ``[k + 1]``, ``len_t`` ``[1]``. The program runs as for a ragged step (per-row positions in the
+  embedding and the RoPE table); ``_attend_graph`` appends the rows' K/V into the one cache (``kv_append``'s
+  shared-cache form) and attends with ``Tq = k + 1``, row i over its own ``n + i`` keys; the greedy sampler
+  chooses per row and ``spec_advance`` accepts the confirmed drafts, keeps the history and drafts the next
+  step's rows, all on the device. ``run_speculative`` replays bursts of steps without a host synchronisation
+  per step and reads the history's new part once per burst.
+
 The host only tracks the cache length (one per replay) to switch to the reference's
 sliding-window re-prefill when the window is full, and copies each burst of tokens back once
 (stop-token checks per burst). Prefill and re-prefill run eagerly. RoPE models (Gemma) rotate
@@ -145,12 +154,18 @@ class _GraphMode:
 
     graph_mode = False
 
-    def init_graph_state(self, device, rows: int | None = None):
-        """``rows``: a ragged decoder's row count — one slot and one length per row instead of one."""
+    shared = False
+
+    def init_graph_state(self, device, rows: int | None = None, shared: bool = False):
+        """``rows``: a ragged decoder's row count — one slot and one length per row instead of one.
+        ``shared`` (a speculative decoder): the rows are positions of one sequence in a batch-1 cache — a slot
+        per row, one length; the program takes its per-row positions as from a ragged cache."""
         self.ragged = rows is not None
+        self.shared = bool(shared)
+        assert self.ragged or not self.shared
         n = rows if self.ragged else 1
         self.pos_t = torch.zeros(n, dtype=torch.long, device=device)  # slot written by the step
-        self.len_t = torch.ones(n, dtype=torch.long, device=device)   # cache length after it
+        self.len_t = torch.ones(1 if self.shared else n, dtype=torch.long, device=device)   # cache length after it
         self._rope_tables: dict = {}
 
     def begin_step(self):
@@ -177,6 +192,9 @@ class StaticKVCache(_GraphMode, kvc.KVCache):
         # k, v, q are views into this layer's fused QKV rows: one kernel appends K/V at pos_t,
         # the decode kernel reads q in place and the cache length from len_t
         kc, vc = self._k[l], self._v[l]
+        if self.shared:  # the rows' K/V into the one cache at pos_t [R], then Tq = R queries over len_t [1] keys
+            _ext.kernels().kv_append(k, v, kc, vc, None, None, self.pos_t, 0)
+            return attn_ops.decode_attention(_as_one_sequence(q), kc, vc, kc.shape[2], seq_len_dev=self.len_t)
         if FUSED_APPEND:
             return attn_ops.decode_attention(q, kc, vc, kc.shape[2], seq_len_dev=self.len_t, k_new=k, v_new=v)
         _ext.kernels().kv_append(k, v, kc, vc, None, None, self.pos_t, 0)
@@ -204,6 +222,10 @@ class StaticTurboKVCache(_GraphMode, kvc.TurboQuantKVCache):
     def _attend_graph(self, l: int, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
         # same per-token int8 quantiser as the eager append (kv_quantize)
         self._dtype[l] = k.dtype
+        if self.shared:
+            _ext.kernels().kv_append(k, v, self._k[l], self._v[l], self._sk[l], self._sv[l], self.pos_t, 0)
+            return attn_ops.decode_attention(_as_one_sequence(q), self._k[l], self._v[l], self._k[l].shape[2],
+                                             self._sk[l], self._sv[l], seq_len_dev=self.len_t)
         if FUSED_APPEND:
             return attn_ops.decode_attention(q, self._k[l], self._v[l], self._k[l].shape[2], self._sk[l],
                                              self._sv[l], seq_len_dev=self.len_t, k_new=k, v_new=v)
@@ -217,6 +239,12 @@ def _qkv_views(qkv: Tensor, H: int, Hkv: int, D: int):
     rows = qkv.shape[0]
     q, k, v = qkv.view(rows, 1, -1).split([H * D, Hkv * D, Hkv * D], dim=2)
     return q.reshape(rows, 1, H, D), k.view(rows, 1, Hkv, D), v.view(rows, 1, Hkv, D)
+
+
+def _as_one_sequence(q: Tensor) -> Tensor:
+    """q [rows, 1, H, D] (a view into the fused QKV rows) as [1, rows, H, D]: the rows as consecutive queries
+    of one sequence, still read in place."""
+    return q.squeeze(1).unsqueeze(0)
 
 
 class _PlainSteps:
@@ -726,7 +754,7 @@ class GraphDecoder:
 
     def __init__(self, model, rows: int, capacity: int, temperature: float, top_k: int | None,
                  top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None,
-                 ragged: bool = False):
+                 ragged: bool = False, speculate: int | None = None):
         # weak: the model caches its decoders (model.__dict__), so a strong reference would make a
         # cycle that only the cyclic GC frees — and a collection that runs while ANOTHER graph is
         # being captured destroys this one's graph mid-capture (a hard abort)
@@ -738,7 +766,12 @@ class GraphDecoder:
         self.cache = cls(len(self.attn), capacity)
         # ragged (ops/ragged.py): every row at its own position and cache length — pos_t / len_t are [rows]
         self.ragged = bool(ragged)
-        self.cache.init_graph_state(self.device, rows if self.ragged else None)
+        # speculative (ops/speculative.py): ``rows`` = k + 1 positions of one sequence in a batch-1 cache
+        self.speculate = int(speculate or 0)
+        assert not self.speculate or (rows == self.speculate + 1 and not self.ragged and not temperature), \
+            (rows, speculate, ragged, temperature)
+        self.cache.init_graph_state(self.device, rows if self.ragged or self.speculate else None,
+                                    shared=bool(self.speculate))
         self._lens_t: Tensor | None = None  # the call's prompt lengths [rows] (device) and the longest
         self._lmax = 0
         self.rows, self.capacity = rows, capacity
@@ -756,6 +789,17 @@ class GraphDecoder:
         self.program = GPTDecodeProgram.build(model) or GemmaDecodeProgram.build(model)
         if self.ragged and self.program is None:
             raise ValueError("a ragged decoder needs a decode program (bf16 GPT-2-pattern or Gemma-family model)")
+        if self.speculate:
+            if self.program is None or not _ext.available():
+                raise ValueError("a speculative decoder needs a decode program (bf16 GPT-2-pattern or Gemma-family "
+                                 "model) and the built kernels")
+            # the history and its int32 counters in one buffer, so a burst's result is one read:
+            # [n, emitted, limit, steps, accepted, -, -, -] then hist [capacity]
+            self._spec_buf = torch.zeros(8 + capacity, dtype=torch.int32, device=self.device)
+            self.hist = self._spec_buf[8:]
+            self.n_t, self.emitted_t, self.limit_t, self.steps_t, self.accepted_t = (self._spec_buf[i:i + 1] for i in range(5))
+            self._greedy_u = torch.zeros(rows, dtype=torch.float32, device=self.device)  # (the greedy sampler reads none)
+            self._spec_host: tuple[list[int], int] | None = None  # what _set_state loads: (tokens, limit)
         # the weight format in effect: "int8" when asked for AND this decoder's step qualifies (a
         # decode program at 1-4 rows whose linears all fit the int8 GEMV); the quantised copies exist
         # from here on, before the warm-up step and the capture
@@ -799,6 +843,8 @@ class GraphDecoder:
 
     # ------------------------------------------------------------------ the step
     def _step(self):
+        if self.speculate:
+            return self._spec_step()
         for p in self.pos_layers:
             p.position_offset_tensor = self.cache.pos_t
         self.cache.graph_mode = True
@@ -855,6 +901,62 @@ class GraphDecoder:
             self.cache.graph_mode = False
             for p in self.pos_layers:
                 p.position_offset_tensor = None
+
+    def _spec_step(self):
+        """One speculative step: the program on the k + 1 rows of ``idx`` at ``pos_t``, the greedy sampler on
+        every row, then ``spec_advance``: accept, emit into ``hist``, draft, and the next step's idx / pos_t /
+        len_t. No ``sample_step`` and no fused advance: nothing here counts steps by one."""
+        K = _ext.kernels()
+        self.cache.graph_mode = True
+        self.cache.begin_step()
+        try:
+            last = self.program.forward(self.idx, self.cache).contiguous()
+            cand = K.sample_tokens(last, self._greedy_u, 0.0, 0)
+            K.spec_advance(self.hist, self.n_t, cand, self.idx, self.cache.pos_t, self.cache.len_t, self.emitted_t,
+                           self.limit_t, self.steps_t, self.accepted_t, self.speculate, False)
+        finally:
+            self.cache.graph_mode = False
+
+    def _spec_load(self, tokens: list[int], limit: int):
+        """The state of a call whose sequence so far is ``tokens`` and which wants ``limit`` more: history,
+        counters at zero, and — the draft half of ``spec_advance``, run eagerly — the first step's rows."""
+        n = len(tokens)
+        assert 1 <= n and limit >= 0 and n + limit + self.speculate <= self.capacity, (n, limit, self.capacity)
+        head = torch.tensor([n, 0, limit, 0, 0, 0, 0, 0] + list(tokens), dtype=torch.int32)
+        self._spec_buf[:head.numel()].copy_(head)
+        _ext.kernels().spec_advance(self.hist, self.n_t, self.idx, self.idx, self.cache.pos_t, self.cache.len_t,
+                                    self.emitted_t, self.limit_t, self.steps_t, self.accepted_t, self.speculate, True)
+
+    @torch.inference_mode()
+    def run_speculative(self, tokens: list[int], limit: int, stop_token: int | None = None):
+        """Emit ``limit`` tokens behind ``tokens`` (the sequence so far; the cache holds its positions — the
+        last one's slot is rewritten by the first step, whose row 0 feeds that token, so a cache that holds
+        all but the last will do as well) -> (the new tokens, cut behind the first
+        ``stop_token``; {"steps", "drafted", "accepted"}). Bursts of ``ceil(remaining / (k + 1))`` replays with
+        no host synchronisation inside; after each, one read of the counters and the history. Every step emits
+        at least one token and a step at the limit is frozen, so a burst neither stalls nor overshoots."""
+        k, n0 = self.speculate, len(tokens)
+        assert self.cache.seq_len() in (n0 - 1, n0), (self.cache.seq_len(), n0)
+        self._spec_host = (list(tokens), int(limit))
+        if self.graph is None:
+            self._capture(None, None, 0)
+        else:
+            self._set_state(None, None, 0)
+        n, emitted, steps, accepted, new = n0, 0, 0, 0, []
+        while emitted < limit:
+            burst = -(-(limit - emitted) // (k + 1))
+            for _ in range(burst):
+                self.graph.replay()
+            got = self._spec_buf[:8 + min(n + burst * (k + 1), self.capacity)].tolist()
+            n1, emitted, steps, accepted = got[0], got[1], got[3], got[4]
+            assert n1 > n and n1 - n0 == emitted, (n, n1, n0, emitted)  # every step emits
+            new += got[8 + n:8 + n1]
+            n = n1
+            if stop_token is not None and stop_token in new:
+                new = new[:new.index(stop_token) + 1]
+                break
+        self.cache._len = [n0 + len(new) - 1] * self.cache.num_layers
+        return new, {"steps": steps, "drafted": steps * k, "accepted": accepted}
 
     # The sampler kernel hashes each uniform from (seed_t, step_t, row) as
     #   seed + G·(step + 1) + R·(row + 1)  (mod 2^64, csrc/kernels/sampling.hip),
@@ -922,7 +1024,10 @@ class GraphDecoder:
         return self._lens_t + (cache_len - self._lmax)
 
     def _set_state(self, last_tok: Tensor, cache_len, start: int = 0):
-        """``cache_len``: the cache length every row is at — or, ragged, int64 [rows]: each row's own."""
+        """``cache_len``: the cache length every row is at — or, ragged, int64 [rows]: each row's own. A
+        speculative decoder's state is its call's (``run_speculative``), whatever the arguments."""
+        if self.speculate:
+            return self._spec_load(*self._spec_host)
         self.seed_t.fill_(self._burst_seed(start))
         self.idx.copy_(last_tok)
         if self.ragged:
@@ -967,7 +1072,8 @@ class GraphDecoder:
                 gc.enable()
         self.graph = g
         self._set_state(last_tok, cache_len, start)  # capture does not execute; state is as before
-        log.info(f"captured decode graph: rows={self.rows}{' ragged' if self.ragged else ''} block={self.capacity} "
+        spec = f" speculate={self.speculate}" if self.speculate else ""
+        log.info(f"captured decode graph: rows={self.rows}{' ragged' if self.ragged else ''}{spec} block={self.capacity} "
                  f"temperature={self.temperature} top_k={self.top_k} top_p={self.top_p} min_p={self.min_p} "
                  f"penalties={'on' if self._penalised else 'off'} logprobs={'on' if self._lp_on else 'off'} "
                  f"stop={'on' if self._stop_on else 'off'} logit_bias={self._bias_form}")
@@ -1034,7 +1140,8 @@ def _normalise_filters(temperature: float, top_p: float | None, min_p: float | N
 
 def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: int | None,
                 top_p: float | None = None, min_p: float | None = None,
-                weight_quant: str | None = None, ragged: bool = False) -> GraphDecoder | None:
+                weight_quant: str | None = None, ragged: bool = False,
+                speculate: int | None = None) -> GraphDecoder | None:
     """Cached per model and (rows, block size, sampling settings, weights identity, ragged or not, weight
     format in effect for ``weight_quant`` — as ``ops.weight_quant.resolve`` returned it); None when the
     model does not qualify (CPU, no attention, RoPE head_dim without a decode kernel) or ``PENROZ_GRAPH_DECODE=0``
@@ -1043,7 +1150,7 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
     # before its options are checked, so a third belongs there too: tests/test_ragged.py ties the two together)
     if not applicable(model):
         return None
-    if ragged and not ragged_program_ok(model):
+    if (ragged or speculate) and not ragged_program_ok(model):
         return None
     p = next(model.parameters())
     # weights identity AND version: in-place updates (training) re-capture, so nothing captured
@@ -1052,6 +1159,8 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
     base = (rows, block_size, float(temperature), top_k if temperature else None,
             *_normalise_filters(temperature, top_p, min_p), kvc.TURBO_QUANT_ENABLED, p.data_ptr(), p.dtype, version,
             bool(ragged))
+    if speculate:  # (a plain decoder's key is what it always was)
+        base += (("speculate", int(speculate)),)
     cache = model.__dict__.setdefault("_graph_decoders", {})
     # the key holds the weight format IN EFFECT: a request for int8 that this step cannot honour
     # (more than 4 rows, no decode program, a K that does not fit) shares the bf16 decoder instead of
@@ -1061,7 +1170,8 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
         weight_quant = None
     dec = cache.get(base + (weight_quant,))
     if dec is None:
-        dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p, weight_quant, ragged=ragged)
+        spec = {"speculate": int(speculate)} if speculate else {}
+        dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p, weight_quant, ragged=ragged, **spec)
         if dec.weight_quant != weight_quant:  # asked for int8, runs bf16
             if len(unused) >= 64:
                 unused.clear()
@@ -1078,5 +1188,8 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
 def decoder_for(model, rows: int, block_size: int, opts, ragged: bool = False) -> GraphDecoder | None:
     """``get_decoder`` for a generate call's checked options (``ops.decode_options.DecodeOptions``)."""
     ragged = {"ragged": True} if ragged else {}  # (a rectangular call's lookup is what it always was)
+    if opts.speculate:  # k + 1 rows for the call's one sequence
+        return get_decoder(model, opts.speculate + 1, block_size, 0.0, None, weight_quant=opts.weight_quant,
+                           speculate=opts.speculate)
     return get_decoder(model, rows, block_size, opts.temperature, opts.top_k, opts.top_p, opts.min_p,
                        opts.weight_quant, **ragged)

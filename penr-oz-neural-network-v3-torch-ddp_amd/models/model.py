@@ -46,6 +46,7 @@ from penroz.models.layers import CausalSelfAttention, PositionEmbedding, Softmax
 from penroz.models.mapper import Mapper
 from penroz.ops import logprobs as lp_ops
 from penroz.ops import ragged as ragged_ops
+from penroz.ops import speculative as spec_ops
 from penroz.ops import stopping as stop_ops
 from penroz.ops.decode_options import KEYWORDS, DecodeCall, DecodeOptions, check_options
 from penroz.ops import fused as fused_ops
@@ -80,6 +81,17 @@ def _rectangular(input_context: list) -> list:
     return input_context
 
 
+def call_shape_of(input_context, block_size: int, stream: bool = False) -> dict:
+    """What ``check_options`` checks ``speculate`` against: the call's rows, prompt length and window, as far
+    as ``input_context`` shows them (a malformed one is refused where it always was)."""
+    rows = prompt_len = None
+    if isinstance(input_context, (list, tuple)) and len(input_context) > 0:
+        nested = isinstance(input_context[0], (list, tuple))
+        rows = len(input_context) if nested else 1
+        prompt_len = max(len(r) for r in input_context if isinstance(r, (list, tuple))) if nested else len(input_context)
+    return {"rows": rows, "prompt_len": prompt_len, "block_size": block_size, "stream": stream}
+
+
 def _status(code: str, message: str) -> dict:
     return {"code": code, "dt": dt.now().isoformat(), "message": message}
 
@@ -87,6 +99,8 @@ def _status(code: str, message: str) -> dict:
 class NeuralNetworkModel(nn.Module):
     _detect_shm_path = staticmethod(ckpt.detect_shm_path)
     SHM_PATH = ckpt.detect_shm_path()
+    # the last speculative generate call's {"steps", "drafted", "accepted"} (ops/speculative.py); None: none yet
+    last_speculation: dict | None = None
 
     def __init__(self, model_id: str, mapper: Mapper):
         super().__init__()
@@ -473,7 +487,7 @@ class NeuralNetworkModel(nn.Module):
                         frequency_penalty: float | None = None, logprobs: int | None = None,
                         stop: list | None = None, logit_bias: dict | None = None,
                         banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
-                        min_tokens: int | None = None):
+                        min_tokens: int | None = None, speculate: int | None = None):
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
         "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
@@ -490,10 +504,17 @@ class NeuralNetworkModel(nn.Module):
         logits are rewritten behind the penalties, in front of temperature and the filters; a banned or
         not allowed token — and, for the first ``min_tokens`` tokens, ``stop_token`` and the one-token
         sequences of ``stop`` — gets the finite floor -2^100 (fp16: -2^15) and is never drawn. None, {},
-        [] and 0 are off (``allowed_token_ids=[]`` is an error); the result's shape does not change."""
+        [] and 0 are off (``allowed_token_ids=[]`` is an error); the result's shape does not change.
+        ``speculate`` k in 1..3 (ops/speculative.py): prompt-lookup speculative decoding — a decode step runs
+        k + 1 positions of the sequence and emits 1 to k + 1 tokens; greedy, one row,
+        ``len(prompt) + max_new_tokens + k <= block_size``, with none of the options above but ``weight_quant``
+        and ``stop_token``. The tokens are the plain call's; ``last_speculation`` then holds
+        {"steps", "drafted", "accepted"}. None or 0: off."""
         options = _keywords(locals())
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
-                                            stop_token, **options)
+                                            stop_token, **options, call_shape=call_shape_of(input_context, block_size))
+        if prepared[2].speculate:
+            return self._generate_speculative(*prepared, block_size, max_new_tokens)
         return [t for t in self._generate(*prepared, block_size, max_new_tokens, full_context=True)][-1]
 
     @torch.inference_mode()
@@ -505,14 +526,16 @@ class NeuralNetworkModel(nn.Module):
                                frequency_penalty: float | None = None, logprobs: int | None = None,
                                stop: list | None = None, logit_bias: dict | None = None,
                                banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
-                               min_tokens: int | None = None):
+                               min_tokens: int | None = None, speculate: int | None = None):
         """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``. With
         ``stop`` the stream ends with the token that completes a stop sequence. ``logit_bias`` /
-        ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in ``generate_tokens``."""
+        ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in ``generate_tokens``.
+        ``speculate`` is refused here: a speculative step emits several tokens at once."""
         options = _keywords(locals())
         log.info("Streaming token generation started")
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
-                                            stop_token, **options)
+                                            stop_token, **options,
+                                            call_shape=call_shape_of(input_context, block_size, stream=True))
         yield from self._generate(*prepared, block_size, max_new_tokens, full_context=False)
         log.info("Streaming token generation completed")
 
@@ -651,6 +674,37 @@ class NeuralNetworkModel(nn.Module):
             plain = logprobs is None and (run is None or routed)
             yield context[0].tolist() if plain else (context[0].tolist(), info)
 
+    def _generate_speculative(self, context: Tensor, softmax_layer, opts: DecodeOptions, block_size, max_new_tokens):
+        """The one row's prompt plus its tokens, from what ``_prepare_generation`` returned, by prompt-lookup
+        speculative decoding (ops/speculative.py): the prompt is prefilled eagerly with the speculative
+        decoder's batch-1 cache attached; every token comes from the decoder's bursts
+        (``GraphDecoder.run_speculative``), whose first step feeds the prompt's last token again as its row 0
+        and rewrites that token's cache slot; the result is cut behind the first ``stop_token``. Where that
+        decoder does not exist (CPU, ``PENROZ_GRAPH_DECODE=0``, a model without a decode program) the plain path
+        runs: the same tokens by definition. ``last_speculation``: the call's {"steps", "drafted", "accepted"}."""
+        from penroz.models import graph_decode
+        self.last_speculation = {"steps": 0, "drafted": 0, "accepted": 0}
+        dec = graph_decode.decoder_for(self, 1, block_size, opts)
+        if dec is None:
+            spec_ops.log_fallback("no captured decode step with a decode program here: CPU, PENROZ_GRAPH_DECODE=0 "
+                                  "or a model it does not take")
+            plain = replace(opts, speculate=None)
+            return [t for t in self._generate(context, softmax_layer, plain, block_size, max_new_tokens, True)][-1]
+        tokens, stop_token = context[0].tolist(), opts.stop_token
+        if max_new_tokens <= 0:
+            return tokens
+        dec.attach()
+        cache, pos = dec.cache, dec.pos_layers
+        cache.clear()
+        try:
+            self(context, skip_softmax=True)  # prefill: the prompt's K/V (it fits the window: check_speculate)
+            new, self.last_speculation = dec.run_speculative(tokens, max_new_tokens, stop_token)
+            tokens += new
+        finally:
+            cache.log_metrics()
+            dec.detach()
+        return tokens
+
     def _generate_eager(self, input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
                         full_context, **options):
         """Per-token path (kept for A/B and as the reference-shaped loop), with the public methods' option
@@ -717,7 +771,7 @@ class NeuralNetworkModel(nn.Module):
                        frequency_penalty: float | None = None, logprobs: int | None = None,
                        stop: list | None = None, logit_bias: dict | None = None,
                        banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
-                       min_tokens: int | None = None):
+                       min_tokens: int | None = None, speculate: int | None = None):
         """All rows' contexts (the reference returns row 0 only — bug 5). With ``logprobs`` n:
         ``(contexts, [info per row])``, each ``info`` (``generate_tokens``) as long as that row's
         returned continuation. With ``stop`` (ops/stopping.py) every row finishes on its own: the
@@ -731,10 +785,14 @@ class NeuralNetworkModel(nn.Module):
         ``max(len_b) + max_new_tokens <= block_size`` is required — a ragged call never slides its window
         (rows would reach it at different steps; the re-prefill is a whole-batch operation). On the GPU the
         rows share one captured step, each at its own position (models/graph_decode.py); elsewhere they run
-        one at a time (``ops.ragged.reference_generate``). Rows of one length take the rectangular path."""
+        one at a time (``ops.ragged.reference_generate``). Rows of one length take the rectangular path.
+        ``speculate``: as in ``generate_tokens``, for a batch of one row."""
         options = _keywords(locals())
         lens = ragged_ops.ragged_lengths(input_context)
         prompts = None
+        if speculate:  # checked against the call's shape before anything runs
+            check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
+                          call_shape=call_shape_of(input_context, block_size))
         if lens is not None:
             prompts = ragged_ops.check_prompts(input_context, block_size, max_new_tokens, self._vocab_size())
             why = self._ragged_fallback()
@@ -745,6 +803,8 @@ class NeuralNetworkModel(nn.Module):
             input_context = ragged_ops.pad_prompts(prompts)  # (its K/V behind a row's length are never read)
         context, sm, opts = self._prepare_generation(input_context, max_new_tokens, temperature, top_k, stop_token,
                                                      **options)
+        if opts.speculate:
+            return [self._generate_speculative(context, sm, opts, block_size, max_new_tokens)]
         logprobs = opts.logprobs
         run = stop_ops.StopRun(opts.stop) if opts.stop is not None else None
         rows, prompt_len = context.shape

@@ -18,6 +18,7 @@ from penroz.ops import logit_bias as bias_ops
 from penroz.ops import logprobs as lp_ops
 from penroz.ops import penalties as pen_ops
 from penroz.ops import sampling as samp_ops
+from penroz.ops import speculative as spec_ops
 from penroz.ops import stopping as stop_ops
 from penroz.ops import weight_quant as wq_ops
 
@@ -40,6 +41,7 @@ class DecodeOptions:
     stop_token: int | None = None
     bias: bias_ops.Canonical | None = None  # ``check_logit_bias``', with ``min_tokens`` folded into its entries
     min_tokens: int = 0
+    speculate: int | None = None  # ``check_speculate``'s k in 1..3 (ops/speculative.py); None: off
     asked: str = field(default="", compare=False, repr=False)  # the options as given, in the words of the log line
 
     def describe(self) -> str:
@@ -56,8 +58,11 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
                   presence_penalty: float | None = None, frequency_penalty: float | None = None,
                   logprobs: int | None = None, stop: list | None = None, logit_bias: dict | None = None,
                   banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
-                  min_tokens: int | None = None) -> DecodeOptions:
+                  min_tokens: int | None = None, speculate: int | None = None,
+                  call_shape: dict | None = None) -> DecodeOptions:
     """Every check of a generate call, once each, in this order; ValueError for the first that fails.
+    ``call_shape`` is no option of the call: what the caller knows of its shape (``rows``, ``prompt_len``,
+    ``block_size``, ``stream``), which ``speculate`` is checked against (ops/speculative.py).
     ``V``: the model's vocabulary size, which token ids are checked against. None: the model's layer list
     does not show one, and the options that rewrite logits by id are refused. ``NOT_LOADED`` (the service,
     before it loads the model): not known yet, ids are checked against 2^31 only."""
@@ -75,6 +80,13 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
     if bias is not None and V is None and loaded:
         raise ValueError("logit_bias / banned_token_ids / allowed_token_ids / min_tokens need a model whose "
                          "layer list ends with the vocabulary projection")
+    active = [name for name, v, off in (("repetition_penalty", repetition_penalty, 1.0), ("presence_penalty", presence_penalty, 0.0),
+                                        ("frequency_penalty", frequency_penalty, 0.0)) if v is not None and float(v) != off]
+    active += [name for name, on in (("logprobs", n is not None), ("stop", seqs is not None), ("logit_bias", bool(logit_bias)),
+                                     ("banned_token_ids", bool(banned_token_ids)), ("allowed_token_ids", allowed_token_ids is not None),
+                                     ("min_tokens", bool(min_tokens))) if on]
+    k = spec_ops.check_speculate(speculate, temperature=temperature, active=active, max_new_tokens=max_new_tokens,
+                                 **(call_shape or {}))
     asked = "" if top_k is None else f" top {top_k}"
     asked += "" if top_p is None else f" top_p {top_p}"
     asked += "" if min_p is None else f" min_p {min_p}"
@@ -86,12 +98,14 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
         asked += f" logit bias {len(bias.ids)} entries"
         asked += "" if bias.allowed is None else f" {len(bias.allowed)} allowed ids"
         asked += "" if not min_tokens else f" min_tokens {min_tokens}"
+    asked += "" if k is None else f" speculate {k}"
     return DecodeOptions(temperature, top_k, top_p, min_p, quant, penalties, n, seqs, stop_token, bias,
-                         min_tokens or 0, asked)
+                         min_tokens or 0, k, asked)
 
 
 # the option keywords of the public generate methods: ``check_options``' own, by name
-KEYWORDS = tuple(name for name, p in inspect.signature(check_options).parameters.items() if p.kind is p.KEYWORD_ONLY)
+KEYWORDS = tuple(name for name, p in inspect.signature(check_options).parameters.items()
+                 if p.kind is p.KEYWORD_ONLY and name != "call_shape")
 
 
 class DecodeCall:

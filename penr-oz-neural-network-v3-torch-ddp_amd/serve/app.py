@@ -38,7 +38,7 @@ from fastapi.staticfiles import StaticFiles
 from pydantic import BaseModel, Field, StrictInt
 
 from penroz.models.mapper import Mapper
-from penroz.models.model import NeuralNetworkModel
+from penroz.models.model import NeuralNetworkModel, call_shape_of
 from penroz.ops import grad_clip as grad_clip_ops
 from penroz.ops import weight_quant as wq_ops
 from penroz.ops.decode_options import KEYWORDS, NOT_LOADED, check_options
@@ -182,6 +182,12 @@ class GenerateRequest(ModelRequest):
     weight_quant: str | None = Field(None, examples=[None],
                                      description="Decode weight format: \"int8\" (weight-only int8 for batch 1-4 "
                                                  "decode steps), \"\" (bf16), null: PENROZ_DECODE_WEIGHTS")
+    speculate: StrictInt | None = Field(None, examples=[None],
+                                  description="Prompt-lookup speculative decoding: verify this many draft tokens "
+                                              "(1 to 3) per decode step; greedy, one sequence, no stream, prompt + "
+                                              "max_new_tokens + speculate <= block_size; the tokens are the plain "
+                                              "call's, and \"speculation\" reports steps, drafted and accepted; "
+                                              "null or 0: off")
     stream: bool = Field(False, examples=[False], description="Stream tokens as text/plain lines")
     batch: bool = Field(False, examples=[False],
                         description="Return every row: {\"sequences\": [[...], ...]}, each row's prompt plus its "
@@ -486,8 +492,11 @@ def model_generate(body: GenerateRequest = Body(...)):
         raise ValueError("batch returns every row at once: not together with stream")
     # (likewise, streams too: an unknown weight format, a malformed stop set, logit bias, banned or allowed set or
     # min_tokens, stop_token together with stop; ids beyond the vocabulary: once the model is loaded and it is known)
-    stop = check_options(NOT_LOADED, body.max_new_tokens, body.temperature, body.top_k, body.stop_token,
-                         **{name: getattr(body, name) for name in KEYWORDS}).stop
+    # (and everything a speculative call does not take: its shape is the request's own)
+    early = check_options(NOT_LOADED, body.max_new_tokens, body.temperature, body.top_k, body.stop_token,
+                          **{name: getattr(body, name) for name in KEYWORDS},
+                          call_shape=call_shape_of(body.input, body.block_size, stream=body.stream))
+    stop = early.stop
     model = load_for_serving(body.model_id)
     penalties = dict(repetition_penalty=body.repetition_penalty, presence_penalty=body.presence_penalty,
                      frequency_penalty=body.frequency_penalty)
@@ -498,12 +507,17 @@ def model_generate(body: GenerateRequest = Body(...)):
         penalties["logprobs"] = body.logprobs
     if stop is not None:  # (likewise)
         penalties["stop"] = stop
+    if early.speculate:  # (likewise)
+        penalties["speculate"] = early.speculate
     if body.batch:
         # every row of the batch, ragged or not (ops/ragged.py): generate_batch's result, row for row
         with _Held(model):
             res = model.generate_batch(body.input, body.block_size, body.max_new_tokens, body.temperature,
                                        body.top_k, body.stop_token, top_p=body.top_p, min_p=body.min_p,
                                        weight_quant=body.weight_quant, **penalties)
+            speculation = model.last_speculation
+        if early.speculate:
+            return {"sequences": res, "speculation": speculation}
         if body.logprobs is None and stop is None:
             return {"sequences": res}
         sequences, infos = res
@@ -528,6 +542,9 @@ def model_generate(body: GenerateRequest = Body(...)):
         tokens = model.generate_tokens(body.input, body.block_size, body.max_new_tokens, body.temperature,
                                        body.top_k, body.stop_token, top_p=body.top_p, min_p=body.min_p,
                                        weight_quant=body.weight_quant, **penalties)
+        speculation = model.last_speculation
+    if early.speculate:
+        return {"tokens": tokens, "speculation": speculation}
     if body.logprobs is None and stop is None:
         return {"tokens": tokens}
     tokens, info = tokens
