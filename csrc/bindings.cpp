@@ -84,6 +84,11 @@ torch::Tensor decode_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c
 bool decode_small_applies(int64_t B, int64_t Tq, int64_t H, int64_t Hkv, int64_t D, int64_t S);
 std::tuple<bool, int64_t, int64_t, bool> decode_attn_plan(int64_t B, int64_t Tq, int64_t H, int64_t Hkv, int64_t D,
                                                           int64_t S, bool bf16_plain, int64_t counters);
+// prefill_attn.hip
+torch::Tensor prefill_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, c10::optional<torch::Tensor> k_scale,
+                           c10::optional<torch::Tensor> v_scale, int64_t S, int64_t q_offset, double scale);
+std::tuple<bool, int64_t, int64_t, int64_t, int64_t> prefill_attn_plan(int64_t B, int64_t Tq, int64_t H, int64_t Hkv,
+                                                                       int64_t D, bool q_bf16, const std::string& cache);
 // elementwise.hip (deferred.h)
 void set_deferred_reduce_stream(int64_t stream, int64_t device);
 // decode_attn.hip
@@ -328,6 +333,12 @@ PYBIND11_MODULE(penroz_kernels, m) {
   m.def("decode_attn_plan", &decode_attn_plan, pybind11::arg("B"), pybind11::arg("Tq"), pybind11::arg("H"),
         pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("S"), pybind11::arg("bf16_plain") = true,
         pybind11::arg("counters") = 0, "decode_attn's plan: (small kernel, splits, keys per split, merge) (host only)");
+  m.def("prefill_attn", &prefill_attn, pybind11::arg("q"), pybind11::arg("kc"), pybind11::arg("vc"), pybind11::arg("k_scale"),
+        pybind11::arg("v_scale"), pybind11::arg("S"), pybind11::arg("q_offset"), pybind11::arg("scale"),
+        "MFMA attention of many query rows over the first S = q_offset + Tq cache slots (bf16 or int8 cache)");
+  m.def("prefill_attn_plan", &prefill_attn_plan, pybind11::arg("B"), pybind11::arg("Tq"), pybind11::arg("H"),
+        pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("q_bf16") = true, pybind11::arg("cache") = "bf16",
+        "prefill_attn's plan: (admitted, tile rows, positions per tile, workgroups, LDS bytes) (host only)");
   m.def("set_deferred_reduce_stream", &set_deferred_reduce_stream);
   m.def("kv_append", &kv_append, pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("kc"), pybind11::arg("vc"),
         pybind11::arg("ks") = pybind11::none(), pybind11::arg("vs") = pybind11::none(),

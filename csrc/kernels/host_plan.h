@@ -374,4 +374,41 @@ inline DecodeAttnPlan plan_decode_attn(int64_t B, int64_t Tq, int64_t H, int64_t
   return {false, (int)std::max<int64_t>(1, splits), keys, merge};
 }
 
+// ---- prefill attention launch plan (prefill_attn.hip) ----
+// What is built: bf16 q over a bf16 or int8 cache, head_dim 64 / 128 / 256, group size H / Hkv 1 / 2 / 4 / 8
+// (a power of two <= 32: a wave's 32 tile rows hold whole positions). Everything else stays on decode_attn.
+using PrefillDims = IntList<64, 128, 256>;
+using PrefillWaves = IntList<1, 2, 4>;  // waves per workgroup, 32 tile rows each
+constexpr int prefill_keys(int D) { return D >= 256 ? 32 : 64; }  // keys per staged K / V tile
+constexpr int kPrefillFillWgs = 256;    // workgroups wanted before a tile may widen: one per CU
+constexpr int kCuLdsBytes = 160 * 1024;
+enum class CacheKind { BF16, I8, Other };
+struct PrefillAttnPlan {
+  bool ok;         // admitted; everything below is 0 when not
+  int tile_rows;   // (position, query head of the group) rows per workgroup: 32 per wave
+  int tile_pos;    // positions per tile = tile_rows / G
+  int64_t grid;    // workgroups: B · Hkv · ceil(Tq / tile_pos), one per (batch, KV head, query tile)
+  int lds_bytes;   // two stages of a K and a V tile, and the int8 scales
+};
+
+// The key range is never split (an output row must not depend on the grid), so the only freedom is the
+// tile width: the widest of 128 / 64 / 32 rows that still gives kPrefillFillWgs workgroups, else 32.
+// Wider tiles stage each K / V tile for more rows; narrower ones fill the chip at batch 1 (Gemma-3 1B,
+// one KV head, 1024 positions × 4 heads: 32 workgroups of 128 rows, 128 of 32).
+inline PrefillAttnPlan plan_prefill_attn(int64_t B, int64_t Tq, int64_t H, int64_t Hkv, int64_t D, bool q_bf16, CacheKind cache) {
+  const int64_t G = Hkv > 0 && H % Hkv == 0 ? H / Hkv : 0;
+  if (!q_bf16 || cache == CacheKind::Other || B < 1 || Tq < 1 || !(D == 64 || D == 128 || D == 256) ||
+      !(G == 1 || G == 2 || G == 4 || G == 8))
+    return {false, 0, 0, 0, 0};
+  int waves = 4;
+  auto grid_of = [&](int nw) { return B * Hkv * ((Tq * G + 32 * nw - 1) / (32 * nw)); };
+  while (waves > 1 && grid_of(waves) < kPrefillFillWgs) waves /= 2;
+  const int64_t grid = grid_of(waves);
+  if (grid >= (int64_t(1) << 31)) return {false, 0, 0, 0, 0};
+  // two stages of a K and a V tile; D = 256: also the tile's query rows; int8: two stages of K and V scales
+  const int keys = prefill_keys((int)D);
+  const int lds = 4 * keys * (int)D * 2 + (D >= 256 ? 32 * waves * (int)D * 2 : 0) + (cache == CacheKind::I8 ? 4 * keys * 4 : 16);
+  return {true, 32 * waves, (int)(32 * waves / G), grid, lds};
+}
+
 }  // namespace penroz

@@ -224,6 +224,47 @@ def decode_rope_fusable(B: int, H: int, Hkv: int, D: int, cap: int, cache_dtype:
             and kernels().decode_small_applies(B, 1, H, Hkv, D, cap))
 
 
+# Prefill over the cache (csrc/kernels/prefill_attn.hip): many query rows against the cache through the
+# MFMA kernel instead of one decode workgroup per query position. PENROZ_PREFILL_ATTN=0 restores the
+# decode-kernel route; PENROZ_PREFILL_MIN_TQ is the smallest Tq routed (default: profiles/prefill_attn.md).
+PREFILL_MIN_TQ = 32
+_CACHE_NAMES = {torch.bfloat16: "bf16", torch.int8: "int8"}
+
+
+def _packed_rows(q: Tensor) -> bool:
+    """q [B, Tq, H, D] can be read in place: unit dim stride, packed heads, a uniform row stride."""
+    return (q.stride(3) == 1 and q.stride(2) == q.shape[3]
+            and (q.shape[1] == 1 or q.stride(0) == q.shape[1] * q.stride(1)))
+
+
+def prefill_applies(B: int, Tq: int, H: int, Hkv: int, D: int, q_dtype: torch.dtype,
+                    cache_dtype: torch.dtype) -> bool:
+    """The prefill kernel's own launch plan admits the shape (``prefill_attn_plan``, host_plan.h)."""
+    return bool(kernels().prefill_attn_plan(B, Tq, H, Hkv, D, q_dtype == torch.bfloat16,
+                                            _CACHE_NAMES.get(cache_dtype, "other"))[0])
+
+
+def prefill_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, seq_len: int,
+                      k_scale: Tensor | None = None, v_scale: Tensor | None = None) -> Tensor:
+    """``q [B, Tq, H, D]`` (bf16, query i at position ``seq_len - Tq + i``) against the first ``seq_len``
+    slots of a bf16 or int8 cache ``[B, Hkv, cap, D]`` -> ``[B, Tq, H·D]``, on the MFMA prefill kernel.
+    The definition is ``reference_cache_attention``'s; a shape the kernel does not serve is an error."""
+    if not _packed_rows(q) or q.data_ptr() % 16 or q.stride(1) % 8:
+        q = q.contiguous()
+    Tq = q.shape[1]
+    return kernels().prefill_attn(q, k_cache, v_cache, k_scale, v_scale, int(seq_len), int(seq_len - Tq),
+                                  1.0 / math.sqrt(q.shape[-1]))
+
+
+def _prefill_route(q: Tensor, k_cache: Tensor) -> bool:
+    if os.environ.get("PENROZ_PREFILL_ATTN", "1") == "0":
+        return False
+    B, Tq, H, D = q.shape
+    if Tq < int(os.environ.get("PENROZ_PREFILL_MIN_TQ", PREFILL_MIN_TQ)):
+        return False
+    return prefill_applies(B, Tq, H, k_cache.shape[1], D, q.dtype, k_cache.dtype)
+
+
 def decode_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, seq_len: int,
                      k_scale: Tensor | None = None, v_scale: Tensor | None = None,
                      seq_len_dev: Tensor | None = None, k_new: Tensor | None = None,
@@ -247,9 +288,11 @@ def decode_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, seq_len: int,
     if rope is not None and (k_new is None or not use_kernels(q)):
         raise ValueError("in-kernel RoPE needs the decode kernel's fused append")
     if use_kernels(q) and q.shape[-1] in DECODE_HEAD_DIMS:
+        # a prefill (host-side length, nothing fused): the MFMA kernel where its plan admits the shape
+        if seq_len_dev is None and k_new is None and rope is None and _prefill_route(q, k_cache):
+            return prefill_attention(q, k_cache, v_cache, seq_len, k_scale, v_scale)
         # a view into the fused QKV rows is read in place (packed heads, uniform row stride)
-        if not (q.stride(3) == 1 and q.stride(2) == q.shape[3]
-                and (Tq == 1 or q.stride(0) == q.shape[1] * q.stride(1))):
+        if not _packed_rows(q):
             q = q.contiguous()
         return kernels().decode_attn(q, k_cache, v_cache, k_scale, v_scale, int(seq_len),
                                      int(seq_len - Tq), 1.0 / math.sqrt(q.shape[-1]), seq_len_dev, k_new, v_new,

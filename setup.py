@@ -62,8 +62,13 @@ def _newer(src: str, obj: str, deps: list[str]) -> bool:
     return any(os.path.getmtime(d) > t for d in [src] + deps)
 
 
+# per-source flags: prefill_attn.hip is compiled without the packed-fp32 VALU forms
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"prefill_attn.hip": _NO_PK_F32}
+
+
 def _compile(src: str, obj: str, flags: list[str]):
-    cmd = [HIPCC] + flags + ["-c", src, "-o", obj]
+    cmd = [HIPCC] + flags + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"compile failed: {src}\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
@@ -119,7 +124,7 @@ def dump_isa(src_name: str) -> str:
     out_dir = os.path.join(OUT, "isa")
     os.makedirs(out_dir, exist_ok=True)
     out = os.path.join(out_dir, os.path.splitext(src_name)[0] + ".s")
-    cmd = [HIPCC] + _flags("penroz_kernels") + ["--cuda-device-only", "-S", src, "-o", out]
+    cmd = [HIPCC] + _flags("penroz_kernels") + EXTRA_FLAGS.get(src_name, []) + ["--cuda-device-only", "-S", src, "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"isa dump failed: {src}\n{r.stderr}")
