@@ -411,4 +411,34 @@ inline PrefillAttnPlan plan_prefill_attn(int64_t B, int64_t Tq, int64_t H, int64
   return {true, 32 * waves, (int)(32 * waves / G), grid, lds};
 }
 
+// ---- lm_head scoring launch plan (lmhead_lse.hip) ----
+constexpr int kLmheadColTile = 128, kLmheadKStep = 32;  // vocabulary columns per tile, reduction depth per stage
+constexpr int kLmheadMaxC = 16384, kLmheadMaxSplits = 1024;
+constexpr int kLmheadFillWgs = 512;  // workgroups wanted: two per CU (one's epilogue under the other's MFMAs)
+struct LmheadPlan {
+  int row_tile;   // rows of h per workgroup: 128 or 256 (0: refused; everything below is 0 then)
+  int splits;     // S: contiguous vocabulary ranges, each swept by one workgroup per row tile
+  int tiles_per;  // column tiles per range (the last range may hold fewer, never none)
+  int grid;       // row tiles · S, rounded up to the 8 XCDs (the excess workgroups return at once)
+};
+
+// 256-row tiles read W half as often as 128-row ones and are taken from 512 rows on; below that the
+// narrower tile wastes fewer MFMA rows. S fills the machine whatever N is: N = 1 over GPT-2's 393
+// column tiles gives 393 ranges of one tile, N = 4096 over Gemma's 2048 gives 16 row tiles x 32 ranges
+// of 64. splits_forced > 0 (tests, A/B) replaces the wanted S; either is clamped to the column tiles,
+// then lowered to the S that leaves no range empty. A row's bits depend on S and on nothing else here.
+inline LmheadPlan plan_lmhead_lse(int64_t N, int64_t V, int64_t C, int splits_forced) {
+  if (N < 1 || N > (int64_t(1) << 24) || V < 1 || V > (int64_t(1) << 30) || C < kLmheadKStep || C > kLmheadMaxC ||
+      C % kLmheadKStep != 0)
+    return {0, 0, 0, 0};
+  const int row_tile = N >= 512 ? 256 : 128;
+  const int64_t tiles_m = (N + row_tile - 1) / row_tile;
+  const int64_t ct = (V + kLmheadColTile - 1) / kLmheadColTile;
+  int64_t want = splits_forced > 0 ? splits_forced : (kLmheadFillWgs + tiles_m - 1) / tiles_m;
+  want = std::max<int64_t>(1, std::min<int64_t>({want, ct, kLmheadMaxSplits}));
+  const int64_t per = (ct + want - 1) / want;
+  const int64_t splits = (ct + per - 1) / per;
+  return {row_tile, (int)splits, (int)per, (int)((tiles_m * splits + 7) / 8 * 8)};
+}
+
 }  // namespace penroz

@@ -45,6 +45,7 @@ from penroz.models.kv_cache import KVCache, create_kv_cache
 from penroz.models.layers import CausalSelfAttention, PositionEmbedding, SoftmaxOnLast
 from penroz.models.mapper import Mapper
 from penroz.ops import logprobs as lp_ops
+from penroz.ops import prompt_logprobs as plp_ops
 from penroz.ops import ragged as ragged_ops
 from penroz.ops import speculative as spec_ops
 from penroz.ops import stopping as stop_ops
@@ -90,6 +91,19 @@ def call_shape_of(input_context, block_size: int, stream: bool = False) -> dict:
         rows = len(input_context) if nested else 1
         prompt_len = max(len(r) for r in input_context if isinstance(r, (list, tuple))) if nested else len(input_context)
     return {"rows": rows, "prompt_len": prompt_len, "block_size": block_size, "stream": stream}
+
+
+def _with_prompt_scores(result, scored, rows: bool):
+    """A generate call's result with its prompt's scores under ``info["prompt_logprobs"]``: ``(tokens, info)``,
+    as ``logprobs`` / ``stop`` return it (``rows``: ``generate_batch``'s ``(contexts, [info per row])``)."""
+    plain = not (isinstance(result, tuple) and len(result) == 2)
+    tokens, info = (result, [{} for _ in scored] if rows else {}) if plain else result
+    if rows:
+        for row_info, s in zip(info, scored):
+            row_info["prompt_logprobs"] = s
+    else:
+        info["prompt_logprobs"] = scored
+    return tokens, info
 
 
 def _status(code: str, message: str) -> dict:
@@ -423,6 +437,53 @@ class NeuralNetworkModel(nn.Module):
                 return None
         return None
 
+    def _head_index(self) -> int | None:
+        """Index of the vocabulary projection ``_vocab_size`` finds: the last linear layer, with at most
+        softmax layers behind it."""
+        for i in range(len(self.layers) - 1, -1, -1):
+            if isinstance(self.layers[i], nn.Linear):
+                return i
+            if not isinstance(self.layers[i], nn.Softmax):
+                return None
+        return None
+
+    @torch.inference_mode()
+    def score_tokens(self, sequences: list, block_size: int) -> list[dict]:
+        """Log-probabilities of given tokens (ops/prompt_logprobs.py): one dict per sequence with
+        ``token_logprobs``, ``top_tokens`` and ``top_logprobs``, each as long as the sequence; position i
+        holds the score of token i given the tokens before it, position 0 None. Sequences of 2 to
+        ``block_size`` tokens, of any lengths: they are right-padded as a ragged prefill is (ops/ragged.py;
+        attention is causal, so real positions do not see the pads), run once through every layer in front
+        of the vocabulary projection with any KV cache detached, and the real rows are scored in one
+        ``score_rows`` call — on the GPU without any ``[rows, V]`` logits. ValueError, before any forward
+        pass, for a bad length or token id, or a layer list that does not end in a linear (+ softmax)."""
+        head_i = self._head_index()
+        seqs = plp_ops.check_sequences(sequences, block_size, None if head_i is None else self._vocab_size())
+        self.eval()
+        device = next(self.parameters()).device
+        lens = [len(s) for s in seqs]
+        x = torch.tensor(ragged_ops.pad_prompts(seqs), dtype=torch.long, device=device)
+        attn, pos = self._find_attention_layers(), self._find_position_embeddings()
+        saved, offs = [(a._kv_cache, a._layer_idx) for a in attn], [p.position_offset for p in pos]
+        self._detach_kv_cache(pos)
+        try:
+            with self._autocast(device):
+                for layer in self.layers[:head_i]:
+                    x = layer(x)
+        finally:
+            for a, (c, i) in zip(attn, saved):
+                a.set_kv_cache(c, i)
+            for p, o in zip(pos, offs):
+                p.position_offset = o
+        h = torch.cat([x[b, :n - 1] for b, n in enumerate(lens)])
+        targets = torch.tensor([t for s in seqs for t in s[1:]], dtype=torch.long, device=device)
+        head = self.layers[head_i]
+        if head.weight.dtype in (torch.bfloat16, torch.float16):
+            # a 16-bit projection reads its input in its own type (under autocast a LayerNorm hands it fp32
+            # rows and the linear rounds them): those rounded rows are the operand
+            h = h.to(head.weight.dtype)
+        return plp_ops.to_dicts(lens, *plp_ops.score_rows(h, head.weight, head.bias, targets))
+
     def _prepare_generation(self, input_context: list, max_new_tokens: int, temperature: float, top_k: int | None,
                             stop_token: int | None = None, **options):
         """(context [rows, T] on the model's device, the softmax layer, the call's checked options): a
@@ -487,7 +548,8 @@ class NeuralNetworkModel(nn.Module):
                         frequency_penalty: float | None = None, logprobs: int | None = None,
                         stop: list | None = None, logit_bias: dict | None = None,
                         banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
-                        min_tokens: int | None = None, speculate: int | None = None):
+                        min_tokens: int | None = None, speculate: int | None = None,
+                        prompt_logprobs: bool | None = None):
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
         "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
@@ -509,10 +571,19 @@ class NeuralNetworkModel(nn.Module):
         k + 1 positions of the sequence and emits 1 to k + 1 tokens; greedy, one row,
         ``len(prompt) + max_new_tokens + k <= block_size``, with none of the options above but ``weight_quant``
         and ``stop_token``. The tokens are the plain call's; ``last_speculation`` then holds
-        {"steps", "drafted", "accepted"}. None or 0: off."""
+        {"steps", "drafted", "accepted"}. None or 0: off.
+        ``prompt_logprobs`` True (ops/prompt_logprobs.py): the call first scores row 0's prompt
+        (``score_tokens``, a prompt pass of its own), then generates exactly as without it, and returns
+        ``(tokens, info)`` with ``info["prompt_logprobs"]`` = ``score_tokens``' dict beside whatever ``logprobs`` /
+        ``stop`` put there. The prompt needs 2 to ``block_size`` tokens; not together with ``speculate``."""
         options = _keywords(locals())
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
                                             stop_token, **options, call_shape=call_shape_of(input_context, block_size))
+        if prepared[2].prompt_logprobs:  # every step below sees the options of the call without it
+            scored = self.score_tokens([prepared[0][0].tolist()], block_size)[0]
+            plain = (prepared[0], prepared[1], replace(prepared[2], prompt_logprobs=False))
+            res = [t for t in self._generate(*plain, block_size, max_new_tokens, full_context=True)][-1]
+            return _with_prompt_scores(res, scored, rows=False)
         if prepared[2].speculate:
             return self._generate_speculative(*prepared, block_size, max_new_tokens)
         return [t for t in self._generate(*prepared, block_size, max_new_tokens, full_context=True)][-1]
@@ -526,11 +597,13 @@ class NeuralNetworkModel(nn.Module):
                                frequency_penalty: float | None = None, logprobs: int | None = None,
                                stop: list | None = None, logit_bias: dict | None = None,
                                banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
-                               min_tokens: int | None = None, speculate: int | None = None):
+                               min_tokens: int | None = None, speculate: int | None = None,
+                               prompt_logprobs: bool | None = None):
         """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``. With
         ``stop`` the stream ends with the token that completes a stop sequence. ``logit_bias`` /
         ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in ``generate_tokens``.
-        ``speculate`` is refused here: a speculative step emits several tokens at once."""
+        ``speculate`` is refused here: a speculative step emits several tokens at once. So is
+        ``prompt_logprobs``: a prompt's scores come with a finished call."""
         options = _keywords(locals())
         log.info("Streaming token generation started")
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
@@ -771,7 +844,8 @@ class NeuralNetworkModel(nn.Module):
                        frequency_penalty: float | None = None, logprobs: int | None = None,
                        stop: list | None = None, logit_bias: dict | None = None,
                        banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
-                       min_tokens: int | None = None, speculate: int | None = None):
+                       min_tokens: int | None = None, speculate: int | None = None,
+                       prompt_logprobs: bool | None = None):
         """All rows' contexts (the reference returns row 0 only — bug 5). With ``logprobs`` n:
         ``(contexts, [info per row])``, each ``info`` (``generate_tokens``) as long as that row's
         returned continuation. With ``stop`` (ops/stopping.py) every row finishes on its own: the
@@ -786,8 +860,20 @@ class NeuralNetworkModel(nn.Module):
         (rows would reach it at different steps; the re-prefill is a whole-batch operation). On the GPU the
         rows share one captured step, each at its own position (models/graph_decode.py); elsewhere they run
         one at a time (``ops.ragged.reference_generate``). Rows of one length take the rectangular path.
-        ``speculate``: as in ``generate_tokens``, for a batch of one row."""
+        ``speculate``: as in ``generate_tokens``, for a batch of one row.
+        ``prompt_logprobs`` True: every row's prompt is scored first, in one ``score_tokens`` call (rows of any
+        lengths, 2 to ``block_size`` tokens each); then the call runs as without it and returns
+        ``(contexts, [info per row])`` with ``info["prompt_logprobs"]`` per row."""
         options = _keywords(locals())
+        if prompt_logprobs:  # checked with every other option before anything runs; the rest is the call without it
+            check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
+                          call_shape=call_shape_of(input_context, block_size))
+            nested = isinstance(input_context, (list, tuple)) and len(input_context) > 0 and \
+                isinstance(input_context[0], (list, tuple))
+            scored = self.score_tokens(input_context if nested else [input_context], block_size)
+            plain = self.generate_batch(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
+                                        **{**options, "prompt_logprobs": None})
+            return _with_prompt_scores(plain, scored, rows=True)
         lens = ragged_ops.ragged_lengths(input_context)
         prompts = None
         if speculate:  # checked against the call's shape before anything runs

@@ -4,7 +4,8 @@ state one call keeps while it runs (``DecodeCall``).
 The public generate methods take their options as keywords; everything behind them — the token
 loops of models/model.py, the captured step of models/graph_decode.py, ``/generate``'s early 400 —
 takes the checked object. The checks themselves live with their features (ops/sampling.py,
-ops/weight_quant.py, ops/penalties.py, ops/logprobs.py, ops/stopping.py, ops/logit_bias.py); this
+ops/weight_quant.py, ops/penalties.py, ops/logprobs.py, ops/stopping.py, ops/logit_bias.py,
+ops/speculative.py, ops/prompt_logprobs.py); this
 module is the one place that calls them, in one order.
 """
 from __future__ import annotations
@@ -17,6 +18,7 @@ from torch import Tensor
 from penroz.ops import logit_bias as bias_ops
 from penroz.ops import logprobs as lp_ops
 from penroz.ops import penalties as pen_ops
+from penroz.ops import prompt_logprobs as plp_ops
 from penroz.ops import sampling as samp_ops
 from penroz.ops import speculative as spec_ops
 from penroz.ops import stopping as stop_ops
@@ -42,6 +44,7 @@ class DecodeOptions:
     bias: bias_ops.Canonical | None = None  # ``check_logit_bias``', with ``min_tokens`` folded into its entries
     min_tokens: int = 0
     speculate: int | None = None  # ``check_speculate``'s k in 1..3 (ops/speculative.py); None: off
+    prompt_logprobs: bool = False  # the call also scores its prompt (ops/prompt_logprobs.py)
     asked: str = field(default="", compare=False, repr=False)  # the options as given, in the words of the log line
 
     def describe(self) -> str:
@@ -59,7 +62,7 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
                   logprobs: int | None = None, stop: list | None = None, logit_bias: dict | None = None,
                   banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                   min_tokens: int | None = None, speculate: int | None = None,
-                  call_shape: dict | None = None) -> DecodeOptions:
+                  prompt_logprobs: bool | None = None, call_shape: dict | None = None) -> DecodeOptions:
     """Every check of a generate call, once each, in this order; ValueError for the first that fails.
     ``call_shape`` is no option of the call: what the caller knows of its shape (``rows``, ``prompt_len``,
     ``block_size``, ``stream``), which ``speculate`` is checked against (ops/speculative.py).
@@ -87,6 +90,7 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
                                      ("min_tokens", bool(min_tokens))) if on]
     k = spec_ops.check_speculate(speculate, temperature=temperature, active=active, max_new_tokens=max_new_tokens,
                                  **(call_shape or {}))
+    scored = plp_ops.check_prompt_logprobs(prompt_logprobs, speculate=k, stream=bool((call_shape or {}).get("stream")))
     asked = "" if top_k is None else f" top {top_k}"
     asked += "" if top_p is None else f" top_p {top_p}"
     asked += "" if min_p is None else f" min_p {min_p}"
@@ -99,8 +103,9 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
         asked += "" if bias.allowed is None else f" {len(bias.allowed)} allowed ids"
         asked += "" if not min_tokens else f" min_tokens {min_tokens}"
     asked += "" if k is None else f" speculate {k}"
+    asked += "" if not scored else " prompt_logprobs"
     return DecodeOptions(temperature, top_k, top_p, min_p, quant, penalties, n, seqs, stop_token, bias,
-                         min_tokens or 0, k, asked)
+                         min_tokens or 0, k, scored, asked)
 
 
 # the option keywords of the public generate methods: ``check_options``' own, by name

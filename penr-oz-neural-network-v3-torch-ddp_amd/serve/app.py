@@ -35,7 +35,7 @@ from fastapi.exceptions import RequestValidationError
 from fastapi.params import Query
 from fastapi.responses import HTMLResponse, JSONResponse, RedirectResponse, Response, StreamingResponse
 from fastapi.staticfiles import StaticFiles
-from pydantic import BaseModel, Field, StrictInt
+from pydantic import BaseModel, Field, StrictBool, StrictInt
 
 from penroz.models.mapper import Mapper
 from penroz.models.model import NeuralNetworkModel, call_shape_of
@@ -188,6 +188,12 @@ class GenerateRequest(ModelRequest):
                                               "max_new_tokens + speculate <= block_size; the tokens are the plain "
                                               "call's, and \"speculation\" reports steps, drafted and accepted; "
                                               "null or 0: off")
+    prompt_logprobs: StrictBool = Field(False, examples=[False],
+                                        description="Also score the prompt: \"prompt_logprobs\" holds, per prompt "
+                                                    "position, the token's log-probability given the tokens before "
+                                                    "it, the most likely token and its log-probability (null at "
+                                                    "position 0); one object, a list of them with batch; prompts of 2 "
+                                                    "to block_size tokens; not with stream or speculate")
     stream: bool = Field(False, examples=[False], description="Stream tokens as text/plain lines")
     batch: bool = Field(False, examples=[False],
                         description="Return every row: {\"sequences\": [[...], ...]}, each row's prompt plus its "
@@ -509,6 +515,22 @@ def model_generate(body: GenerateRequest = Body(...)):
         penalties["stop"] = stop
     if early.speculate:  # (likewise)
         penalties["speculate"] = early.speculate
+    if early.prompt_logprobs:  # (likewise; never with stream or speculate: the early check refused those)
+        penalties["prompt_logprobs"] = True
+
+    def with_prompt_scores(out: dict, scores) -> dict:
+        if scores is not None:
+            out["prompt_logprobs"] = scores
+        return out
+
+    def split_prompt_scores(res, rows: bool):
+        """(the call's result as it is without the option, the prompt's scores or None)"""
+        if not early.prompt_logprobs:
+            return res, None
+        tokens, info = res
+        scores = [i.pop("prompt_logprobs") for i in info] if rows else info.pop("prompt_logprobs")
+        return (tokens if body.logprobs is None and stop is None else (tokens, info)), scores
+
     if body.batch:
         # every row of the batch, ragged or not (ops/ragged.py): generate_batch's result, row for row
         with _Held(model):
@@ -518,8 +540,9 @@ def model_generate(body: GenerateRequest = Body(...)):
             speculation = model.last_speculation
         if early.speculate:
             return {"sequences": res, "speculation": speculation}
+        res, scores = split_prompt_scores(res, rows=True)
         if body.logprobs is None and stop is None:
-            return {"sequences": res}
+            return with_prompt_scores({"sequences": res}, scores)
         sequences, infos = res
         out = {"sequences": sequences}
         if stop is not None:
@@ -527,7 +550,7 @@ def model_generate(body: GenerateRequest = Body(...)):
             out["stop_sequence"] = [info.pop("stop_sequence") for info in infos]
         if body.logprobs is not None:
             out["logprobs"] = infos
-        return out
+        return with_prompt_scores(out, scores)
     if body.stream:
         # the lock is held for the stream's whole lifetime (the KV cache stays attached between
         # chunks) and released by the background task even when the client goes away mid-stream
@@ -545,15 +568,16 @@ def model_generate(body: GenerateRequest = Body(...)):
         speculation = model.last_speculation
     if early.speculate:
         return {"tokens": tokens, "speculation": speculation}
+    tokens, scores = split_prompt_scores(tokens, rows=False)
     if body.logprobs is None and stop is None:
-        return {"tokens": tokens}
+        return with_prompt_scores({"tokens": tokens}, scores)
     tokens, info = tokens
     out = {"tokens": tokens}
     if stop is not None:
         out["finish_reason"], out["stop_sequence"] = info.pop("finish_reason"), info.pop("stop_sequence")
     if body.logprobs is not None:
         out["logprobs"] = info
-    return out
+    return with_prompt_scores(out, scores)
 
 
 @app.post("/decode/")
