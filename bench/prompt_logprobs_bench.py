@@ -1,7 +1,8 @@
-"""Prompt scoring (csrc/kernels/lmhead_lse.hip): three arms alternating in one process —
+"""Prompt scoring (csrc/kernels/lmhead_lse.hip): six arms alternating in one process —
 (a) the fused kernel through ``ops.prompt_logprobs.score_rows``; (b) the route it replaces: hipBLASLt
 ``h · Wᵀ`` to bf16 logits, fp32 ``log_softmax``, ``gather``, ``max``; (c) hipBLASLt's GEMM alone, the
-floor for the matrix work. Every arm is warmed up; a round times ``--iters`` calls between two
+floor for the matrix work; (d, e) the kernel's top-n form, ``score_rows(..., top_n=5 / 20)``; (f) the route
+that replaces: (b)'s GEMM and ``log_softmax``, then ``topk(20)``. Every arm is warmed up; a round times ``--iters`` calls between two
 synchronises; the median and the min-max spread of ``--rounds`` rounds are reported, with TF/s from
 2·N·V·C and each arm's peak extra device memory (``torch.cuda.max_memory_allocated`` over one call,
 above what the operands hold). The arms' outputs are compared once per shape.
@@ -77,9 +78,18 @@ def main():
             def gemm():
                 return h @ W.T
 
-            arms = {"fused": fused, "unfused": unfused, "gemm": gemm}
+            def unfused_top20():
+                lsm = torch.log_softmax((h @ W.T).float(), dim=-1)
+                best = lsm.topk(20, dim=-1)
+                return lsm.gather(1, t.unsqueeze(1)).squeeze(1), best.indices, best.values
+
+            arms = {"fused": fused, "unfused": unfused, "gemm": gemm,
+                    "fused_top5": lambda: plp.score_rows(h, W, None, t, 5),
+                    "fused_top20": lambda: plp.score_rows(h, W, None, t, 20), "unfused_top20": unfused_top20}
             got, ref = fused(), unfused()
             diff = (got[0] - ref[0]).abs().max().item()  # (the unfused route rounds its logits to bf16)
+            top20 = arms["fused_top20"]()
+            assert torch.equal(top20[3][:, 0], top20[1]) and (top20[4][:, 1:] <= top20[4][:, :-1]).all()
             mem = {k: peak_extra_mib(f) for k, f in arms.items()}
             for f in arms.values():
                 timed(f, 2)
@@ -89,6 +99,7 @@ def main():
                     us[k].append(timed(f, a.iters))
             fl = 2.0 * N * V * C
             row = {"head": name, "C": C, "V": V, "N": N, "plan": list(plp.kernels().lmhead_lse_plan(N, V, C)),
+                   "plan_top_n": list(plp.kernels().lmhead_lse_plan(N, V, C, 0, 20)),
                    "max_abs_diff_vs_unfused": round(diff, 5)}
             for k in arms:
                 row[k + "_us"] = stats(us[k])

@@ -90,12 +90,9 @@ torch::Tensor prefill_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, 
 std::tuple<bool, int64_t, int64_t, int64_t, int64_t> prefill_attn_plan(int64_t B, int64_t Tq, int64_t H, int64_t Hkv,
                                                                        int64_t D, bool q_bf16, const std::string& cache);
 // lmhead_lse.hip
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lmhead_lse(torch::Tensor h, torch::Tensor w,
-                                                                   c10::optional<torch::Tensor> bias,
-                                                                   torch::Tensor targets, int64_t splits);
 std::vector<torch::Tensor> lmhead_lse_raw(torch::Tensor h, torch::Tensor w, c10::optional<torch::Tensor> bias,
-                                          torch::Tensor targets, int64_t splits);
-std::tuple<int64_t, int64_t, int64_t> lmhead_lse_plan(int64_t N, int64_t V, int64_t C, int64_t splits);
+                                          torch::Tensor targets, int64_t splits, int64_t top_n);
+std::tuple<int64_t, int64_t, int64_t> lmhead_lse_plan(int64_t N, int64_t V, int64_t C, int64_t splits, int64_t top_n);
 // elementwise.hip (deferred.h)
 void set_deferred_reduce_stream(int64_t stream, int64_t device);
 // decode_attn.hip
@@ -346,16 +343,25 @@ PYBIND11_MODULE(penroz_kernels, m) {
   m.def("prefill_attn_plan", &prefill_attn_plan, pybind11::arg("B"), pybind11::arg("Tq"), pybind11::arg("H"),
         pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("q_bf16") = true, pybind11::arg("cache") = "bf16",
         "prefill_attn's plan: (admitted, tile rows, positions per tile, workgroups, LDS bytes) (host only)");
-  m.def("lmhead_lse", &lmhead_lse, pybind11::arg("h"), pybind11::arg("w"), pybind11::arg("bias"), pybind11::arg("targets"),
-        pybind11::arg("splits") = 0,
+  m.def("lmhead_lse",
+        [](torch::Tensor h, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor targets, int64_t splits,
+           int64_t top_n) -> pybind11::tuple {
+          auto r = lmhead_lse_raw(h, w, bias, targets, splits, top_n);
+          if (top_n > 0) return pybind11::make_tuple(r[0], r[1], r[2], r[5], r[6]);
+          return pybind11::make_tuple(r[0], r[1], r[2]);
+        },
+        pybind11::arg("h"), pybind11::arg("w"), pybind11::arg("bias"), pybind11::arg("targets"), pybind11::arg("splits") = 0,
+        pybind11::arg("top_n") = 0,
         "prompt scoring without logits: bf16 h [N, C], W [V, C], bias [V] or None, int64 targets [N] -> "
-        "(token_logprob fp32 [N], top_token int64 [N], top_logprob fp32 [N]); splits > 0 forces the vocabulary ranges");
+        "(token_logprob fp32 [N], top_token int64 [N], top_logprob fp32 [N]); splits > 0 forces the vocabulary ranges; "
+        "top_n in 1..20 appends (ids int64 [N, top_n], logprobs fp32 [N, top_n]): the top_n most likely tokens per row");
   m.def("lmhead_lse_raw", &lmhead_lse_raw, pybind11::arg("h"), pybind11::arg("w"), pybind11::arg("bias"),
-        pybind11::arg("targets"), pybind11::arg("splits") = 0,
-        "lmhead_lse's three results followed by the target logit and the logsumexp (fp32 [N] each)");
+        pybind11::arg("targets"), pybind11::arg("splits") = 0, pybind11::arg("top_n") = 0,
+        "lmhead_lse's three results followed by the target logit and the logsumexp (fp32 [N] each), then the top_n pair");
   m.def("lmhead_lse_plan", &lmhead_lse_plan, pybind11::arg("N"), pybind11::arg("V"), pybind11::arg("C"),
-        pybind11::arg("splits") = 0,
-        "lmhead_lse's plan: (row tile, vocabulary ranges S, workgroups); row tile 0: the shape is refused (host only)");
+        pybind11::arg("splits") = 0, pybind11::arg("top_n") = 0,
+        "lmhead_lse's plan: (row tile, vocabulary ranges S, workgroups); row tile 0: the shape is refused; top_n > 0: "
+        "the top-n form's (host only)");
   m.def("set_deferred_reduce_stream", &set_deferred_reduce_stream);
   m.def("kv_append", &kv_append, pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("kc"), pybind11::arg("vc"),
         pybind11::arg("ks") = pybind11::none(), pybind11::arg("vs") = pybind11::none(),

@@ -415,6 +415,7 @@ inline PrefillAttnPlan plan_prefill_attn(int64_t B, int64_t Tq, int64_t H, int64
 constexpr int kLmheadColTile = 128, kLmheadKStep = 32;  // vocabulary columns per tile, reduction depth per stage
 constexpr int kLmheadMaxC = 16384, kLmheadMaxSplits = 1024;
 constexpr int kLmheadFillWgs = 512;  // workgroups wanted: two per CU (one's epilogue under the other's MFMAs)
+constexpr int kLmheadTopCap = 20;    // the top-n form's list capacity: the n most likely tokens of a row, n <= 20
 struct LmheadPlan {
   int row_tile;   // rows of h per workgroup: 128 or 256 (0: refused; everything below is 0 then)
   int splits;     // S: contiguous vocabulary ranges, each swept by one workgroup per row tile
@@ -427,11 +428,13 @@ struct LmheadPlan {
 // column tiles gives 393 ranges of one tile, N = 4096 over Gemma's 2048 gives 16 row tiles x 32 ranges
 // of 64. splits_forced > 0 (tests, A/B) replaces the wanted S; either is clamped to the column tiles,
 // then lowered to the S that leaves no range empty. A row's bits depend on S and on nothing else here.
-inline LmheadPlan plan_lmhead_lse(int64_t N, int64_t V, int64_t C, int splits_forced) {
+// top_n: the form that also keeps every row's n best columns. Its per-row lists (rows · kLmheadTopCap · 8 B
+// of LDS beside the ring) fit two workgroups per CU only at 128 rows, so it takes that tile at every N.
+inline LmheadPlan plan_lmhead_lse(int64_t N, int64_t V, int64_t C, int splits_forced, bool top_n = false) {
   if (N < 1 || N > (int64_t(1) << 24) || V < 1 || V > (int64_t(1) << 30) || C < kLmheadKStep || C > kLmheadMaxC ||
       C % kLmheadKStep != 0)
     return {0, 0, 0, 0};
-  const int row_tile = N >= 512 ? 256 : 128;
+  const int row_tile = N >= 512 && !top_n ? 256 : 128;
   const int64_t tiles_m = (N + row_tile - 1) / row_tile;
   const int64_t ct = (V + kLmheadColTile - 1) / kLmheadColTile;
   int64_t want = splits_forced > 0 ? splits_forced : (kLmheadFillWgs + tiles_m - 1) / tiles_m;

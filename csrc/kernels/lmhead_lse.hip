@@ -40,6 +40,14 @@
 // output element of an MFMA is its own fixed chain over k, and all reductions of a row run in a
 // fixed order over its own values. The same row scored within another N — in the 128-row or the
 // 256-row form — gives the same bits as long as S is the same.
+//
+// Top-n form (top_n in 1..20, ops/prompt_logprobs.py's top_n): the same sweep also keeps, per row, the n
+// best (logit, lowest id first) columns of the range in an LDS list behind the ring, selected in the tile
+// epilogue on the accumulators (see lmhead_lse_kernel's TN), and the merge kernel folds the S lists of a
+// row to ids [N, n] and logprobs [N, n]. It runs the 128-row tile at every N (68.5 KiB of LDS, two
+// workgroups per CU), its three plain outputs are bitwise those of the plain launch at the same S, its
+// entry 0 is (top_token, top_logprob) bitwise, and the guarantees above hold for the lists as well. With
+// top_n = 0 the launcher starts exactly the kernels of before (the TN = 0 / TOPN = false instantiations).
 #include "attn_common.h"
 #include "host_plan.h"
 #include <torch/extension.h>
@@ -67,13 +75,51 @@ __device__ __forceinline__ uint4 ll_read16(const char* base, unsigned off) {
 // exp(d) for d <= 0 (−inf gives 0)
 __device__ __forceinline__ float ll_exp(float d) { return __builtin_amdgcn_exp2f(d * kLog2e); }
 
+// Top-n keys: (the logit's bits mapped so that unsigned order is float order, ~column id) in one 64-bit
+// word — one total order, larger = better, the lowest id first among equal logits (−0 counts as +0, as a
+// float compare does). 0 is the empty slot: below every real key (−inf maps to 0x007fffff).
+using ll_key_t = unsigned long long;
+__device__ __forceinline__ ll_key_t ll_key(float x, int col) {
+  unsigned u = __float_as_uint(x == 0.f ? 0.f : x);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((ll_key_t)u << 32) | (unsigned)~col;
+}
+__device__ __forceinline__ float ll_key_value(ll_key_t k) {
+  const unsigned u = (unsigned)(k >> 32);
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+__device__ __forceinline__ void ll_wave_fence() {  // LDS written by one half-wave, read by the other
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // partials: pf [4][S][N] fp32 (m, s, best, x_target), pid [S][N] int32 (best id)
-template <int RB, bool BIAS>
+//
+// TN > 0 (the top-n form, RB = 1): the launch also keeps each row's topn <= TN best keys of this vocabulary
+// range. Behind the ring sit the lists, [TN][128 rows] keys (consecutive rows in consecutive 8-B slots: no
+// bank conflict) sorted best first, and their fill counts [128]; a row's list belongs to its wave alone
+// (lanes l and l + 32), so no barrier guards it. A lane carries its row's count, n-th key (0 until the list
+// is full) and that key's logit tv. Per column tile a lane whose tile maximum is below tv is done: none of
+// its 64 columns can enter; a wave with no other lane skips the rest. Otherwise the wave walks its 64
+// accumulator registers (a rolled loop, the register picked by a scalar index) with one compare x >= tv
+// each. Where a lane passes, the two half-waves take turns (the lower columns first): reload count and n-th
+// key (the other half may just have moved them), build the key and compare it exactly, and insert a key
+// that beats the n-th by shifting the worse keys down one slot, a divergent loop over LDS; then every
+// lane of the wave reloads its row's threshold, so tv is never stale. Which keys
+// a list holds after a tile does not depend on the order they were offered in (keys are distinct, and the
+// n best of a set is one set), so the result is that of the definition whatever the divergence does. Past
+// the first tiles a row sees about n / t insertions in its t-th tile. The partial lists go to
+// plist [S][N][topn], empty slots 0. The −inf columns >= V of the ragged last tile are offered like any
+// other: every real column beats them (a higher logit, or −inf with a lower id), so they only ever sit in
+// slots that would otherwise be empty, and the merge kernel drops them by their id.
+template <int RB, bool BIAS, int TN = 0>
 __global__ void __launch_bounds__(256, 2) lmhead_lse_kernel(const bf16* __restrict__ H, const bf16* __restrict__ W,
                                                             const float* __restrict__ bias,
                                                             const int64_t* __restrict__ targets, float* __restrict__ pf,
                                                             int* __restrict__ pid, int N, int V, int C, int ldh, int ldw,
-                                                            int tiles_m, int splits, int tiles_per) {
+                                                            int tiles_m, int splits, int tiles_per,
+                                                            ll_key_t* __restrict__ plist, int topn) {
+  static_assert(TN == 0 || RB == 1, "the top-n lists are laid out for the 128-row tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BM = 128 * RB;
   constexpr int H_TILE = BM * LL_BK * 2;
@@ -154,6 +200,23 @@ __global__ void __launch_bounds__(256, 2) lmhead_lse_kernel(const bf16* __restri
     PZ_DEVICE_CHECK(t >= 0 && t < V);
     rtgt[i] = (int)t;
     asm volatile("" : "+v"(rtgt[i]));  // the load is waited for here, not inside the counted loop
+  }
+
+  // top-n state of this lane's row (tile row lrow): fill count, n-th key (0: not full), its logit
+  ll_key_t* const lst = reinterpret_cast<ll_key_t*>(smem + LL_NBUF * STAGE);  // [TN][BM]
+  int* const lcnt = reinterpret_cast<int*>(lst + TN * BM);                     // [BM]
+  const int lrow = 32 * w + l32;
+  int tcnt = 0;
+  ll_key_t thr = 0;
+  float tv = -INFINITY;
+  auto top_reload = [&]() {
+    tcnt = lcnt[lrow];
+    thr = tcnt == topn ? lst[(topn - 1) * BM + lrow] : 0;
+    tv = tcnt == topn ? ll_key_value(thr) : -INFINITY;
+  };
+  if constexpr (TN > 0) {
+    if (half == 0) lcnt[lrow] = 0;
+    ll_wave_fence();
   }
 
   // the accumulators of a column tile start from its bias (or 0): column of acc[i][j][r] =
@@ -246,6 +309,40 @@ __global__ void __launch_bounds__(256, 2) lmhead_lse_kernel(const bf16* __restri
               for (int r = 0; r < 16; ++r)
                 if (tl == 32 * j + 8 * (r >> 2) + (r & 3)) rxt[i] = acc[i][j][r];
           }
+          if constexpr (TN > 0) {
+            const bool want = cm >= tv && m0 + lrow < N;  // (a clamped row keeps no list)
+            if (__ballot(want)) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+#pragma unroll 1
+                for (int r = 0; r < 16; ++r) {  // rolled: one insertion body per block, the register picked by r
+                  const float x = acc[i][j][r];
+                  const bool pass = want && x >= tv;  // (a column >= V of the ragged tile is −inf and may enter: the merge drops it)
+                  if (__ballot(pass)) {
+#pragma unroll 1
+                    for (int turn = 0; turn < 2; ++turn) {
+                      if (pass && half == turn) {
+                        top_reload();
+                        const ll_key_t k = ll_key(x, cb + 32 * j + 8 * (r >> 2) + (r & 3));
+                        if (k > thr) {
+                          int s = min(tcnt, topn - 1);  // the slot that opens: a full list drops its n-th key
+                          while (s > 0) {
+                            const ll_key_t p = lst[(s - 1) * BM + lrow];
+                            if (p > k) break;
+                            lst[s * BM + lrow] = p;
+                            --s;
+                          }
+                          lst[s * BM + lrow] = k;
+                          lcnt[lrow] = min(tcnt + 1, topn);
+                        }
+                      }
+                      ll_wave_fence();
+                    }
+                    top_reload();
+                  }
+                }
+            }
+          }
         }
         acc_init(n0 + LL_BN);
       }
@@ -276,14 +373,30 @@ __global__ void __launch_bounds__(256, 2) lmhead_lse_kernel(const bf16* __restri
       pid[o] = take ? oi : rid[i];
     }
   }
+  if constexpr (TN > 0) {  // the row's list, its two lanes taking alternate slots
+    top_reload();
+    if (m0 + lrow < N) {
+      ll_key_t* out = plist + ((size_t)sp * N + m0 + lrow) * topn;
+      for (int s = half; s < topn; s += 2) out[s] = s < tcnt ? lst[s * BM + lrow] : 0;
+    }
+  }
 }
 
 // one wave per row folds the S partials: lane l takes splits l, l + 64, ... in ascending order, then the 64
 // lanes combine in the fixed order of wave_max / wave_sum (common.h) — the result depends on S alone
+//
+// TOPN: the wave also folds the row's S · topn partial keys to its topn best, kept sorted across the lanes
+// (lane j holds the j-th best; the wave keeps 64, the first topn count). Lane l loads candidate 64 b + l
+// of batch b; the few that beat the current topn-th key are taken in lane order, each inserted with one
+// ballot (its rank = the lanes holding a better key) and one shift by a lane. Keys are distinct, so the
+// result is the topn best of the set in the keys' order, whatever the partials' order was.
+template <bool TOPN>
 __global__ void __launch_bounds__(256) lmhead_lse_merge_kernel(const float* __restrict__ pf, const int* __restrict__ pid,
                                                                int N, int S, float* __restrict__ token_lp,
                                                                int64_t* __restrict__ top_id, float* __restrict__ top_lp,
-                                                               float* __restrict__ x_t, float* __restrict__ lse_out) {
+                                                               float* __restrict__ x_t, float* __restrict__ lse_out,
+                                                               const ll_key_t* __restrict__ plist, int topn, int V,
+                                                               int64_t* __restrict__ n_id, float* __restrict__ n_lp) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;  // (a whole wave)
@@ -318,6 +431,42 @@ __global__ void __launch_bounds__(256) lmhead_lse_merge_kernel(const float* __re
     x_t[row] = xt;
     lse_out[row] = lse;
   }
+  if constexpr (TOPN) {
+    const float lse = M + logf(s);  // (M and s are the same in every lane)
+    ll_key_t mine = 0;
+    unsigned long long nth = 0;  // lane topn - 1's key (wave-uniform)
+    const int total = S * topn;
+    constexpr int PF = 8;  // batches loaded together: S · topn / 64 dependent round trips otherwise (123 at 393 x 20)
+    for (int c0 = 0; c0 < total; c0 += 64 * PF) {
+      ll_key_t keys[PF];
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const int c = c0 + 64 * u + lane;
+        keys[u] = c < total ? plist[((size_t)(c / topn) * N + row) * topn + c % topn] : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const ll_key_t key = ~(unsigned)keys[u] < (unsigned)V ? keys[u] : 0;  // 0: a masked column of the ragged tile, an empty slot
+        unsigned long long todo = __ballot(key > nth);
+        while (todo) {
+          const int src = __builtin_ctzll(todo);
+          todo &= todo - 1;
+          const ll_key_t k = ((ll_key_t)(unsigned)__builtin_amdgcn_readlane((int)(key >> 32), src) << 32) |
+                             (unsigned)__builtin_amdgcn_readlane((int)key, src);
+          if (k <= nth) continue;  // (nth rose since the ballot)
+          const int rank = __popcll(__ballot(mine > k));
+          const ll_key_t up = ((ll_key_t)(unsigned)__shfl_up((int)(mine >> 32), 1) << 32) | (unsigned)__shfl_up((int)mine, 1);
+          mine = lane < rank ? mine : lane == rank ? k : up;
+          nth = ((ll_key_t)(unsigned)__builtin_amdgcn_readlane((int)(mine >> 32), topn - 1) << 32) |
+                (unsigned)__builtin_amdgcn_readlane((int)mine, topn - 1);
+        }
+      }
+    }
+    if (lane < topn) {  // entries past min(topn, V) stay empty: −1 / −inf
+      n_id[(size_t)row * topn + lane] = mine ? (int64_t)(unsigned)~(unsigned)mine : -1;
+      n_lp[(size_t)row * topn + lane] = mine ? ll_key_value(mine) - lse : -INFINITY;
+    }
+  }
 }
 
 }  // namespace
@@ -325,8 +474,8 @@ __global__ void __launch_bounds__(256) lmhead_lse_merge_kernel(const float* __re
 
 using namespace penroz;
 
-std::tuple<int64_t, int64_t, int64_t> lmhead_lse_plan(int64_t N, int64_t V, int64_t C, int64_t splits) {
-  const LmheadPlan p = plan_lmhead_lse(N, V, C, (int)std::max<int64_t>(0, std::min<int64_t>(splits, kLmheadMaxSplits)));
+std::tuple<int64_t, int64_t, int64_t> lmhead_lse_plan(int64_t N, int64_t V, int64_t C, int64_t splits, int64_t top_n) {
+  const LmheadPlan p = plan_lmhead_lse(N, V, C, (int)std::max<int64_t>(0, std::min<int64_t>(splits, kLmheadMaxSplits)), top_n > 0);
   return {p.row_tile, p.splits, p.grid};
 }
 
@@ -336,8 +485,12 @@ std::tuple<int64_t, int64_t, int64_t> lmhead_lse_plan(int64_t N, int64_t V, int6
 // so a caller that compares rows across N pins it. The last two results are what the tests hold to the
 // reference exactly (the target logit) and diagnostics; the merge kernel writes them on every call (2 N
 // floats that lmhead_lse, the public triple, drops).
+// top_n in 1..20: the top-n form (128-row tiles at every N), which appends (top_n_ids int64 [N, top_n],
+// top_n_logprobs fp32 [N, top_n]): per row the min(top_n, V) most likely tokens, best first, the lowest id
+// first among equal logits, then −1 / −inf. 0: exactly the launches of before.
 std::vector<torch::Tensor> lmhead_lse_raw(torch::Tensor h, torch::Tensor w, c10::optional<torch::Tensor> bias,
-                                          torch::Tensor targets, int64_t splits) {
+                                          torch::Tensor targets, int64_t splits, int64_t top_n) {
+  TORCH_CHECK(top_n >= 0 && top_n <= kLmheadTopCap, "lmhead_lse: top_n must be in [0, ", kLmheadTopCap, "], got ", top_n);
   TORCH_CHECK(h.is_cuda() && w.is_cuda() && targets.is_cuda(), "lmhead_lse: CUDA tensors");
   TORCH_CHECK(h.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16,
               "lmhead_lse: bf16 h and W only (fp16 / fp32 take ops.prompt_logprobs' torch path)");
@@ -346,7 +499,7 @@ std::vector<torch::Tensor> lmhead_lse_raw(torch::Tensor h, torch::Tensor w, c10:
   const int64_t N = h.size(0), C = h.size(1), V = w.size(0);
   TORCH_CHECK(targets.scalar_type() == torch::kInt64 && targets.dim() == 1 && targets.numel() == N,
               "lmhead_lse: targets int64 [N]");
-  const LmheadPlan p = plan_lmhead_lse(N, V, C, (int)std::max<int64_t>(0, std::min<int64_t>(splits, kLmheadMaxSplits)));
+  const LmheadPlan p = plan_lmhead_lse(N, V, C, (int)std::max<int64_t>(0, std::min<int64_t>(splits, kLmheadMaxSplits)), top_n > 0);
   TORCH_CHECK(p.row_tile != 0, "lmhead_lse: needs N >= 1, V >= 1 and C a multiple of ", kLmheadKStep, " in [",
               kLmheadKStep, ", ", kLmheadMaxC, "], got N = ", N, ", V = ", V, ", C = ", C);
   const int64_t ldh = N > 1 ? h.stride(0) : C, ldw = V > 1 ? w.stride(0) : C;
@@ -368,9 +521,17 @@ std::vector<torch::Tensor> lmhead_lse_raw(torch::Tensor h, torch::Tensor w, c10:
   auto token_lp = torch::empty({N}, fopt), top_lp = torch::empty({N}, fopt), x_t = torch::empty({N}, fopt);
   auto lse = torch::empty({N}, fopt);
   auto top_id = torch::empty({N}, h.options().dtype(torch::kInt64));
+  const int n = (int)top_n;
+  torch::Tensor plist, n_id, n_lp;  // the partial lists [S, N, n] (64-bit keys) and the two top-n results
+  if (n > 0) {
+    plist = torch::empty({p.splits, N, n}, h.options().dtype(torch::kInt64));
+    n_id = torch::empty({N, n}, h.options().dtype(torch::kInt64));
+    n_lp = torch::empty({N, n}, fopt);
+  }
   auto stream = at::hip::getCurrentHIPStream();
   const int tiles_m = (int)((N + p.row_tile - 1) / p.row_tile);
   const int lds1 = LL_NBUF * (128 * LL_BK * 2 + LL_W_TILE), lds2 = LL_NBUF * (256 * LL_BK * 2 + LL_W_TILE);
+  const int ldsn = lds1 + 128 * (kLmheadTopCap * 8 + 4);  // the 128-row ring, the rows' lists and their counts: 68.5 KiB
   static bool attr_set = false;  // the 256-row ring (72 KiB) is beyond the 64 KiB a kernel gets unasked
   if (!attr_set) {
     auto allow = [](auto kern, int lds) {
@@ -381,32 +542,38 @@ std::vector<torch::Tensor> lmhead_lse_raw(torch::Tensor h, torch::Tensor w, c10:
     allow(lmhead_lse_kernel<1, true>, lds1);
     allow(lmhead_lse_kernel<2, false>, lds2);
     allow(lmhead_lse_kernel<2, true>, lds2);
+    allow(lmhead_lse_kernel<1, false, kLmheadTopCap>, ldsn);
+    allow(lmhead_lse_kernel<1, true, kLmheadTopCap>, ldsn);
     attr_set = true;
   }
   auto launch = [&](auto kern, int lds) {
     hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), lds, stream, reinterpret_cast<const bf16*>(h.data_ptr()),
                        reinterpret_cast<const bf16*>(w.data_ptr()), bf.defined() ? bf.data_ptr<float>() : nullptr,
                        tg.data_ptr<int64_t>(), pf.data_ptr<float>(), pid.data_ptr<int>(), (int)N, (int)V, (int)C, (int)ldh,
-                       (int)ldw, tiles_m, p.splits, p.tiles_per);
+                       (int)ldw, tiles_m, p.splits, p.tiles_per,
+                       n > 0 ? reinterpret_cast<ll_key_t*>(plist.data_ptr<int64_t>()) : nullptr, n);
     TORCH_CHECK(hipGetLastError() == hipSuccess, "lmhead_lse: the kernel launch failed");
   };
-  if (p.row_tile == 128) {
+  if (n > 0) {
+    if (bf.defined()) launch(lmhead_lse_kernel<1, true, kLmheadTopCap>, ldsn);
+    else launch(lmhead_lse_kernel<1, false, kLmheadTopCap>, ldsn);
+  } else if (p.row_tile == 128) {
     if (bf.defined()) launch(lmhead_lse_kernel<1, true>, lds1);
     else launch(lmhead_lse_kernel<1, false>, lds1);
   } else {
     if (bf.defined()) launch(lmhead_lse_kernel<2, true>, lds2);
     else launch(lmhead_lse_kernel<2, false>, lds2);
   }
-  hipLaunchKernelGGL(lmhead_lse_merge_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, pf.data_ptr<float>(),
-                     pid.data_ptr<int>(), (int)N, p.splits, token_lp.data_ptr<float>(), top_id.data_ptr<int64_t>(),
-                     top_lp.data_ptr<float>(), x_t.data_ptr<float>(), lse.data_ptr<float>());
-  TORCH_CHECK(hipGetLastError() == hipSuccess, "lmhead_lse: the merge kernel's launch failed");
+  auto merge = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, stream, pf.data_ptr<float>(), pid.data_ptr<int>(),
+                       (int)N, p.splits, token_lp.data_ptr<float>(), top_id.data_ptr<int64_t>(), top_lp.data_ptr<float>(),
+                       x_t.data_ptr<float>(), lse.data_ptr<float>(),
+                       n > 0 ? reinterpret_cast<const ll_key_t*>(plist.data_ptr<int64_t>()) : nullptr, n, (int)V,
+                       n > 0 ? n_id.data_ptr<int64_t>() : nullptr, n > 0 ? n_lp.data_ptr<float>() : nullptr);
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "lmhead_lse: the merge kernel's launch failed");
+  };
+  if (n > 0) merge(lmhead_lse_merge_kernel<true>);
+  else merge(lmhead_lse_merge_kernel<false>);
+  if (n > 0) return {token_lp, top_id, top_lp, x_t, lse, n_id, n_lp};
   return {token_lp, top_id, top_lp, x_t, lse};
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> lmhead_lse(torch::Tensor h, torch::Tensor w,
-                                                                   c10::optional<torch::Tensor> bias,
-                                                                   torch::Tensor targets, int64_t splits) {
-  auto r = lmhead_lse_raw(h, w, bias, targets, splits);
-  return {r[0], r[1], r[2]};
 }

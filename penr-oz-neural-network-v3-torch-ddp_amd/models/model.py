@@ -448,16 +448,20 @@ class NeuralNetworkModel(nn.Module):
         return None
 
     @torch.inference_mode()
-    def score_tokens(self, sequences: list, block_size: int) -> list[dict]:
+    def score_tokens(self, sequences: list, block_size: int, top_n: int = 0) -> list[dict]:
         """Log-probabilities of given tokens (ops/prompt_logprobs.py): one dict per sequence with
         ``token_logprobs``, ``top_tokens`` and ``top_logprobs``, each as long as the sequence; position i
         holds the score of token i given the tokens before it, position 0 None. Sequences of 2 to
         ``block_size`` tokens, of any lengths: they are right-padded as a ragged prefill is (ops/ragged.py;
         attention is causal, so real positions do not see the pads), run once through every layer in front
         of the vocabulary projection with any KV cache detached, and the real rows are scored in one
-        ``score_rows`` call — on the GPU without any ``[rows, V]`` logits. ValueError, before any forward
-        pass, for a bad length or token id, or a layer list that does not end in a linear (+ softmax)."""
+        ``score_rows`` call — on the GPU without any ``[rows, V]`` logits. ``top_n`` n in 1..20 adds
+        ``top_n``: per position the ``[id, logprob]`` pairs of its n most likely tokens, best first (None at
+        position 0), selected in the same sweep. ValueError, before any forward pass, for a bad length, token
+        id or ``top_n``, or a layer list that does not end in a linear (+ softmax)."""
         head_i = self._head_index()
+        if isinstance(top_n, bool) or not isinstance(top_n, int) or not 0 <= top_n <= plp_ops.MAX_TOP_N:
+            raise ValueError(f"top_n must be an int in [0, {plp_ops.MAX_TOP_N}], got {top_n!r}")
         seqs = plp_ops.check_sequences(sequences, block_size, None if head_i is None else self._vocab_size())
         self.eval()
         device = next(self.parameters()).device
@@ -482,7 +486,7 @@ class NeuralNetworkModel(nn.Module):
             # a 16-bit projection reads its input in its own type (under autocast a LayerNorm hands it fp32
             # rows and the linear rounds them): those rounded rows are the operand
             h = h.to(head.weight.dtype)
-        return plp_ops.to_dicts(lens, *plp_ops.score_rows(h, head.weight, head.bias, targets))
+        return plp_ops.to_dicts(lens, *plp_ops.score_rows(h, head.weight, head.bias, targets, top_n))
 
     def _prepare_generation(self, input_context: list, max_new_tokens: int, temperature: float, top_k: int | None,
                             stop_token: int | None = None, **options):
@@ -549,7 +553,7 @@ class NeuralNetworkModel(nn.Module):
                         stop: list | None = None, logit_bias: dict | None = None,
                         banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                         min_tokens: int | None = None, speculate: int | None = None,
-                        prompt_logprobs: bool | None = None):
+                        prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None):
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
         "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
@@ -575,13 +579,15 @@ class NeuralNetworkModel(nn.Module):
         ``prompt_logprobs`` True (ops/prompt_logprobs.py): the call first scores row 0's prompt
         (``score_tokens``, a prompt pass of its own), then generates exactly as without it, and returns
         ``(tokens, info)`` with ``info["prompt_logprobs"]`` = ``score_tokens``' dict beside whatever ``logprobs`` /
-        ``stop`` put there. The prompt needs 2 to ``block_size`` tokens; not together with ``speculate``."""
+        ``stop`` put there. The prompt needs 2 to ``block_size`` tokens; not together with ``speculate``.
+        ``prompt_top_logprobs`` n in 1..20, with ``prompt_logprobs`` only: that dict also holds ``top_n``, the n
+        most likely tokens of every prompt position (``score_tokens``' ``top_n``). None or 0: off."""
         options = _keywords(locals())
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
                                             stop_token, **options, call_shape=call_shape_of(input_context, block_size))
         if prepared[2].prompt_logprobs:  # every step below sees the options of the call without it
-            scored = self.score_tokens([prepared[0][0].tolist()], block_size)[0]
-            plain = (prepared[0], prepared[1], replace(prepared[2], prompt_logprobs=False))
+            scored = self.score_tokens([prepared[0][0].tolist()], block_size, prepared[2].prompt_top_logprobs)[0]
+            plain = (prepared[0], prepared[1], replace(prepared[2], prompt_logprobs=False, prompt_top_logprobs=0))
             res = [t for t in self._generate(*plain, block_size, max_new_tokens, full_context=True)][-1]
             return _with_prompt_scores(res, scored, rows=False)
         if prepared[2].speculate:
@@ -598,12 +604,12 @@ class NeuralNetworkModel(nn.Module):
                                stop: list | None = None, logit_bias: dict | None = None,
                                banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                                min_tokens: int | None = None, speculate: int | None = None,
-                               prompt_logprobs: bool | None = None):
+                               prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None):
         """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``. With
         ``stop`` the stream ends with the token that completes a stop sequence. ``logit_bias`` /
         ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in ``generate_tokens``.
-        ``speculate`` is refused here: a speculative step emits several tokens at once. So is
-        ``prompt_logprobs``: a prompt's scores come with a finished call."""
+        ``speculate`` is refused here: a speculative step emits several tokens at once. So are
+        ``prompt_logprobs`` and ``prompt_top_logprobs``: a prompt's scores come with a finished call."""
         options = _keywords(locals())
         log.info("Streaming token generation started")
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
@@ -845,7 +851,7 @@ class NeuralNetworkModel(nn.Module):
                        stop: list | None = None, logit_bias: dict | None = None,
                        banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                        min_tokens: int | None = None, speculate: int | None = None,
-                       prompt_logprobs: bool | None = None):
+                       prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None):
         """All rows' contexts (the reference returns row 0 only — bug 5). With ``logprobs`` n:
         ``(contexts, [info per row])``, each ``info`` (``generate_tokens``) as long as that row's
         returned continuation. With ``stop`` (ops/stopping.py) every row finishes on its own: the
@@ -863,16 +869,17 @@ class NeuralNetworkModel(nn.Module):
         ``speculate``: as in ``generate_tokens``, for a batch of one row.
         ``prompt_logprobs`` True: every row's prompt is scored first, in one ``score_tokens`` call (rows of any
         lengths, 2 to ``block_size`` tokens each); then the call runs as without it and returns
-        ``(contexts, [info per row])`` with ``info["prompt_logprobs"]`` per row."""
+        ``(contexts, [info per row])`` with ``info["prompt_logprobs"]`` per row; ``prompt_top_logprobs`` n adds
+        ``top_n`` to each, as in ``generate_tokens``."""
         options = _keywords(locals())
-        if prompt_logprobs:  # checked with every other option before anything runs; the rest is the call without it
-            check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
-                          call_shape=call_shape_of(input_context, block_size))
+        if prompt_logprobs or prompt_top_logprobs:  # checked with every other option before anything runs; the rest is the call without them
+            top_n = check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
+                                  call_shape=call_shape_of(input_context, block_size)).prompt_top_logprobs
             nested = isinstance(input_context, (list, tuple)) and len(input_context) > 0 and \
                 isinstance(input_context[0], (list, tuple))
-            scored = self.score_tokens(input_context if nested else [input_context], block_size)
+            scored = self.score_tokens(input_context if nested else [input_context], block_size, top_n)
             plain = self.generate_batch(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
-                                        **{**options, "prompt_logprobs": None})
+                                        **{**options, "prompt_logprobs": None, "prompt_top_logprobs": None})
             return _with_prompt_scores(plain, scored, rows=True)
         lens = ragged_ops.ragged_lengths(input_context)
         prompts = None

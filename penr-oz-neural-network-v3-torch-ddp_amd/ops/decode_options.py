@@ -45,6 +45,7 @@ class DecodeOptions:
     min_tokens: int = 0
     speculate: int | None = None  # ``check_speculate``'s k in 1..3 (ops/speculative.py); None: off
     prompt_logprobs: bool = False  # the call also scores its prompt (ops/prompt_logprobs.py)
+    prompt_top_logprobs: int = 0  # ... and reports this many most likely tokens per prompt position (0: none)
     asked: str = field(default="", compare=False, repr=False)  # the options as given, in the words of the log line
 
     def describe(self) -> str:
@@ -62,7 +63,8 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
                   logprobs: int | None = None, stop: list | None = None, logit_bias: dict | None = None,
                   banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                   min_tokens: int | None = None, speculate: int | None = None,
-                  prompt_logprobs: bool | None = None, call_shape: dict | None = None) -> DecodeOptions:
+                  prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
+                  call_shape: dict | None = None) -> DecodeOptions:
     """Every check of a generate call, once each, in this order; ValueError for the first that fails.
     ``call_shape`` is no option of the call: what the caller knows of its shape (``rows``, ``prompt_len``,
     ``block_size``, ``stream``), which ``speculate`` is checked against (ops/speculative.py).
@@ -91,6 +93,7 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
     k = spec_ops.check_speculate(speculate, temperature=temperature, active=active, max_new_tokens=max_new_tokens,
                                  **(call_shape or {}))
     scored = plp_ops.check_prompt_logprobs(prompt_logprobs, speculate=k, stream=bool((call_shape or {}).get("stream")))
+    scored_n = plp_ops.check_prompt_top_logprobs(prompt_top_logprobs, prompt_logprobs=scored)
     asked = "" if top_k is None else f" top {top_k}"
     asked += "" if top_p is None else f" top_p {top_p}"
     asked += "" if min_p is None else f" min_p {min_p}"
@@ -104,8 +107,9 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
         asked += "" if not min_tokens else f" min_tokens {min_tokens}"
     asked += "" if k is None else f" speculate {k}"
     asked += "" if not scored else " prompt_logprobs"
+    asked += "" if not scored_n else f" top {scored_n}"
     return DecodeOptions(temperature, top_k, top_p, min_p, quant, penalties, n, seqs, stop_token, bias,
-                         min_tokens or 0, k, scored, asked)
+                         min_tokens or 0, k, scored, scored_n, asked)
 
 
 # the option keywords of the public generate methods: ``check_options``' own, by name

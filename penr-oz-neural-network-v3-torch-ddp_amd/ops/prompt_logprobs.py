@@ -10,6 +10,13 @@ final ``nn.Linear``), ``W [V, C]`` and the optional ``bias [V]`` that linear's p
 * ``top_token[i] = argmax_v x[i, v]``, the lowest id among equal maxima;
 * ``top_logprob[i] = max_v x[i, v] − logsumexp(x[i, :])``.
 
+With ``1 <= n <= 20`` (``top_n``, the option ``prompt_top_logprobs``):
+
+* ``top_n[i]`` = the ``min(n, V)`` pairs ``(v, x[i, v] − logsumexp(x[i, :]))`` with the largest ``x[i, v]``, ordered
+  by logit descending, by token id ascending among equal logits (the order ``ops/logprobs.py`` gives generated
+  tokens), as ``ids int64 [N, n]`` and ``logprobs fp32 [N, n]`` with ``−1`` / ``−inf`` past ``min(n, V)``. Entry 0
+  is ``(top_token[i], top_logprob[i])``.
+
 This differs from the module path (``nn.Linear`` under autocast, ``ops/logprobs.py``), which rounds
 the logits to bf16 before any softmax: the values here are those of the unrounded logits.
 
@@ -17,10 +24,10 @@ For a token sequence ``s`` of length ``L`` with ``2 <= L <= block_size``, positi
 is scored from the hidden row at position ``i − 1`` with target ``s[i]``; position 0 has no score and is
 ``None`` in lists (``NeuralNetworkModel.score_tokens``).
 
-``reference_score`` is the definition in fp64. ``score_rows`` is what runs: for bf16 GPU operands of a
+``reference_score`` and ``reference_top_n`` are the definition in fp64. ``score_rows`` is what runs: for bf16 GPU operands of a
 shape the launcher takes, ``csrc/kernels/lmhead_lse.hip`` — an MFMA kernel that sweeps ``h · Wᵀ`` tile by
-tile and reduces every tile in registers (running maximum, Σexp, best column, target logit), so no
-``[N, V]`` tensor exists; otherwise the same maths in fp32 torch over chunks of rows, which never holds
+tile and reduces every tile in registers (running maximum, Σexp, best column, target logit; with ``top_n``
+the row's n best columns, selected in the same sweep), so no ``[N, V]`` tensor exists; otherwise the same maths in fp32 torch over chunks of rows, which never holds
 more than one bounded ``[chunk, V]`` block.
 """
 from __future__ import annotations
@@ -31,6 +38,7 @@ from torch import Tensor
 from penroz.ops._ext import use_kernels, kernels
 
 CHUNK_ELEMS = 1 << 24  # the torch path's [chunk, V] fp32 block: at most 64 MiB
+MAX_TOP_N = 20  # the kernel's list capacity (kLmheadTopCap, csrc/kernels/host_plan.h); ops/logprobs.py's limit too
 
 
 def check_prompt_logprobs(value, *, speculate=None, stream: bool = False) -> bool:
@@ -44,6 +52,18 @@ def check_prompt_logprobs(value, *, speculate=None, stream: bool = False) -> boo
         raise ValueError("prompt_logprobs does not compose with speculate")
     if value and stream:
         raise ValueError("prompt_logprobs does not stream: the prompt's scores come with the finished call")
+    return value
+
+
+def check_prompt_top_logprobs(value, *, prompt_logprobs: bool) -> int:
+    """``value`` as n in 0..20 (None and 0: off). ValueError unless it is None or such an int (no bool), and
+    for an n > 0 without ``prompt_logprobs`` — whose own check has already refused ``speculate`` and streams."""
+    if value is None:
+        return 0
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= MAX_TOP_N:
+        raise ValueError(f"prompt_top_logprobs must be None or an int in [0, {MAX_TOP_N}], got {value!r}")
+    if value and not prompt_logprobs:
+        raise ValueError("prompt_top_logprobs needs prompt_logprobs: true (the most likely tokens come with the prompt's scores)")
     return value
 
 
@@ -89,6 +109,25 @@ def reference_score(h: Tensor, W: Tensor, bias: Tensor | None, targets: Tensor) 
     return xt - lse, top, best - lse
 
 
+def _top_n_of(x: Tensor, lse: Tensor, n: int) -> tuple[Tensor, Tensor]:
+    """The definition's ``top_n`` of logits ``x [rows, V]``: (ids int64 [rows, n], x − lse in x's type [rows, n]).
+    A stable descending sort keeps equal logits in ascending id order."""
+    order = torch.sort(x, dim=-1, descending=True, stable=True).indices[:, :n]
+    ids = torch.full((x.shape[0], n), -1, dtype=torch.int64, device=x.device)
+    lps = torch.full((x.shape[0], n), float("-inf"), dtype=x.dtype, device=x.device)
+    ids[:, :order.shape[1]] = order
+    lps[:, :order.shape[1]] = x.gather(1, order) - lse.unsqueeze(1)
+    return ids, lps
+
+
+def reference_top_n(h: Tensor, W: Tensor, bias: Tensor | None, n: int) -> tuple[Tensor, Tensor]:
+    """The module docstring's ``top_n`` in fp64: (ids int64 [N, n], logprobs fp64 [N, n]), on the operands' device."""
+    x = h.double() @ W.double().T
+    if bias is not None:
+        x = x + bias.double()
+    return _top_n_of(x, torch.logsumexp(x, dim=-1), n)
+
+
 def kernel_takes(h: Tensor, W: Tensor, bias: Tensor | None = None) -> bool:
     """Whether ``lmhead_lse``'s launcher accepts these operands once they are contiguous — every check it
     makes: bf16 GPU rows of a planned shape, a device bias [V], 16-B aligned data, and h and a column tile
@@ -104,14 +143,21 @@ def kernel_takes(h: Tensor, W: Tensor, bias: Tensor | None = None) -> bool:
     return kernels().lmhead_lse_plan(h.shape[0], W.shape[0], h.shape[1])[0] != 0
 
 
-def score_rows(h: Tensor, W: Tensor, bias: Tensor | None, targets: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+def score_rows(h: Tensor, W: Tensor, bias: Tensor | None, targets: Tensor, top_n: int = 0) -> tuple[Tensor, ...]:
     """(token_logprob fp32 [N], top_token int64 [N], top_logprob fp32 [N]) of the definition: the kernel for
-    operands ``kernel_takes`` admits, otherwise fp32 torch over chunks of rows."""
+    operands ``kernel_takes`` admits, otherwise fp32 torch over chunks of rows. ``top_n`` n in 1..20 appends
+    the definition's ``top_n``: (ids int64 [N, n], logprobs fp32 [N, n])."""
+    if isinstance(top_n, bool) or not 0 <= top_n <= MAX_TOP_N:
+        raise ValueError(f"top_n must be an int in [0, {MAX_TOP_N}], got {top_n!r}")
     targets = targets.to(h.device).long().reshape(-1)
     bias = None if bias is None else bias.to(h.device)
     if kernel_takes(h, W, bias):
+        if top_n:
+            return kernels().lmhead_lse(h.contiguous(), W.contiguous(), bias, targets.contiguous(), top_n=top_n)
         return kernels().lmhead_lse(h.contiguous(), W.contiguous(), bias, targets.contiguous())
     N, V = h.shape[0], W.shape[0]
+    n_ids = torch.empty(N, top_n, dtype=torch.int64, device=h.device)
+    n_lps = torch.empty(N, top_n, dtype=torch.float32, device=h.device)
     lp = torch.empty(N, dtype=torch.float32, device=h.device)
     top_lp = torch.empty_like(lp)
     top = torch.empty(N, dtype=torch.int64, device=h.device)
@@ -126,17 +172,26 @@ def score_rows(h: Tensor, W: Tensor, bias: Tensor | None, targets: Tensor) -> tu
         top[a:a + step] = _lowest_argmax(x, best)
         lp[a:a + step] = x.gather(1, targets[a:a + step].unsqueeze(1)).squeeze(1) - lse
         top_lp[a:a + step] = best - lse
-    return lp, top, top_lp
+        if top_n:
+            n_ids[a:a + step], n_lps[a:a + step] = _top_n_of(x, lse, top_n)
+    return (lp, top, top_lp, n_ids, n_lps) if top_n else (lp, top, top_lp)
 
 
-def to_dicts(lens: list[int], lp: Tensor, top: Tensor, top_lp: Tensor) -> list[dict]:
+def to_dicts(lens: list[int], lp: Tensor, top: Tensor, top_lp: Tensor, n_ids: Tensor | None = None,
+             n_lps: Tensor | None = None) -> list[dict]:
     """The scored rows of sequences of ``lens`` tokens (``len − 1`` rows each, concatenated) as one dict
-    per sequence: ``token_logprobs``, ``top_tokens``, ``top_logprobs``, each ``len`` long with None first."""
+    per sequence: ``token_logprobs``, ``top_tokens``, ``top_logprobs``, each ``len`` long with None first.
+    With ``score_rows``' ``top_n`` pair also ``"top_n"``: None, then per position the ``[id, logprob]`` pairs
+    of its most likely tokens, best first (``min(n, V)`` of them)."""
     lps, tops, top_lps = lp.tolist(), top.tolist(), top_lp.tolist()
+    pairs = None if n_ids is None else [[[i, p] for i, p in zip(ids, ps) if i >= 0]
+                                        for ids, ps in zip(n_ids.tolist(), n_lps.tolist())]
     out, a = [], 0
     for n in lens:
         b = a + n - 1
         out.append({"token_logprobs": [None] + lps[a:b], "top_tokens": [None] + tops[a:b],
                     "top_logprobs": [None] + top_lps[a:b]})
+        if pairs is not None:
+            out[-1]["top_n"] = [None] + pairs[a:b]
         a = b
     return out

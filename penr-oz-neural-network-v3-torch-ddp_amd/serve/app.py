@@ -194,6 +194,11 @@ class GenerateRequest(ModelRequest):
                                                     "it, the most likely token and its log-probability (null at "
                                                     "position 0); one object, a list of them with batch; prompts of 2 "
                                                     "to block_size tokens; not with stream or speculate")
+    prompt_top_logprobs: StrictInt | None = Field(None, ge=0, le=20, examples=[None],
+                                                  description="With prompt_logprobs: also \"top_n\", per prompt position "
+                                                              "this many most likely tokens with their log-probabilities, "
+                                                              "best first ([id, logprob] pairs; null at position 0); null "
+                                                              "or 0: off")
     stream: bool = Field(False, examples=[False], description="Stream tokens as text/plain lines")
     batch: bool = Field(False, examples=[False],
                         description="Return every row: {\"sequences\": [[...], ...]}, each row's prompt plus its "
@@ -517,6 +522,8 @@ def model_generate(body: GenerateRequest = Body(...)):
         penalties["speculate"] = early.speculate
     if early.prompt_logprobs:  # (likewise; never with stream or speculate: the early check refused those)
         penalties["prompt_logprobs"] = True
+    if early.prompt_top_logprobs:  # (likewise)
+        penalties["prompt_top_logprobs"] = early.prompt_top_logprobs
 
     def with_prompt_scores(out: dict, scores) -> dict:
         if scores is not None:
