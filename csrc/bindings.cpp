@@ -89,6 +89,14 @@ torch::Tensor prefill_attn(torch::Tensor q, torch::Tensor kc, torch::Tensor vc, 
                            c10::optional<torch::Tensor> v_scale, int64_t S, int64_t q_offset, double scale);
 std::tuple<bool, int64_t, int64_t, int64_t, int64_t> prefill_attn_plan(int64_t B, int64_t Tq, int64_t H, int64_t Hkv,
                                                                        int64_t D, bool q_bf16, const std::string& cache);
+// shared_prefix_attn.hip
+torch::Tensor shared_prefix_attn(torch::Tensor q, torch::Tensor k_new, torch::Tensor v_new, torch::Tensor kp,
+                                 torch::Tensor vp, torch::Tensor ks, torch::Tensor vs, torch::Tensor prefix_t,
+                                 torch::Tensor len_t, double scale, int64_t splits);
+std::tuple<bool, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t> shared_prefix_plan(int64_t R, int64_t H, int64_t Hkv,
+                                                                                         int64_t D, int64_t capP,
+                                                                                         int64_t splits);
+std::vector<std::pair<int64_t, int64_t>> shared_prefix_ranges(int64_t P, int64_t S);
 // lmhead_lse.hip
 std::vector<torch::Tensor> lmhead_lse_raw(torch::Tensor h, torch::Tensor w, c10::optional<torch::Tensor> bias,
                                           torch::Tensor targets, int64_t splits, int64_t top_n);
@@ -343,6 +351,18 @@ PYBIND11_MODULE(penroz_kernels, m) {
   m.def("prefill_attn_plan", &prefill_attn_plan, pybind11::arg("B"), pybind11::arg("Tq"), pybind11::arg("H"),
         pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("q_bf16") = true, pybind11::arg("cache") = "bf16",
         "prefill_attn's plan: (admitted, tile rows, positions per tile, workgroups, LDS bytes) (host only)");
+  m.def("shared_prefix_attn", &shared_prefix_attn, pybind11::arg("q"), pybind11::arg("k_new"), pybind11::arg("v_new"),
+        pybind11::arg("kp"), pybind11::arg("vp"), pybind11::arg("ks"), pybind11::arg("vs"), pybind11::arg("prefix_t"),
+        pybind11::arg("len_t"), pybind11::arg("scale"), pybind11::arg("splits") = 0,
+        "one decode step of R samples of one prompt: q [R, H, D] over the prefix cache [1, Hkv, capP, D] (first *prefix_t "
+        "slots) and each row's suffix cache [R, Hkv, capS, D] (*len_t - *prefix_t slots, the last written from k_new / "
+        "v_new) -> [R, H·D]; splits > 0 forces the prefix key ranges");
+  m.def("shared_prefix_plan", &shared_prefix_plan, pybind11::arg("R"), pybind11::arg("H"), pybind11::arg("Hkv"),
+        pybind11::arg("D"), pybind11::arg("capP"), pybind11::arg("splits") = 0,
+        "shared_prefix_attn's plan: (admitted, query-tile rows, query tiles per KV head, key ranges S, workgroups of "
+        "launch 1, LDS bytes, fp32 workspace floats) (host only)");
+  m.def("shared_prefix_ranges", &shared_prefix_ranges, pybind11::arg("P"), pybind11::arg("S"),
+        "the S prefix workgroups' key ranges [first, second) at prefix length P, as the kernel derives them (host only)");
   m.def("lmhead_lse",
         [](torch::Tensor h, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor targets, int64_t splits,
            int64_t top_n) -> pybind11::tuple {

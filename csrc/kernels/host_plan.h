@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <utility>
 
 namespace penroz {
 
@@ -409,6 +410,54 @@ inline PrefillAttnPlan plan_prefill_attn(int64_t B, int64_t Tq, int64_t H, int64
   const int keys = prefill_keys((int)D);
   const int lds = 4 * keys * (int)D * 2 + (D >= 256 ? 32 * waves * (int)D * 2 : 0) + (cache == CacheKind::I8 ? 4 * keys * 4 : 16);
   return {true, 32 * waves, (int)(32 * waves / G), grid, lds};
+}
+
+// ---- shared-prefix decode attention launch plan (shared_prefix_attn.hip) ----
+// R rows (samples of one prompt) against one prefix cache of capP slots and their own suffix caches. Built:
+// bf16, head_dim 64 / 128 / 256, H / Hkv 1 / 2 / 4 / 8, 2-64 rows; everything else is refused and the caller
+// runs the replicated call.
+constexpr int kSharedPrefixMaxSplits = 16, kSharedPrefixFillWgs = 512, kSharedPrefixMaxRows = 64;
+struct SharedPrefixPlan {
+  bool ok;            // admitted; everything below is 0 when not
+  int tile_rows;      // packed (row, group head) query rows per prefix workgroup: 32, 64 or 128
+  int tiles;          // query tiles per KV head
+  int splits;         // S: key ranges of the prefix, one workgroup per (KV head, query tile, range)
+  int64_t grid;       // launch 1: Hkv · tiles · S prefix workgroups, then R · Hkv suffix workgroups
+  int lds_bytes;      // the larger of the two kinds' LDS
+  int64_t ws_floats;  // fp32 workspace: S + 1 partials (o[D], m, l) per (row, head)
+};
+
+// The query tile is the narrowest of 32 / 64 / 128 rows that holds the R·G packed rows of a KV head (128 when
+// they are more: several tiles), so a staged K / V tile serves as many rows as there are. S aims at two
+// workgroups per CU in launch 1 — the suffix workgroups count for at most half of them, they are short — is
+// capped at kSharedPrefixMaxSplits (every range costs a partial per row and head) and at the 64-key tiles of
+// the capacity. It is fixed here, from the capacity, so a captured graph keeps it; the kernel derives the
+// range bounds from the device-side length. splits_forced > 0 (tests, A/B) replaces S, up to the cap.
+inline SharedPrefixPlan plan_shared_prefix(int64_t R, int64_t H, int64_t Hkv, int64_t D, int64_t capP, int splits_forced = 0) {
+  const int64_t G = Hkv > 0 && H % Hkv == 0 ? H / Hkv : 0;
+  if (R < 2 || R > kSharedPrefixMaxRows || capP < 1 || capP > (int64_t(1) << 22) || !(D == 64 || D == 128 || D == 256) ||
+      !(G == 1 || G == 2 || G == 4 || G == 8) || Hkv > 1024)
+    return {false, 0, 0, 0, 0, 0, 0};
+  const int64_t rows = R * G;
+  const int tile_rows = rows <= 32 ? 32 : rows <= 64 ? 64 : 128;
+  const int64_t tiles = (rows + tile_rows - 1) / tile_rows;
+  const int64_t suffix = R * Hkv, key_tiles = (capP + 63) / 64;
+  int64_t s = (kSharedPrefixFillWgs - std::min<int64_t>(suffix, kSharedPrefixFillWgs / 2) + Hkv * tiles - 1) / (Hkv * tiles);
+  s = std::max<int64_t>(1, std::min<int64_t>({s, key_tiles, kSharedPrefixMaxSplits}));
+  if (splits_forced > 0) s = std::min<int64_t>(splits_forced, kSharedPrefixMaxSplits);
+  const int keys = prefill_keys((int)D);
+  const int prefix_lds = 4 * keys * (int)D * 2 + (D >= 256 ? tile_rows * (int)D * 2 : 0) + 16;
+  const int suffix_keys = D * 2 * 256 <= 32768 ? 256 : (int)(32768 / (D * 2));
+  const int suffix_lds = 32768 + 8 * (int)D * 4 + 8 * suffix_keys * 4 + 80 * 4;
+  return {true, tile_rows, (int)tiles, (int)s, Hkv * tiles * s + suffix, std::max(prefix_lds, suffix_lds),
+          (s + 1) * R * H * (D + 2)};
+}
+
+// The key range of prefix workgroup s at prefix length P, as the kernel derives it: [first, second), empty
+// (first >= second) when the range starts at or beyond P.
+inline std::pair<int64_t, int64_t> shared_prefix_range(int64_t P, int S, int s) {
+  const int64_t per = (((P + 63) / 64 + S - 1) / S) * 64;
+  return {s * per, std::min<int64_t>(P, (s + 1) * per)};
 }
 
 // ---- lm_head scoring launch plan (lmhead_lse.hip) ----

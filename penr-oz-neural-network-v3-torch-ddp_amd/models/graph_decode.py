@@ -67,6 +67,12 @@ between steps lives on the device:
   step's rows, all on the device. ``run_speculative`` replays bursts of steps without a host synchronisation
   per step and reads the history's new part once per burst.
 
+* ``n`` samples of one prompt (``ops/shared_prefix.py``): a ``GraphDecoder`` with ``shared_prefix=True`` keeps the
+  prompt's K/V once, in a batch-1 prefix cache that the eager prompt pass fills, and a suffix cache per row for
+  the tokens the rows generate (``SharedPrefixKVCache``); ``_attend_graph`` is one call of
+  ``csrc/kernels/shared_prefix_attn.hip``, which reads the prefix length and the total length from the device.
+  The step is the uniform step otherwise: one ``pos_t``, one ``len_t``, the same programs and sampler.
+
 The host only tracks the cache length (one per replay) to switch to the reference's
 sliding-window re-prefill when the window is full, and copies each burst of tokens back once
 (stop-token checks per burst). Prefill and re-prefill run eagerly. RoPE models (Gemma) rotate
@@ -232,6 +238,64 @@ class StaticTurboKVCache(_GraphMode, kvc.TurboQuantKVCache):
         _ext.kernels().kv_append(k, v, self._k[l], self._v[l], self._sk[l], self._sv[l], self.pos_t, 0)
         return attn_ops.decode_attention(q, self._k[l], self._v[l], self._k[l].shape[2], self._sk[l], self._sv[l],
                                          seq_len_dev=self.len_t)
+
+
+class SharedPrefixKVCache(_GraphMode, kvc.KVCache):
+    """The cache of an ``n`` call (ops/shared_prefix.py). Prefix side: this batch-1 bf16 ``KVCache``, which the
+    eager prompt pass fills through the module path (``prefill_attn.hip``, as for any prompt). Suffix side: per
+    layer ``[rows, Hkv, suffix_capacity, D]``, allocated by the warm-up step, and ``prefix_t``, the prompt's length
+    on the device. ``seq_len`` counts prompt and generated tokens together; ``len_t`` is that plus one."""
+
+    def init_shared(self, rows: int, suffix_capacity: int, device):
+        self.rows, self.suffix_capacity = rows, suffix_capacity
+        self.prefix_t = torch.zeros(1, dtype=torch.long, device=device)
+        self.prefix_len: int | None = None  # set by the first burst after a prompt pass
+        self._ks: list[Tensor | None] = [None] * self.num_layers
+        self._vs: list[Tensor | None] = [None] * self.num_layers
+
+    def clear(self):
+        super().clear()
+        self.prefix_len = None
+
+    def _attend_graph(self, l: int, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
+        kp, vp = self._k[l], self._v[l]
+        if self._ks[l] is None:  # (the warm-up step, outside any capture)
+            shape = (self.rows, kp.shape[1], self.suffix_capacity, kp.shape[3])
+            self._ks[l], self._vs[l] = kp.new_zeros(shape), kp.new_zeros(shape)
+        return attn_ops.shared_prefix_attention(q.squeeze(1), k.squeeze(1), v.squeeze(1), kp, vp, self._ks[l],
+                                                self._vs[l], self.prefix_t, self.len_t)
+
+
+def _attention_shapes(model) -> list[tuple[int, int, int]]:
+    """(H, Hkv, D) of every attention layer of a model with a decode program."""
+    prog = GPTDecodeProgram.build(model)
+    if prog is not None:
+        return [(prog.spec.H, prog.spec.H, prog.spec.D)]
+    return [(a.num_heads, a.num_kv_heads, a.head_dim) for a in model._find_attention_layers()]
+
+
+def shared_prefix_splits(model, rows: int, capacity: int) -> int:
+    """The prefix key ranges S of the shared-prefix kernel's plan for the model's first attention layer."""
+    H, Hkv, D = _attention_shapes(model)[0]
+    return int(_ext.kernels().shared_prefix_plan(rows, H, Hkv, D, capacity)[3])
+
+
+def shared_prefix_fallback(model, rows: int, capacity: int) -> str | None:
+    """Why an ``n`` call of ``rows`` samples runs as the replicated batch, or None: the shared-prefix step
+    serves it. What ``get_decoder(shared_prefix=True)`` needs, asked before the call's first forward pass."""
+    from penroz.ops import shared_prefix as sp_ops
+    if not sp_ops.enabled():
+        return "PENROZ_SHARED_PREFIX=0"
+    if not applicable(model):
+        return "no captured decode step here: CPU, PENROZ_GRAPH_DECODE=0 or a model it does not take"
+    if not ragged_program_ok(model):
+        return "the model has no decode program (bf16 GPT-2-pattern or Gemma-family, PENROZ_DECODE_PROGRAM=1)"
+    if kvc.TURBO_QUANT_ENABLED:
+        return "the int8 KV cache: the kernel takes bf16 caches"
+    shapes = _attention_shapes(model)
+    if not all(attn_ops.shared_prefix_applies(rows, H, Hkv, D, capacity) for H, Hkv, D in shapes):
+        return f"the kernel's plan refuses {rows} rows at heads {sorted(set(shapes))}"
+    return None
 
 
 def _qkv_views(qkv: Tensor, H: int, Hkv: int, D: int):
@@ -754,7 +818,8 @@ class GraphDecoder:
 
     def __init__(self, model, rows: int, capacity: int, temperature: float, top_k: int | None,
                  top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None,
-                 ragged: bool = False, speculate: int | None = None):
+                 ragged: bool = False, speculate: int | None = None, shared_prefix: bool = False,
+                 suffix_capacity: int | None = None):
         # weak: the model caches its decoders (model.__dict__), so a strong reference would make a
         # cycle that only the cyclic GC frees — and a collection that runs while ANOTHER graph is
         # being captured destroys this one's graph mid-capture (a hard abort)
@@ -763,6 +828,11 @@ class GraphDecoder:
         self.attn = model._find_attention_layers()
         self.pos_layers = model._find_position_embeddings()
         cls = StaticTurboKVCache if kvc.TURBO_QUANT_ENABLED else StaticKVCache
+        # n samples of one prompt (ops/shared_prefix.py): ``rows`` rows over one prefix cache and their own suffixes
+        self.shared_prefix = bool(shared_prefix)
+        assert not self.shared_prefix or not (ragged or speculate or kvc.TURBO_QUANT_ENABLED), (ragged, speculate)
+        if self.shared_prefix:
+            cls = SharedPrefixKVCache
         self.cache = cls(len(self.attn), capacity)
         # ragged (ops/ragged.py): every row at its own position and cache length — pos_t / len_t are [rows]
         self.ragged = bool(ragged)
@@ -772,6 +842,8 @@ class GraphDecoder:
             (rows, speculate, ragged, temperature)
         self.cache.init_graph_state(self.device, rows if self.ragged or self.speculate else None,
                                     shared=bool(self.speculate))
+        if self.shared_prefix:
+            self.cache.init_shared(rows, int(suffix_capacity or capacity), self.device)
         self._lens_t: Tensor | None = None  # the call's prompt lengths [rows] (device) and the longest
         self._lmax = 0
         self.rows, self.capacity = rows, capacity
@@ -787,6 +859,8 @@ class GraphDecoder:
         attn_ops.decode_counters(self.device)  # (the decode attention's split-merge counters too)
         gemm_ops.load_tuned_gemms()  # measured hipBLASLt solutions for the decode-shaped GEMMs too
         self.program = GPTDecodeProgram.build(model) or GemmaDecodeProgram.build(model)
+        if self.shared_prefix and (self.program is None or not _ext.available()):
+            raise ValueError("a shared-prefix decoder needs a decode program and the built kernels")
         if self.ragged and self.program is None:
             raise ValueError("a ragged decoder needs a decode program (bf16 GPT-2-pattern or Gemma-family model)")
         if self.speculate:
@@ -1090,6 +1164,12 @@ class GraphDecoder:
         assert 0 < cache_len and cache_len + n_steps <= self.capacity, (cache_len, n_steps, self.capacity)
         assert not self.ragged or cache_len >= self._lmax, (cache_len, self._lmax)
         lens = self._row_lengths(cache_len)
+        if self.shared_prefix:
+            if self.cache.prefix_len is None:  # the first burst behind the prompt pass: what the cache holds is the prefix
+                self.cache.prefix_len = cache_len
+                self.cache.prefix_t.fill_(cache_len)
+            assert cache_len + n_steps - self.cache.prefix_len <= self.cache.suffix_capacity, \
+                (cache_len, n_steps, self.cache.prefix_len, self.cache.suffix_capacity)
         if self.graph is None:
             self._capture(last_tok, lens, start)
         else:
@@ -1141,7 +1221,8 @@ def _normalise_filters(temperature: float, top_p: float | None, min_p: float | N
 def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: int | None,
                 top_p: float | None = None, min_p: float | None = None,
                 weight_quant: str | None = None, ragged: bool = False,
-                speculate: int | None = None) -> GraphDecoder | None:
+                speculate: int | None = None, shared_prefix: bool = False,
+                suffix_capacity: int | None = None) -> GraphDecoder | None:
     """Cached per model and (rows, block size, sampling settings, weights identity, ragged or not, weight
     format in effect for ``weight_quant`` — as ``ops.weight_quant.resolve`` returned it); None when the
     model does not qualify (CPU, no attention, RoPE head_dim without a decode kernel) or ``PENROZ_GRAPH_DECODE=0``
@@ -1150,7 +1231,7 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
     # before its options are checked, so a third belongs there too: tests/test_ragged.py ties the two together)
     if not applicable(model):
         return None
-    if (ragged or speculate) and not ragged_program_ok(model):
+    if (ragged or speculate or shared_prefix) and not ragged_program_ok(model):
         return None
     p = next(model.parameters())
     # weights identity AND version: in-place updates (training) re-capture, so nothing captured
@@ -1161,6 +1242,8 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
             bool(ragged))
     if speculate:  # (a plain decoder's key is what it always was)
         base += (("speculate", int(speculate)),)
+    if shared_prefix:  # (likewise): another cache, and the suffix capacity sizes it
+        base += (("shared_prefix", int(suffix_capacity or block_size)),)
     cache = model.__dict__.setdefault("_graph_decoders", {})
     # the key holds the weight format IN EFFECT: a request for int8 that this step cannot honour
     # (more than 4 rows, no decode program, a K that does not fit) shares the bf16 decoder instead of
@@ -1171,7 +1254,9 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
     dec = cache.get(base + (weight_quant,))
     if dec is None:
         spec = {"speculate": int(speculate)} if speculate else {}
-        dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p, weight_quant, ragged=ragged, **spec)
+        shared = {"shared_prefix": True, "suffix_capacity": suffix_capacity} if shared_prefix else {}
+        dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p, weight_quant, ragged=ragged,
+                           **spec, **shared)
         if dec.weight_quant != weight_quant:  # asked for int8, runs bf16
             if len(unused) >= 64:
                 unused.clear()
@@ -1185,11 +1270,14 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
     return dec
 
 
-def decoder_for(model, rows: int, block_size: int, opts, ragged: bool = False) -> GraphDecoder | None:
-    """``get_decoder`` for a generate call's checked options (``ops.decode_options.DecodeOptions``)."""
+def decoder_for(model, rows: int, block_size: int, opts, ragged: bool = False,
+                suffix_capacity: int | None = None) -> GraphDecoder | None:
+    """``get_decoder`` for a generate call's checked options (``ops.decode_options.DecodeOptions``).
+    ``suffix_capacity``: the call is an ``n`` call on the shared-prefix step, its rows generate at most this many."""
     ragged = {"ragged": True} if ragged else {}  # (a rectangular call's lookup is what it always was)
+    shared = {"shared_prefix": True, "suffix_capacity": suffix_capacity} if suffix_capacity is not None else {}
     if opts.speculate:  # k + 1 rows for the call's one sequence
         return get_decoder(model, opts.speculate + 1, block_size, 0.0, None, weight_quant=opts.weight_quant,
                            speculate=opts.speculate)
     return get_decoder(model, rows, block_size, opts.temperature, opts.top_k, opts.top_p, opts.min_p,
-                       opts.weight_quant, **ragged)
+                       opts.weight_quant, **ragged, **shared)

@@ -26,6 +26,7 @@ micro-step losses all-reduced as an average, rank data stride ``B·T·rank`` /
 """
 from __future__ import annotations
 
+import copy
 import logging
 import os
 import random
@@ -47,6 +48,7 @@ from penroz.models.mapper import Mapper
 from penroz.ops import logprobs as lp_ops
 from penroz.ops import prompt_logprobs as plp_ops
 from penroz.ops import ragged as ragged_ops
+from penroz.ops import shared_prefix as sp_ops
 from penroz.ops import speculative as spec_ops
 from penroz.ops import stopping as stop_ops
 from penroz.ops.decode_options import KEYWORDS, DecodeCall, DecodeOptions, check_options
@@ -82,15 +84,17 @@ def _rectangular(input_context: list) -> list:
     return input_context
 
 
-def call_shape_of(input_context, block_size: int, stream: bool = False) -> dict:
-    """What ``check_options`` checks ``speculate`` against: the call's rows, prompt length and window, as far
-    as ``input_context`` shows them (a malformed one is refused where it always was)."""
+def call_shape_of(input_context, block_size: int, stream: bool = False, single: bool = False) -> dict:
+    """What ``check_options`` checks ``speculate`` and ``n`` against: the call's rows, prompt length and window, as
+    far as ``input_context`` shows them (a malformed one is refused where it always was). ``single``: the caller
+    returns one row (``generate_tokens`` / ``generate_tokens_stream``), which an ``n`` call is refused for."""
     rows = prompt_len = None
     if isinstance(input_context, (list, tuple)) and len(input_context) > 0:
         nested = isinstance(input_context[0], (list, tuple))
         rows = len(input_context) if nested else 1
         prompt_len = max(len(r) for r in input_context if isinstance(r, (list, tuple))) if nested else len(input_context)
-    return {"rows": rows, "prompt_len": prompt_len, "block_size": block_size, "stream": stream}
+    shape = {"rows": rows, "prompt_len": prompt_len, "block_size": block_size, "stream": stream}
+    return {**shape, "single": True} if single else shape
 
 
 def _with_prompt_scores(result, scored, rows: bool):
@@ -115,6 +119,8 @@ class NeuralNetworkModel(nn.Module):
     SHM_PATH = ckpt.detect_shm_path()
     # the last speculative generate call's {"steps", "drafted", "accepted"} (ops/speculative.py); None: none yet
     last_speculation: dict | None = None
+    # an ``n`` call that ran on the shared-prefix step (ops/shared_prefix.py): {"rows", "prefix_len", "splits"}; else None
+    last_shared_prefix: dict | None = None
 
     def __init__(self, model_id: str, mapper: Mapper):
         super().__init__()
@@ -553,7 +559,8 @@ class NeuralNetworkModel(nn.Module):
                         stop: list | None = None, logit_bias: dict | None = None,
                         banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                         min_tokens: int | None = None, speculate: int | None = None,
-                        prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None):
+                        prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
+                        n: int | None = None):
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
         "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
@@ -581,10 +588,12 @@ class NeuralNetworkModel(nn.Module):
         ``(tokens, info)`` with ``info["prompt_logprobs"]`` = ``score_tokens``' dict beside whatever ``logprobs`` /
         ``stop`` put there. The prompt needs 2 to ``block_size`` tokens; not together with ``speculate``.
         ``prompt_top_logprobs`` n in 1..20, with ``prompt_logprobs`` only: that dict also holds ``top_n``, the n
-        most likely tokens of every prompt position (``score_tokens``' ``top_n``). None or 0: off."""
+        most likely tokens of every prompt position (``score_tokens``' ``top_n``). None or 0: off.
+        ``n``: ``generate_batch``'s; here only None or 1 (this method returns one row)."""
         options = _keywords(locals())
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
-                                            stop_token, **options, call_shape=call_shape_of(input_context, block_size))
+                                            stop_token, **options,
+                                            call_shape=call_shape_of(input_context, block_size, single=True))
         if prepared[2].prompt_logprobs:  # every step below sees the options of the call without it
             scored = self.score_tokens([prepared[0][0].tolist()], block_size, prepared[2].prompt_top_logprobs)[0]
             plain = (prepared[0], prepared[1], replace(prepared[2], prompt_logprobs=False, prompt_top_logprobs=0))
@@ -604,7 +613,8 @@ class NeuralNetworkModel(nn.Module):
                                stop: list | None = None, logit_bias: dict | None = None,
                                banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                                min_tokens: int | None = None, speculate: int | None = None,
-                               prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None):
+                               prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
+                               n: int | None = None):
         """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``. With
         ``stop`` the stream ends with the token that completes a stop sequence. ``logit_bias`` /
         ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in ``generate_tokens``.
@@ -614,13 +624,13 @@ class NeuralNetworkModel(nn.Module):
         log.info("Streaming token generation started")
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
                                             stop_token, **options,
-                                            call_shape=call_shape_of(input_context, block_size, stream=True))
+                                            call_shape=call_shape_of(input_context, block_size, stream=True, single=True))
         yield from self._generate(*prepared, block_size, max_new_tokens, full_context=False)
         log.info("Streaming token generation completed")
 
     def _token_bursts(self, context: Tensor, block_size: int, max_new_tokens: int, softmax_layer,
                       opts: DecodeOptions, burst: int, stop_run: stop_ops.StopRun | None = None,
-                      lens: list[int] | None = None):
+                      lens: list[int] | None = None, shared: bool = False):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
         (cache full) run eagerly, exactly as the per-token path. The call keeps one ``DecodeCall``
@@ -643,10 +653,16 @@ class NeuralNetworkModel(nn.Module):
         right-padded to the longest, the decoder is a ragged one (the caller made sure there is one), row
         b's first token comes from the prefill's logits at ``lens[b] - 1`` and every graph step runs row b
         at its own position; the generated tokens are appended behind the padded prompts, and the window
-        never slides (``check_prompts``)."""
+        never slides (``check_prompts``).
+        ``shared`` (an ``n`` call on the shared-prefix step, ops/shared_prefix.py; the caller made sure there is
+        one): ``context`` is the one prompt expanded to ``opts.n`` rows; the prompt pass runs row 0 alone into the
+        decoder's prefix cache, its last logits serve every row's first token — each row its own draw — and
+        the graph steps run the rows over that prefix and their own suffixes. The window never slides (``check_n``)."""
         from penroz.models import graph_decode
         rows = context.shape[0]
-        dec = graph_decode.decoder_for(self, rows, block_size, opts, ragged=lens is not None)
+        suffix = {"suffix_capacity": -(-max(max_new_tokens, 1) // 64) * 64} if shared else {}
+        dec = graph_decode.decoder_for(self, rows, block_size, opts, ragged=lens is not None, **suffix)
+        assert dec is not None or not shared, "an n call needs the shared-prefix decoder (generate_batch falls back before this)"
         last_index = None
         if lens is not None:
             assert dec is not None, "a ragged call needs the ragged decoder (generate_batch falls back before this)"
@@ -673,7 +689,13 @@ class NeuralNetworkModel(nn.Module):
             last = None
             while remaining > 0:
                 n = cache.seq_len() if cache is not None else 0
-                if dec is None or n == 0 or n >= block_size:
+                if shared and n == 0:
+                    logits = self(context[:1], skip_softmax=True)[0][-1]  # the prompt, once (it fits the window)
+                    logits = logits[:, -1, :] if logits.ndim == 3 else logits
+                    new = call.apply(logits.expand(rows, -1).contiguous(), None)
+                    if opts.logprobs is not None:
+                        new, lps = new[0], tuple(t.unsqueeze(1) for t in new[1])
+                elif dec is None or n == 0 or n >= block_size:
                     new = self._generate_next_token(context, block_size, opts.temperature, opts.top_k, softmax_layer,
                                                     cache, pos, call=call, penalty_new=last,
                                                     last_index=last_index if n == 0 else None)
@@ -684,6 +706,9 @@ class NeuralNetworkModel(nn.Module):
                 else:
                     k = min(remaining, block_size - n, burst)
                     new = dec.run(last, k, start=call.produced)
+                    if shared:
+                        self.last_shared_prefix = {"rows": rows, "prefix_len": dec.cache.prefix_len,
+                                                   "splits": graph_decode.shared_prefix_splits(self, rows, block_size)}
                     lps = dec.last_logprobs
                     call.produced += k
                 context = torch.cat((context, new.to(context.device)), dim=1)
@@ -851,7 +876,8 @@ class NeuralNetworkModel(nn.Module):
                        stop: list | None = None, logit_bias: dict | None = None,
                        banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                        min_tokens: int | None = None, speculate: int | None = None,
-                       prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None):
+                       prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
+                       n: int | None = None):
         """All rows' contexts (the reference returns row 0 only — bug 5). With ``logprobs`` n:
         ``(contexts, [info per row])``, each ``info`` (``generate_tokens``) as long as that row's
         returned continuation. With ``stop`` (ops/stopping.py) every row finishes on its own: the
@@ -870,17 +896,40 @@ class NeuralNetworkModel(nn.Module):
         ``prompt_logprobs`` True: every row's prompt is scored first, in one ``score_tokens`` call (rows of any
         lengths, 2 to ``block_size`` tokens each); then the call runs as without it and returns
         ``(contexts, [info per row])`` with ``info["prompt_logprobs"]`` per row; ``prompt_top_logprobs`` n adds
-        ``top_n`` to each, as in ``generate_tokens``."""
+        ``top_n`` to each, as in ``generate_tokens``.
+        ``n`` k in 2..64 (ops/shared_prefix.py): k independent samples of the ONE prompt given — the call
+        ``generate_batch([prompt] * k, ...)`` with the same return shape, row r drawing from row r's stream; not
+        with ``speculate``, and ``len(prompt) + max_new_tokens <= block_size``. On the GPU the prompt is prefilled
+        and cached once and the decode steps read it once for all rows (``last_shared_prefix`` then holds
+        {"rows", "prefix_len", "splits"}); elsewhere the replicated call runs. None or 1: off."""
         options = _keywords(locals())
+        self.last_shared_prefix = None
+        samples = None
+        if n is not None:  # checked against the call's shape, with every other option, before anything runs
+            samples = check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
+                                    call_shape=call_shape_of(input_context, block_size)).n
+            if samples and not call_shape_of(input_context, block_size)["prompt_len"]:
+                raise ValueError("n samples one prompt: a non-empty list of token ids, or a list holding one")
         if prompt_logprobs or prompt_top_logprobs:  # checked with every other option before anything runs; the rest is the call without them
             top_n = check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
                                   call_shape=call_shape_of(input_context, block_size)).prompt_top_logprobs
             nested = isinstance(input_context, (list, tuple)) and len(input_context) > 0 and \
                 isinstance(input_context[0], (list, tuple))
             scored = self.score_tokens(input_context if nested else [input_context], block_size, top_n)
+            if samples:  # one prompt, scored once, reported with every row as the replicated call reports it
+                scored = [copy.deepcopy(scored[0]) for _ in range(samples)]
             plain = self.generate_batch(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
                                         **{**options, "prompt_logprobs": None, "prompt_top_logprobs": None})
             return _with_prompt_scores(plain, scored, rows=True)
+        if samples:
+            from penroz.models import graph_decode
+            prompt = list(input_context[0]) if isinstance(input_context[0], (list, tuple)) else list(input_context)
+            why = graph_decode.shared_prefix_fallback(self, samples, block_size)
+            if why is not None:
+                sp_ops.log_fallback(why)
+                return self.generate_batch([prompt] * samples, block_size, max_new_tokens, temperature, top_k,
+                                           stop_token, **{**options, "n": None})
+            input_context = [prompt]
         lens = ragged_ops.ragged_lengths(input_context)
         prompts = None
         if speculate:  # checked against the call's shape before anything runs
@@ -900,11 +949,13 @@ class NeuralNetworkModel(nn.Module):
             return [self._generate_speculative(context, sm, opts, block_size, max_new_tokens)]
         logprobs = opts.logprobs
         run = stop_ops.StopRun(opts.stop) if opts.stop is not None else None
+        if opts.n:  # the one prompt as every row's: the penalties' begin, the result's rows
+            context = context[:1].expand(opts.n, -1).contiguous()
         rows, prompt_len = context.shape
         s_done, s_fin = [0] * rows, [0] * rows
         infos = [{"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {} for _ in range(rows)]
         burst = 32 if stop_token is not None else max_new_tokens
-        for new in self._token_bursts(context, block_size, max_new_tokens, sm, opts, burst, run, lens):
+        for new in self._token_bursts(context, block_size, max_new_tokens, sm, opts, burst, run, lens, bool(opts.n)):
             if logprobs is not None:
                 new, lps = new
             keep, stopped = new.shape[1], False

@@ -309,3 +309,31 @@ def decode_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, seq_len: int,
         k = k.float() * k_scale[:, :, :seq_len, None]
         v = v.float() * v_scale[:, :, :seq_len, None]
     return reference_cache_attention(q, k, v, seq_len - Tq)
+
+
+# --------------------------------------------------------------------------- n samples of one prompt
+def shared_prefix_applies(R: int, H: int, Hkv: int, D: int, capP: int) -> bool:
+    """The shared-prefix kernel's own launch plan admits the shape (``shared_prefix_plan``, host_plan.h)."""
+    return bool(kernels().shared_prefix_plan(R, H, Hkv, D, capP)[0])
+
+
+def shared_prefix_attention(q: Tensor, k_new: Tensor, v_new: Tensor, kp: Tensor, vp: Tensor, ks: Tensor,
+                            vs: Tensor, prefix_t: Tensor, len_t: Tensor, splits: int = 0) -> Tensor:
+    """One decode step of R samples of one prompt (ops/shared_prefix.py): ``q [R, H, D]``, this step's
+    ``k_new`` / ``v_new [R, Hkv, D]`` (views into the fused QKV rows allowed), the prefix caches
+    ``[1, Hkv, capP, D]`` of which the first ``prefix_t`` slots count, the rows' suffix caches
+    ``[R, Hkv, capS, D]`` and ``len_t``, the total length after this step (both int64 [1]). Writes the new K/V
+    into suffix slot ``len_t - 1 - prefix_t`` and returns ``[R, H·D]``: every row over the prefix keys and its
+    own ``len_t - prefix_t`` suffix keys. GPU: csrc/kernels/shared_prefix_attn.hip (bf16; a shape its plan
+    refuses is an error — ask ``shared_prefix_applies`` first); ``splits`` forces the prefix key ranges.
+    CPU: the reference definition with host-side lengths."""
+    R, H, D = q.shape
+    if use_kernels(q):
+        return kernels().shared_prefix_attn(q, k_new, v_new, kp, vp, ks, vs, prefix_t, len_t, 1.0 / math.sqrt(D),
+                                            int(splits))
+    from penroz.ops.shared_prefix import reference_attention
+    P, n = int(prefix_t.item()), int(len_t.item())
+    slot = n - 1 - P
+    ks[:, :, slot] = k_new
+    vs[:, :, slot] = v_new
+    return reference_attention(q, kp, vp, ks, vs, P, slot + 1).to(q.dtype).reshape(R, H * D)

@@ -5,7 +5,7 @@ The public generate methods take their options as keywords; everything behind th
 loops of models/model.py, the captured step of models/graph_decode.py, ``/generate``'s early 400 —
 takes the checked object. The checks themselves live with their features (ops/sampling.py,
 ops/weight_quant.py, ops/penalties.py, ops/logprobs.py, ops/stopping.py, ops/logit_bias.py,
-ops/speculative.py, ops/prompt_logprobs.py); this
+ops/speculative.py, ops/prompt_logprobs.py, ops/shared_prefix.py); this
 module is the one place that calls them, in one order.
 """
 from __future__ import annotations
@@ -20,6 +20,7 @@ from penroz.ops import logprobs as lp_ops
 from penroz.ops import penalties as pen_ops
 from penroz.ops import prompt_logprobs as plp_ops
 from penroz.ops import sampling as samp_ops
+from penroz.ops import shared_prefix as sp_ops
 from penroz.ops import speculative as spec_ops
 from penroz.ops import stopping as stop_ops
 from penroz.ops import weight_quant as wq_ops
@@ -46,6 +47,7 @@ class DecodeOptions:
     speculate: int | None = None  # ``check_speculate``'s k in 1..3 (ops/speculative.py); None: off
     prompt_logprobs: bool = False  # the call also scores its prompt (ops/prompt_logprobs.py)
     prompt_top_logprobs: int = 0  # ... and reports this many most likely tokens per prompt position (0: none)
+    n: int | None = None  # ``check_n``'s k in 2..64: that many samples of the one prompt (ops/shared_prefix.py); None: off
     asked: str = field(default="", compare=False, repr=False)  # the options as given, in the words of the log line
 
     def describe(self) -> str:
@@ -64,10 +66,11 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
                   banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                   min_tokens: int | None = None, speculate: int | None = None,
                   prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
-                  call_shape: dict | None = None) -> DecodeOptions:
+                  n: int | None = None, call_shape: dict | None = None) -> DecodeOptions:
     """Every check of a generate call, once each, in this order; ValueError for the first that fails.
     ``call_shape`` is no option of the call: what the caller knows of its shape (``rows``, ``prompt_len``,
-    ``block_size``, ``stream``), which ``speculate`` is checked against (ops/speculative.py).
+    ``block_size``, ``stream``), which ``speculate`` and ``n`` are checked against (ops/speculative.py,
+    ops/shared_prefix.py; ``single``: the caller returns one row, which ``n`` alone looks at).
     ``V``: the model's vocabulary size, which token ids are checked against. None: the model's layer list
     does not show one, and the options that rewrite logits by id are refused. ``NOT_LOADED`` (the service,
     before it loads the model): not known yet, ids are checked against 2^31 only."""
@@ -76,7 +79,7 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
     samp_ops._check_filters(top_p, min_p)
     quant = wq_ops.resolve(weight_quant)
     penalties = pen_ops.check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-    n = lp_ops.check_logprobs(logprobs)
+    lp_n = lp_ops.check_logprobs(logprobs)
     seqs = stop_ops.check_stop(stop, V)
     if seqs is not None and stop_token is not None:
         raise ValueError("give stop_token or stop, not both (a stop_token s is the stop sequence [s])")
@@ -87,12 +90,15 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
                          "layer list ends with the vocabulary projection")
     active = [name for name, v, off in (("repetition_penalty", repetition_penalty, 1.0), ("presence_penalty", presence_penalty, 0.0),
                                         ("frequency_penalty", frequency_penalty, 0.0)) if v is not None and float(v) != off]
-    active += [name for name, on in (("logprobs", n is not None), ("stop", seqs is not None), ("logit_bias", bool(logit_bias)),
+    active += [name for name, on in (("logprobs", lp_n is not None), ("stop", seqs is not None), ("logit_bias", bool(logit_bias)),
                                      ("banned_token_ids", bool(banned_token_ids)), ("allowed_token_ids", allowed_token_ids is not None),
                                      ("min_tokens", bool(min_tokens))) if on]
+    call_shape = dict(call_shape or {})
+    single = bool(call_shape.pop("single", False))
     k = spec_ops.check_speculate(speculate, temperature=temperature, active=active, max_new_tokens=max_new_tokens,
-                                 **(call_shape or {}))
-    scored = plp_ops.check_prompt_logprobs(prompt_logprobs, speculate=k, stream=bool((call_shape or {}).get("stream")))
+                                 **call_shape)
+    samples = sp_ops.check_n(n, max_new_tokens=max_new_tokens, speculate=k, single=single, **call_shape)
+    scored = plp_ops.check_prompt_logprobs(prompt_logprobs, speculate=k, stream=bool(call_shape.get("stream")))
     scored_n = plp_ops.check_prompt_top_logprobs(prompt_top_logprobs, prompt_logprobs=scored)
     asked = "" if top_k is None else f" top {top_k}"
     asked += "" if top_p is None else f" top_p {top_p}"
@@ -108,8 +114,9 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
     asked += "" if k is None else f" speculate {k}"
     asked += "" if not scored else " prompt_logprobs"
     asked += "" if not scored_n else f" top {scored_n}"
-    return DecodeOptions(temperature, top_k, top_p, min_p, quant, penalties, n, seqs, stop_token, bias,
-                         min_tokens or 0, k, scored, scored_n, asked)
+    asked += "" if samples is None else f" n {samples}"
+    return DecodeOptions(temperature, top_k, top_p, min_p, quant, penalties, lp_n, seqs, stop_token, bias,
+                         min_tokens or 0, k, scored, scored_n, samples, asked)
 
 
 # the option keywords of the public generate methods: ``check_options``' own, by name

@@ -1,0 +1,97 @@
+"""``n``: several independent samples of one prompt, and the attention that serves them.
+
+``n = k`` (2 <= k <= 64) on one prompt ``p`` means the call ``generate_batch([p] * k, ...)``: there are k rows,
+row r draws from the sampler's stream of row r, and all rows are at the same position in every step. The
+distribution and the return shape are the replicated call's; the bits of the logits may differ, because the
+attention sums in another order. ``n`` of None or 1 is neutral: the call, the step, the return values and the
+graphs are exactly what they are without it.
+
+The replicated call prefills the prompt k times, stores its K/V k times and reads it k times per decode step.
+On the GPU (``models/graph_decode.py``, ``GraphDecoder(shared_prefix=True)``) an ``n`` call prefills row 0 alone
+into a batch-1 *prefix* cache, gives every row a *suffix* cache for the tokens it generates, and attends with
+``csrc/kernels/shared_prefix_attn.hip``: every prefix key is read once per KV head and scored against all rows
+on the matrix cores. Row r's keys are the prefix keys followed by row r's own suffix keys
+(``reference_attention``). A row's bits depend on its own query, the prefix, its suffix, the prefix length and
+the number of prefix key ranges S, which sets the order of the sums. At equal S they do not depend on the
+row count or on the other rows; the launch plan chooses S from the row count (with the heads and the
+capacity), so calls with different ``n`` may run different S and round a row differently. Elsewhere — the CPU, ``PENROZ_GRAPH_DECODE=0``, a model without a decode program, fp32
+parameters, the int8 KV cache, a shape the kernel's plan refuses, ``PENROZ_SHARED_PREFIX=0`` — the replicated
+call runs, which is the same thing by definition; logged once per process.
+
+An ``n`` call takes one prompt row, does not stream, does not speculate, is ``generate_batch``'s (the other
+generate methods return one row), and never slides its window: ``len(prompt) + max_new_tokens <= block_size``,
+for the reason a ragged call does not (the re-prefill is a whole-batch operation on one cache).
+"""
+from __future__ import annotations
+
+import logging
+import math
+import os
+
+import torch
+from torch import Tensor
+
+log = logging.getLogger(__name__)
+
+MAX_N = 64  # the decode step's most rows
+
+
+def enabled() -> bool:
+    """``PENROZ_SHARED_PREFIX=0``: the A/B switch — every ``n`` call runs replicated."""
+    return os.environ.get("PENROZ_SHARED_PREFIX", "1") != "0"
+
+
+def check_n(n, *, rows: int | None = None, prompt_len: int | None = None, max_new_tokens: int | None = None,
+            block_size: int | None = None, stream: bool = False, speculate: int | None = None,
+            single: bool = False) -> int | None:
+    """k in 2..64, or None for neutral (None, 1). ``rows``, ``prompt_len``, ``block_size``, ``stream``: the call's
+    shape where it is known; ``single``: the caller returns one row (``generate_tokens*``). ValueError for
+    what an ``n`` call does not take."""
+    if n is None:
+        return None
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_N:
+        raise ValueError(f"n must be None or an integer in [1, {MAX_N}], got {n!r}")
+    if n == 1:
+        return None
+    if single:
+        raise ValueError("n samples are n rows: generate_tokens and generate_tokens_stream return one row; use "
+                         "generate_batch")
+    if stream:
+        raise ValueError("n samples are returned together: not together with stream")
+    if speculate:
+        raise ValueError("n does not compose with speculate (one greedy sequence)")
+    if rows is not None and rows != 1:
+        raise ValueError(f"n samples one prompt, got {rows} prompt rows")
+    if None not in (prompt_len, max_new_tokens, block_size) and prompt_len + max_new_tokens > block_size:
+        raise ValueError(f"an n call does not slide its window: prompt ({prompt_len}) + max_new_tokens "
+                         f"({max_new_tokens}) must be <= block_size ({block_size})")
+    return int(n)
+
+
+_fallback_logged = False
+
+
+def log_fallback(why: str) -> None:
+    """Once per process: an ``n`` call runs as the replicated call ``[prompt] * n``."""
+    global _fallback_logged
+    if _fallback_logged:
+        return
+    _fallback_logged = True
+    log.info(f"n samples of one prompt run as the replicated batch ({why}): the same call by definition")
+
+
+def reference_attention(q: Tensor, kp: Tensor, vp: Tensor, ks: Tensor, vs: Tensor, prefix_len: int,
+                        suffix_len: int, scale: float | None = None) -> Tensor:
+    """The definition, in fp64: q [R, H, D]; prefix caches [1, Hkv, capP, D], the first ``prefix_len`` slots
+    used; suffix caches [R, Hkv, capS, D], the first ``suffix_len`` used (this step's K/V at slot
+    ``suffix_len - 1`` already). Row r, head h: softmax over the prefix keys followed by row r's suffix keys of
+    KV head h // (H / Hkv). -> [R, H, D] fp64."""
+    R, H, D = q.shape
+    Hkv = kp.shape[1]
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    k = torch.cat([kp[:, :, :prefix_len].expand(R, -1, -1, -1), ks[:, :, :suffix_len]], dim=2).double()
+    v = torch.cat([vp[:, :, :prefix_len].expand(R, -1, -1, -1), vs[:, :, :suffix_len]], dim=2).double()
+    k = k.repeat_interleave(H // Hkv, dim=1)
+    v = v.repeat_interleave(H // Hkv, dim=1)
+    s = torch.einsum("rhd,rhkd->rhk", q.double(), k) * scale
+    return torch.einsum("rhk,rhkd->rhd", torch.softmax(s, dim=-1), v)

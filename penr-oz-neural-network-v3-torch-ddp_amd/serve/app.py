@@ -199,6 +199,11 @@ class GenerateRequest(ModelRequest):
                                                               "this many most likely tokens with their log-probabilities, "
                                                               "best first ([id, logprob] pairs; null at position 0); null "
                                                               "or 0: off")
+    n: StrictInt | None = Field(None, examples=[None],
+                                description="This many (2 to 64) independent samples of the one prompt given: answered "
+                                            "in the batch form, {\"sequences\": [...]} with per-row lists for the "
+                                            "rest; the prompt is prefilled and cached once; prompt + max_new_tokens "
+                                            "<= block_size; not with stream or speculate; null or 1: off")
     stream: bool = Field(False, examples=[False], description="Stream tokens as text/plain lines")
     batch: bool = Field(False, examples=[False],
                         description="Return every row: {\"sequences\": [[...], ...]}, each row's prompt plus its "
@@ -524,6 +529,8 @@ def model_generate(body: GenerateRequest = Body(...)):
         penalties["prompt_logprobs"] = True
     if early.prompt_top_logprobs:  # (likewise)
         penalties["prompt_top_logprobs"] = early.prompt_top_logprobs
+    if early.n:  # (likewise; n samples are n rows: the batch form answers)
+        penalties["n"] = early.n
 
     def with_prompt_scores(out: dict, scores) -> dict:
         if scores is not None:
@@ -538,7 +545,7 @@ def model_generate(body: GenerateRequest = Body(...)):
         scores = [i.pop("prompt_logprobs") for i in info] if rows else info.pop("prompt_logprobs")
         return (tokens if body.logprobs is None and stop is None else (tokens, info)), scores
 
-    if body.batch:
+    if body.batch or early.n:
         # every row of the batch, ragged or not (ops/ragged.py): generate_batch's result, row for row
         with _Held(model):
             res = model.generate_batch(body.input, body.block_size, body.max_new_tokens, body.temperature,
