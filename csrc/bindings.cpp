@@ -97,6 +97,11 @@ std::tuple<bool, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t> shared_pr
                                                                                          int64_t D, int64_t capP,
                                                                                          int64_t splits);
 std::vector<std::pair<int64_t, int64_t>> shared_prefix_ranges(int64_t P, int64_t S);
+torch::Tensor shared_prefix_prefill_attn(torch::Tensor q, torch::Tensor k_new, torch::Tensor v_new, torch::Tensor kp,
+                                         torch::Tensor vp, torch::Tensor ks, torch::Tensor vs, torch::Tensor prefix_t,
+                                         double scale, int64_t splits);
+std::tuple<bool, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t> shared_prefix_prefill_plan(
+    int64_t R, int64_t Tq, int64_t H, int64_t Hkv, int64_t D, int64_t capP, int64_t capS, int64_t splits);
 // lmhead_lse.hip
 std::vector<torch::Tensor> lmhead_lse_raw(torch::Tensor h, torch::Tensor w, c10::optional<torch::Tensor> bias,
                                           torch::Tensor targets, int64_t splits, int64_t top_n);
@@ -363,6 +368,15 @@ PYBIND11_MODULE(penroz_kernels, m) {
         "launch 1, LDS bytes, fp32 workspace floats) (host only)");
   m.def("shared_prefix_ranges", &shared_prefix_ranges, pybind11::arg("P"), pybind11::arg("S"),
         "the S prefix workgroups' key ranges [first, second) at prefix length P, as the kernel derives them (host only)");
+  m.def("shared_prefix_prefill_attn", &shared_prefix_prefill_attn, pybind11::arg("q"), pybind11::arg("k_new"),
+        pybind11::arg("v_new"), pybind11::arg("kp"), pybind11::arg("vp"), pybind11::arg("ks"), pybind11::arg("vs"),
+        pybind11::arg("prefix_t"), pybind11::arg("scale"), pybind11::arg("splits") = 0,
+        "the remainders of R rows that share a prefix: q [R, Tq, H, D], query t of row r over the prefix cache (first "
+        "*prefix_t slots) and row r's new keys 0..t, which are written into suffix slots 0..Tq-1 -> [R, Tq, H·D]");
+  m.def("shared_prefix_prefill_plan", &shared_prefix_prefill_plan, pybind11::arg("R"), pybind11::arg("Tq"), pybind11::arg("H"),
+        pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("capP"), pybind11::arg("capS"), pybind11::arg("splits") = 0,
+        "shared_prefix_prefill_attn's plan: (admitted, tile rows, prefix query tiles per KV head, suffix query tiles per "
+        "(row, KV head), key ranges S, workgroups of launch 1, LDS bytes, fp32 workspace floats) (host only)");
   m.def("lmhead_lse",
         [](torch::Tensor h, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor targets, int64_t splits,
            int64_t top_n) -> pybind11::tuple {

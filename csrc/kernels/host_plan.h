@@ -460,6 +460,44 @@ inline std::pair<int64_t, int64_t> shared_prefix_range(int64_t P, int S, int s) 
   return {s * per, std::min<int64_t>(P, (s + 1) * per)};
 }
 
+// ---- shared-prefix prefill attention launch plan (shared_prefix_attn.hip, the prefill form) ----
+// R rows of Tq query positions each against one prefix cache of capP slots and their own suffix caches of capS.
+// Built: what the decode form takes, Tq from 1 to capS; everything else is refused.
+struct SharedPrefixPrefillPlan {
+  bool ok;            // admitted; everything below is 0 when not
+  int tile_rows;      // packed query rows per workgroup, of both kinds: 32, 64 or 128
+  int tiles;          // prefix query tiles per KV head: ceil(R·Tq·G / tile_rows)
+  int suffix_tiles;   // suffix query tiles per (row, KV head): ceil(Tq·G / tile_rows)
+  int splits;         // S: key ranges of the prefix
+  int copy_wgs;       // workgroups that copy the call's K / V into the suffix slots: 1024 16-B pieces of each per workgroup
+  int64_t grid;       // Hkv · tiles · S prefix, then R · Hkv · suffix_tiles suffix, then copy_wgs copy workgroups
+  int lds_bytes;
+  int64_t ws_floats;  // fp32 workspace: S + 1 partials (o[D], m, l) per (row, position, head)
+};
+
+// The tile is the narrowest of 32 / 64 / 128 rows that holds the R·Tq·G packed rows of a KV head (128 when they
+// are more), so a staged prefix tile serves as many query rows as there are; the suffix workgroups use the same
+// tile over one row's Tq·G. S aims at two workgroups per CU as the decode form does; with R·Tq·G in the
+// thousands the query tiles alone fill the chip and S is 1.
+inline SharedPrefixPrefillPlan plan_shared_prefix_prefill(int64_t R, int64_t Tq, int64_t H, int64_t Hkv, int64_t D,
+                                                          int64_t capP, int64_t capS, int splits_forced = 0) {
+  const SharedPrefixPlan base = plan_shared_prefix(R, H, Hkv, D, capP, splits_forced);
+  if (!base.ok || Tq < 1 || Tq > capS || capS > (int64_t(1) << 22)) return {false, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int64_t G = H / Hkv, rows = R * Tq * G;
+  const int tile_rows = rows <= 32 ? 32 : rows <= 64 ? 64 : 128;
+  const int64_t tiles = (rows + tile_rows - 1) / tile_rows, suffix_tiles = (Tq * G + tile_rows - 1) / tile_rows;
+  const int64_t suffix = R * Hkv * suffix_tiles, key_tiles = (capP + 63) / 64;
+  int64_t s = (kSharedPrefixFillWgs - std::min<int64_t>(suffix, kSharedPrefixFillWgs / 2) + Hkv * tiles - 1) / (Hkv * tiles);
+  s = std::max<int64_t>(1, std::min<int64_t>({s, key_tiles, kSharedPrefixMaxSplits}));
+  if (splits_forced > 0) s = std::min<int64_t>(splits_forced, kSharedPrefixMaxSplits);
+  const int64_t copy_wgs = (R * Tq * Hkv * (D / 8) + 1023) / 1024;
+  const int64_t grid = Hkv * tiles * s + suffix + copy_wgs;
+  if (grid >= (int64_t(1) << 31) || R * Tq * H >= (int64_t(1) << 27)) return {false, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int keys = prefill_keys((int)D);
+  const int lds = 4 * keys * (int)D * 2 + (D >= 256 ? tile_rows * (int)D * 2 : 0) + 16;
+  return {true, tile_rows, (int)tiles, (int)suffix_tiles, (int)s, (int)copy_wgs, grid, lds, (s + 1) * R * Tq * H * (D + 2)};
+}
+
 // ---- lm_head scoring launch plan (lmhead_lse.hip) ----
 constexpr int kLmheadColTile = 128, kLmheadKStep = 32;  // vocabulary columns per tile, reduction depth per stage
 constexpr int kLmheadMaxC = 16384, kLmheadMaxSplits = 1024;

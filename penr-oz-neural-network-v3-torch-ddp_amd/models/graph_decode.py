@@ -256,12 +256,41 @@ class SharedPrefixKVCache(_GraphMode, kvc.KVCache):
     def clear(self):
         super().clear()
         self.prefix_len = None
+        self._remainder = False
+
+    def _suffix(self, l: int):
+        if self._ks[l] is None:  # (an ``n`` call: the warm-up step, outside any capture)
+            kp = self._k[l]
+            shape = (self.rows, kp.shape[1], self.suffix_capacity, kp.shape[3])
+            self._ks[l], self._vs[l] = kp.new_zeros(shape), kp.new_zeros(shape)
+        return self._ks[l], self._vs[l]
+
+    def begin_remainder(self):
+        """A ``share_prefix`` call, behind its prefix pass: what the cache holds is the prefix. The suffix caches
+        exist from here on, and until ``end_remainder`` the eager ``attend`` is the rows' remainder pass — the
+        prefill form of the kernel, which leaves the remainders' K/V in suffix slots 0.."""
+        self.prefix_len = self.seq_len()
+        self.prefix_t.fill_(self.prefix_len)
+        for l in range(self.num_layers):
+            self._suffix(l)
+        self._remainder = True
+
+    def end_remainder(self, total: int):
+        """``total``: the longest row's length, which the host-side cache length counts from (a ragged call's rule)."""
+        self._remainder = False
+        self._len = [total] * self.num_layers
+
+    _remainder = False
+
+    def attend(self, l: int, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
+        if self._remainder and not self.graph_mode:
+            ks, vs = self._suffix(l)
+            return attn_ops.shared_prefix_prefill_attention(q, k, v, self._k[l], self._v[l], ks, vs, self.prefix_t)
+        return super().attend(l, q, k, v)
 
     def _attend_graph(self, l: int, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
         kp, vp = self._k[l], self._v[l]
-        if self._ks[l] is None:  # (the warm-up step, outside any capture)
-            shape = (self.rows, kp.shape[1], self.suffix_capacity, kp.shape[3])
-            self._ks[l], self._vs[l] = kp.new_zeros(shape), kp.new_zeros(shape)
+        self._suffix(l)
         return attn_ops.shared_prefix_attention(q.squeeze(1), k.squeeze(1), v.squeeze(1), kp, vp, self._ks[l],
                                                 self._vs[l], self.prefix_t, self.len_t)
 
@@ -296,6 +325,18 @@ def shared_prefix_fallback(model, rows: int, capacity: int) -> str | None:
     if not all(attn_ops.shared_prefix_applies(rows, H, Hkv, D, capacity) for H, Hkv, D in shapes):
         return f"the kernel's plan refuses {rows} rows at heads {sorted(set(shapes))}"
     return None
+
+
+def share_prefix_fallback(model, rows: int, capacity: int, remainder: int, suffix_capacity: int) -> str | None:
+    """Why a ``share_prefix`` call of ``rows`` prompts whose longest remainder is ``remainder`` tokens runs as the
+    plain call, or None: what an ``n`` call needs, and the prefill form's plan for the remainder pass."""
+    why = shared_prefix_fallback(model, rows, capacity)
+    if why is None:
+        shapes = _attention_shapes(model)
+        if not all(attn_ops.shared_prefix_prefill_applies(rows, remainder, H, Hkv, D, capacity, suffix_capacity)
+                   for H, Hkv, D in shapes):
+            why = f"the kernel's plan refuses {rows} rows of {remainder} positions at heads {sorted(set(shapes))}"
+    return why
 
 
 def _qkv_views(qkv: Tensor, H: int, Hkv: int, D: int):
@@ -830,7 +871,8 @@ class GraphDecoder:
         cls = StaticTurboKVCache if kvc.TURBO_QUANT_ENABLED else StaticKVCache
         # n samples of one prompt (ops/shared_prefix.py): ``rows`` rows over one prefix cache and their own suffixes
         self.shared_prefix = bool(shared_prefix)
-        assert not self.shared_prefix or not (ragged or speculate or kvc.TURBO_QUANT_ENABLED), (ragged, speculate)
+        # (with ``ragged``: rows that share a prefix and differ behind it, each at its own length — ``share_prefix``)
+        assert not self.shared_prefix or not (speculate or kvc.TURBO_QUANT_ENABLED), speculate
         if self.shared_prefix:
             cls = SharedPrefixKVCache
         self.cache = cls(len(self.attn), capacity)

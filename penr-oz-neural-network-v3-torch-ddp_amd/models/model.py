@@ -119,7 +119,8 @@ class NeuralNetworkModel(nn.Module):
     SHM_PATH = ckpt.detect_shm_path()
     # the last speculative generate call's {"steps", "drafted", "accepted"} (ops/speculative.py); None: none yet
     last_speculation: dict | None = None
-    # an ``n`` call that ran on the shared-prefix step (ops/shared_prefix.py): {"rows", "prefix_len", "splits"}; else None
+    # an ``n`` call that ran on the shared-prefix step (ops/shared_prefix.py): {"rows", "prefix_len", "splits"}; a
+    # ``share_prefix`` call that did: those and "remainders", the rows' own lengths behind the prefix; else None
     last_shared_prefix: dict | None = None
 
     def __init__(self, model_id: str, mapper: Mapper):
@@ -560,7 +561,7 @@ class NeuralNetworkModel(nn.Module):
                         banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                         min_tokens: int | None = None, speculate: int | None = None,
                         prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
-                        n: int | None = None):
+                        n: int | None = None, share_prefix: bool | None = None):
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
         "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
@@ -589,7 +590,8 @@ class NeuralNetworkModel(nn.Module):
         ``stop`` put there. The prompt needs 2 to ``block_size`` tokens; not together with ``speculate``.
         ``prompt_top_logprobs`` n in 1..20, with ``prompt_logprobs`` only: that dict also holds ``top_n``, the n
         most likely tokens of every prompt position (``score_tokens``' ``top_n``). None or 0: off.
-        ``n``: ``generate_batch``'s; here only None or 1 (this method returns one row)."""
+        ``n``: ``generate_batch``'s; here only None or 1 (this method returns one row). ``share_prefix``: likewise,
+        here only None or False."""
         options = _keywords(locals())
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
                                             stop_token, **options,
@@ -614,7 +616,7 @@ class NeuralNetworkModel(nn.Module):
                                banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                                min_tokens: int | None = None, speculate: int | None = None,
                                prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
-                               n: int | None = None):
+                               n: int | None = None, share_prefix: bool | None = None):
         """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``. With
         ``stop`` the stream ends with the token that completes a stop sequence. ``logit_bias`` /
         ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in ``generate_tokens``.
@@ -630,7 +632,7 @@ class NeuralNetworkModel(nn.Module):
 
     def _token_bursts(self, context: Tensor, block_size: int, max_new_tokens: int, softmax_layer,
                       opts: DecodeOptions, burst: int, stop_run: stop_ops.StopRun | None = None,
-                      lens: list[int] | None = None, shared: bool = False):
+                      lens: list[int] | None = None, shared: bool = False, prefix: int | None = None):
         """Yield [rows, k] blocks of new tokens (device). On the GPU the decode steps replay a
         captured HIP graph (``graph_decode.py``); prefill and the sliding-window re-prefill
         (cache full) run eagerly, exactly as the per-token path. The call keeps one ``DecodeCall``
@@ -657,12 +659,19 @@ class NeuralNetworkModel(nn.Module):
         ``shared`` (an ``n`` call on the shared-prefix step, ops/shared_prefix.py; the caller made sure there is
         one): ``context`` is the one prompt expanded to ``opts.n`` rows; the prompt pass runs row 0 alone into the
         decoder's prefix cache, its last logits serve every row's first token — each row its own draw — and
-        the graph steps run the rows over that prefix and their own suffixes. The window never slides (``check_n``)."""
+        the graph steps run the rows over that prefix and their own suffixes. The window never slides (``check_n``).
+        ``prefix`` (a ``share_prefix`` call on the shared-prefix step, with ``lens``; the caller made sure there is
+        one): the rows' first ``prefix`` tokens are equal. The prompt pass runs them once, row 0's, into the decoder's
+        prefix cache, then the rows' padded remainders at position ``prefix`` through the prefill form of the
+        shared-prefix kernel; row b's first token comes from the logits at ``lens[b] - prefix - 1``, and the graph
+        steps run every row at its own length over the prefix and its own suffix."""
         from penroz.models import graph_decode
         rows = context.shape[0]
         suffix = {"suffix_capacity": -(-max(max_new_tokens, 1) // 64) * 64} if shared else {}
+        if prefix is not None:
+            suffix = {"suffix_capacity": sp_ops.suffix_capacity(max(lens) - prefix, max_new_tokens)}
         dec = graph_decode.decoder_for(self, rows, block_size, opts, ragged=lens is not None, **suffix)
-        assert dec is not None or not shared, "an n call needs the shared-prefix decoder (generate_batch falls back before this)"
+        assert dec is not None or not (shared or prefix), "an n call needs the shared-prefix decoder (generate_batch falls back before this)"
         last_index = None
         if lens is not None:
             assert dec is not None, "a ragged call needs the ragged decoder (generate_batch falls back before this)"
@@ -689,7 +698,21 @@ class NeuralNetworkModel(nn.Module):
             last = None
             while remaining > 0:
                 n = cache.seq_len() if cache is not None else 0
-                if shared and n == 0:
+                if prefix is not None and n == 0:
+                    self(context[:1, :prefix], skip_softmax=True)  # the common prefix, once; its logits are unused
+                    cache.begin_remainder()
+                    for p in pos:
+                        p.position_offset = prefix
+                    try:
+                        logits = self(context[:, prefix:], skip_softmax=True)[0][-1]  # the rows' padded remainders
+                    finally:
+                        for p in pos:
+                            p.position_offset = 0
+                        cache.end_remainder(context.shape[1])
+                    new = call.apply(logits[torch.arange(rows, device=logits.device), last_index - prefix], None)
+                    if opts.logprobs is not None:
+                        new, lps = new[0], tuple(t.unsqueeze(1) for t in new[1])
+                elif shared and n == 0:
                     logits = self(context[:1], skip_softmax=True)[0][-1]  # the prompt, once (it fits the window)
                     logits = logits[:, -1, :] if logits.ndim == 3 else logits
                     new = call.apply(logits.expand(rows, -1).contiguous(), None)
@@ -706,9 +729,11 @@ class NeuralNetworkModel(nn.Module):
                 else:
                     k = min(remaining, block_size - n, burst)
                     new = dec.run(last, k, start=call.produced)
-                    if shared:
+                    if shared or prefix is not None:
                         self.last_shared_prefix = {"rows": rows, "prefix_len": dec.cache.prefix_len,
                                                    "splits": graph_decode.shared_prefix_splits(self, rows, block_size)}
+                    if prefix is not None:
+                        self.last_shared_prefix["remainders"] = [n_b - prefix for n_b in lens]
                     lps = dec.last_logprobs
                     call.produced += k
                 context = torch.cat((context, new.to(context.device)), dim=1)
@@ -877,7 +902,7 @@ class NeuralNetworkModel(nn.Module):
                        banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                        min_tokens: int | None = None, speculate: int | None = None,
                        prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
-                       n: int | None = None):
+                       n: int | None = None, share_prefix: bool | None = None):
         """All rows' contexts (the reference returns row 0 only — bug 5). With ``logprobs`` n:
         ``(contexts, [info per row])``, each ``info`` (``generate_tokens``) as long as that row's
         returned continuation. With ``stop`` (ops/stopping.py) every row finishes on its own: the
@@ -901,10 +926,18 @@ class NeuralNetworkModel(nn.Module):
         ``generate_batch([prompt] * k, ...)`` with the same return shape, row r drawing from row r's stream; not
         with ``speculate``, and ``len(prompt) + max_new_tokens <= block_size``. On the GPU the prompt is prefilled
         and cached once and the decode steps read it once for all rows (``last_shared_prefix`` then holds
-        {"rows", "prefix_len", "splits"}); elsewhere the replicated call runs. None or 1: off."""
+        {"rows", "prefix_len", "splits"}); elsewhere the replicated call runs. None or 1: off.
+        ``share_prefix`` True (ops/shared_prefix.py): the 2..64 prompts given begin with the same tokens. The call
+        returns what it returns without the option; on the GPU the common prefix is prefilled and cached once, the
+        rows' remainders are prefilled against it and the decode steps read it once for all rows
+        (``last_shared_prefix`` then also holds "remainders"); elsewhere, and without a common prefix, the plain call
+        runs. Not with ``n`` or ``speculate``; ``max(len_b) + max_new_tokens <= block_size``. None or False: off."""
         options = _keywords(locals())
         self.last_shared_prefix = None
         samples = None
+        if share_prefix is not None and share_prefix is not False:  # checked against the call's shape before anything runs
+            check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
+                          call_shape=call_shape_of(input_context, block_size))
         if n is not None:  # checked against the call's shape, with every other option, before anything runs
             samples = check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
                                     call_shape=call_shape_of(input_context, block_size)).n
@@ -931,11 +964,24 @@ class NeuralNetworkModel(nn.Module):
                                            stop_token, **{**options, "n": None})
             input_context = [prompt]
         lens = ragged_ops.ragged_lengths(input_context)
-        prompts = None
+        prompts = prefix = None
+        if share_prefix:
+            from penroz.models import graph_decode
+            prompts = ragged_ops.check_prompts(input_context, block_size, max_new_tokens, self._vocab_size())
+            prefix = sp_ops.split_prompts(prompts)
+            lens = [len(p) for p in prompts]
+            capacity = sp_ops.suffix_capacity(max(lens) - prefix, max_new_tokens)
+            why = "the prompts have no common prefix" if prefix == 0 else graph_decode.share_prefix_fallback(
+                self, len(prompts), block_size, max(lens) - prefix, capacity)
+            if why is not None:
+                sp_ops.log_batch_fallback(why)
+                return self.generate_batch(input_context, block_size, max_new_tokens, temperature, top_k, stop_token,
+                                           **{**options, "share_prefix": None})
+            input_context = ragged_ops.pad_prompts(prompts)
         if speculate:  # checked against the call's shape before anything runs
             check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
                           call_shape=call_shape_of(input_context, block_size))
-        if lens is not None:
+        if lens is not None and prefix is None:
             prompts = ragged_ops.check_prompts(input_context, block_size, max_new_tokens, self._vocab_size())
             why = self._ragged_fallback()
             if why is not None:
@@ -955,7 +1001,7 @@ class NeuralNetworkModel(nn.Module):
         s_done, s_fin = [0] * rows, [0] * rows
         infos = [{"token_logprobs": [], "top_logprobs": []} if logprobs is not None else {} for _ in range(rows)]
         burst = 32 if stop_token is not None else max_new_tokens
-        for new in self._token_bursts(context, block_size, max_new_tokens, sm, opts, burst, run, lens, bool(opts.n)):
+        for new in self._token_bursts(context, block_size, max_new_tokens, sm, opts, burst, run, lens, bool(opts.n), prefix):
             if logprobs is not None:
                 new, lps = new
             keep, stopped = new.shape[1], False

@@ -322,7 +322,8 @@ def shared_prefix_attention(q: Tensor, k_new: Tensor, v_new: Tensor, kp: Tensor,
     """One decode step of R samples of one prompt (ops/shared_prefix.py): ``q [R, H, D]``, this step's
     ``k_new`` / ``v_new [R, Hkv, D]`` (views into the fused QKV rows allowed), the prefix caches
     ``[1, Hkv, capP, D]`` of which the first ``prefix_t`` slots count, the rows' suffix caches
-    ``[R, Hkv, capS, D]`` and ``len_t``, the total length after this step (both int64 [1]). Writes the new K/V
+    ``[R, Hkv, capS, D]`` and ``len_t``, the total length after this step (both int64 [1]; ``len_t`` may be [R]:
+    every row its own length, the GPU kernel only). Writes the new K/V
     into suffix slot ``len_t - 1 - prefix_t`` and returns ``[R, H·D]``: every row over the prefix keys and its
     own ``len_t - prefix_t`` suffix keys. GPU: csrc/kernels/shared_prefix_attn.hip (bf16; a shape its plan
     refuses is an error — ask ``shared_prefix_applies`` first); ``splits`` forces the prefix key ranges.
@@ -337,3 +338,27 @@ def shared_prefix_attention(q: Tensor, k_new: Tensor, v_new: Tensor, kp: Tensor,
     ks[:, :, slot] = k_new
     vs[:, :, slot] = v_new
     return reference_attention(q, kp, vp, ks, vs, P, slot + 1).to(q.dtype).reshape(R, H * D)
+
+
+def shared_prefix_prefill_applies(R: int, Tq: int, H: int, Hkv: int, D: int, capP: int, capS: int) -> bool:
+    """The prefill form's own launch plan admits the shape (``shared_prefix_prefill_plan``, host_plan.h)."""
+    return bool(kernels().shared_prefix_prefill_plan(R, Tq, H, Hkv, D, capP, capS)[0])
+
+
+def shared_prefix_prefill_attention(q: Tensor, k_new: Tensor, v_new: Tensor, kp: Tensor, vp: Tensor, ks: Tensor,
+                                    vs: Tensor, prefix_t: Tensor, splits: int = 0) -> Tensor:
+    """The remainders of R rows that share a prefix (ops/shared_prefix.py, ``share_prefix``): ``q [R, Tq, H, D]``
+    and the rows' new ``k_new`` / ``v_new [R, Tq, Hkv, D]`` (views into the fused QKV rows allowed), the prefix
+    caches ``[1, Hkv, capP, D]`` of which the first ``prefix_t`` (int64 [1]) slots count, and the rows' suffix
+    caches ``[R, Hkv, capS, D]``. Writes the new K/V into suffix slots ``0..Tq-1`` and returns ``[R, Tq, H·D]``:
+    query t of row r over the prefix keys and row r's slots ``0..t``. GPU: the prefill form of
+    csrc/kernels/shared_prefix_attn.hip (bf16; a shape its plan refuses is an error — ask
+    ``shared_prefix_prefill_applies`` first); ``splits`` forces the prefix key ranges. CPU: the definition."""
+    R, Tq, H, D = q.shape
+    if use_kernels(q):
+        return kernels().shared_prefix_prefill_attn(q, k_new, v_new, kp, vp, ks, vs, prefix_t, 1.0 / math.sqrt(D),
+                                                    int(splits))
+    from penroz.ops.shared_prefix import reference_prefill_attention
+    ks[:, :, :Tq] = k_new.transpose(1, 2)
+    vs[:, :, :Tq] = v_new.transpose(1, 2)
+    return reference_prefill_attention(q, kp, vp, ks, vs, int(prefix_t.item())).to(q.dtype).reshape(R, Tq, H * D)

@@ -48,6 +48,7 @@ class DecodeOptions:
     prompt_logprobs: bool = False  # the call also scores its prompt (ops/prompt_logprobs.py)
     prompt_top_logprobs: int = 0  # ... and reports this many most likely tokens per prompt position (0: none)
     n: int | None = None  # ``check_n``'s k in 2..64: that many samples of the one prompt (ops/shared_prefix.py); None: off
+    share_prefix: bool = False  # ``check_share_prefix``': the rows' common prefix is prefilled and cached once (ops/shared_prefix.py)
     asked: str = field(default="", compare=False, repr=False)  # the options as given, in the words of the log line
 
     def describe(self) -> str:
@@ -66,7 +67,7 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
                   banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                   min_tokens: int | None = None, speculate: int | None = None,
                   prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
-                  n: int | None = None, call_shape: dict | None = None) -> DecodeOptions:
+                  n: int | None = None, share_prefix: bool | None = None, call_shape: dict | None = None) -> DecodeOptions:
     """Every check of a generate call, once each, in this order; ValueError for the first that fails.
     ``call_shape`` is no option of the call: what the caller knows of its shape (``rows``, ``prompt_len``,
     ``block_size``, ``stream``), which ``speculate`` and ``n`` are checked against (ops/speculative.py,
@@ -97,6 +98,8 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
     single = bool(call_shape.pop("single", False))
     k = spec_ops.check_speculate(speculate, temperature=temperature, active=active, max_new_tokens=max_new_tokens,
                                  **call_shape)
+    shared = sp_ops.check_share_prefix(share_prefix, n=n, max_new_tokens=max_new_tokens, speculate=k, single=single,
+                                       **call_shape)
     samples = sp_ops.check_n(n, max_new_tokens=max_new_tokens, speculate=k, single=single, **call_shape)
     scored = plp_ops.check_prompt_logprobs(prompt_logprobs, speculate=k, stream=bool(call_shape.get("stream")))
     scored_n = plp_ops.check_prompt_top_logprobs(prompt_top_logprobs, prompt_logprobs=scored)
@@ -115,8 +118,9 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
     asked += "" if not scored else " prompt_logprobs"
     asked += "" if not scored_n else f" top {scored_n}"
     asked += "" if samples is None else f" n {samples}"
+    asked += "" if not shared else " share_prefix"
     return DecodeOptions(temperature, top_k, top_p, min_p, quant, penalties, lp_n, seqs, stop_token, bias,
-                         min_tokens or 0, k, scored, scored_n, samples, asked)
+                         min_tokens or 0, k, scored, scored_n, samples, shared, asked)
 
 
 # the option keywords of the public generate methods: ``check_options``' own, by name

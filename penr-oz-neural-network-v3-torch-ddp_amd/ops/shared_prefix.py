@@ -21,6 +21,19 @@ call runs, which is the same thing by definition; logged once per process.
 An ``n`` call takes one prompt row, does not stream, does not speculate, is ``generate_batch``'s (the other
 generate methods return one row), and never slides its window: ``len(prompt) + max_new_tokens <= block_size``,
 for the reason a ragged call does not (the re-prefill is a whole-batch operation on one cache).
+
+``share_prefix=True`` (``generate_batch`` of 2..64 prompt rows) is the general case: the rows are DIFFERENT prompts
+that begin with the same tokens. The call returns what the same call without the option returns — row b is the
+one-row generation from prompt b (ops/ragged.py); same distribution, same return shape, the bits of the logits may
+differ. ``split_prompts`` cuts the rows at ``P = min(longest common prefix, min(len_b) - 1)``, so every row keeps a
+remainder of at least one token and draws its first token from its own logits. On the GPU the prefix is prefilled
+once into the batch-1 prefix cache, the remainders — right-padded with each row's own last token — run as one
+pass whose attention is the prefill form of the kernel (``reference_prefill_attention``), and the decode steps run
+the rows at their own lengths over that prefix and their own suffixes. ``n`` is the special case of equal rows
+(whose remainder is empty, so its first token comes from the prefix pass). Where ``n`` falls back, and when
+``P == 0``, the plain call runs. There is no threshold on ``P``: the option is the caller's statement that the
+prefix is worth sharing (profiles/shared_prefix_batch.md shows where it is not). Not with ``n``, ``speculate`` or
+``stream``; ``max(len_b) + max_new_tokens <= block_size``.
 """
 from __future__ import annotations
 
@@ -68,6 +81,48 @@ def check_n(n, *, rows: int | None = None, prompt_len: int | None = None, max_ne
     return int(n)
 
 
+def check_share_prefix(share_prefix, *, n=None, rows: int | None = None, prompt_len: int | None = None,
+                       max_new_tokens: int | None = None, block_size: int | None = None, stream: bool = False,
+                       speculate: int | None = None, single: bool = False) -> bool:
+    """True, or False for neutral (None, False). ``rows`` / ``prompt_len`` (the longest row's) / ``block_size`` /
+    ``stream``: the call's shape where it is known; ``single``: the caller returns one row. ValueError for what
+    a ``share_prefix`` call does not take."""
+    if share_prefix is None or share_prefix is False:
+        return False
+    if share_prefix is not True:
+        raise ValueError(f"share_prefix must be None or a boolean, got {share_prefix!r}")
+    if single:
+        raise ValueError("share_prefix is a batch's option: generate_tokens and generate_tokens_stream return one "
+                         "row; use generate_batch")
+    if stream:
+        raise ValueError("share_prefix returns its rows together: not together with stream")
+    if n is not None and n != 1:
+        raise ValueError("share_prefix takes different prompts, n one prompt: not both")
+    if speculate:
+        raise ValueError("share_prefix does not compose with speculate (one greedy sequence)")
+    if rows is not None and not 2 <= rows <= MAX_N:
+        raise ValueError(f"share_prefix takes 2 to {MAX_N} prompt rows, got {rows}")
+    if None not in (prompt_len, max_new_tokens, block_size) and prompt_len + max_new_tokens > block_size:
+        raise ValueError(f"a share_prefix call does not slide its window: the longest prompt ({prompt_len}) + "
+                         f"max_new_tokens ({max_new_tokens}) must be <= block_size ({block_size})")
+    return True
+
+
+def split_prompts(prompts: list[list[int]]) -> int:
+    """P, where a ``share_prefix`` call cuts its rows: the longest common prefix, but at most ``min(len_b) - 1`` —
+    every row keeps a remainder of at least one token. 0: nothing to share."""
+    shortest = min(len(p) for p in prompts)
+    common = 0
+    while common < shortest and all(p[common] == prompts[0][common] for p in prompts):
+        common += 1
+    return max(0, min(common, shortest - 1))
+
+
+def suffix_capacity(remainder: int, max_new_tokens: int) -> int:
+    """Slots of a ``share_prefix`` call's suffix caches: the longest remainder and the new tokens, in 64-key tiles."""
+    return -(-(remainder + max(max_new_tokens, 1)) // 64) * 64
+
+
 _fallback_logged = False
 
 
@@ -78,6 +133,38 @@ def log_fallback(why: str) -> None:
         return
     _fallback_logged = True
     log.info(f"n samples of one prompt run as the replicated batch ({why}): the same call by definition")
+
+
+def log_batch_fallback(why: str) -> None:
+    """Once per process: a ``share_prefix`` call runs as the plain call."""
+    global _batch_fallback_logged
+    if _batch_fallback_logged:
+        return
+    _batch_fallback_logged = True
+    log.info(f"share_prefix runs as the plain batch ({why}): the same call by definition")
+
+
+_batch_fallback_logged = False
+
+
+def reference_prefill_attention(q: Tensor, kp: Tensor, vp: Tensor, ks: Tensor, vs: Tensor, prefix_len: int,
+                                scale: float | None = None) -> Tensor:
+    """The prefill form's definition, in fp64: q [R, Tq, H, D]; prefix caches [1, Hkv, capP, D], the first
+    ``prefix_len`` slots used; suffix caches [R, Hkv, capS, D] with the call's K/V in slots 0..Tq-1 already.
+    Query t of row r, head h: softmax over the prefix keys followed by row r's suffix slots 0..t.
+    -> [R, Tq, H, D] fp64."""
+    R, Tq, H, D = q.shape
+    Hkv = kp.shape[1]
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    k = torch.cat([kp[:, :, :prefix_len].expand(R, -1, -1, -1), ks[:, :, :Tq]], dim=2).double()
+    v = torch.cat([vp[:, :, :prefix_len].expand(R, -1, -1, -1), vs[:, :, :Tq]], dim=2).double()
+    k = k.repeat_interleave(H // Hkv, dim=1)
+    v = v.repeat_interleave(H // Hkv, dim=1)
+    s = torch.einsum("rthd,rhkd->rhtk", q.double(), k) * scale
+    key = torch.arange(prefix_len + Tq, device=q.device)
+    hidden = key[None, :] > prefix_len + torch.arange(Tq, device=q.device)[:, None]
+    s = s.masked_fill(hidden, float("-inf"))
+    return torch.einsum("rhtk,rhkd->rthd", torch.softmax(s, dim=-1), v)
 
 
 def reference_attention(q: Tensor, kp: Tensor, vp: Tensor, ks: Tensor, vs: Tensor, prefix_len: int,

@@ -204,6 +204,10 @@ class GenerateRequest(ModelRequest):
                                             "in the batch form, {\"sequences\": [...]} with per-row lists for the "
                                             "rest; the prompt is prefilled and cached once; prompt + max_new_tokens "
                                             "<= block_size; not with stream or speculate; null or 1: off")
+    share_prefix: bool | None = Field(None, examples=[None],
+                                      description="With batch: the 2 to 64 prompts begin with the same tokens; the "
+                                                  "common prefix is prefilled and cached once, the answer is the one "
+                                                  "without the option; not with n, stream or speculate; null or false: off")
     stream: bool = Field(False, examples=[False], description="Stream tokens as text/plain lines")
     batch: bool = Field(False, examples=[False],
                         description="Return every row: {\"sequences\": [[...], ...]}, each row's prompt plus its "
@@ -506,6 +510,8 @@ def evaluate_model(body: EvaluateRequest = Body(...)):
 def model_generate(body: GenerateRequest = Body(...)):
     if body.batch and body.stream:  # a 400 before the model is touched
         raise ValueError("batch returns every row at once: not together with stream")
+    if body.share_prefix and not body.batch:  # (likewise)
+        raise ValueError("share_prefix is a batch's option: set batch")
     # (likewise, streams too: an unknown weight format, a malformed stop set, logit bias, banned or allowed set or
     # min_tokens, stop_token together with stop; ids beyond the vocabulary: once the model is loaded and it is known)
     # (and everything a speculative call does not take: its shape is the request's own)
@@ -531,6 +537,8 @@ def model_generate(body: GenerateRequest = Body(...)):
         penalties["prompt_top_logprobs"] = early.prompt_top_logprobs
     if early.n:  # (likewise; n samples are n rows: the batch form answers)
         penalties["n"] = early.n
+    if early.share_prefix:  # (likewise)
+        penalties["share_prefix"] = True
 
     def with_prompt_scores(out: dict, scores) -> dict:
         if scores is not None:
