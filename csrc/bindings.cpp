@@ -157,6 +157,14 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> token_logprobs(torch::Te
 void token_logprobs_step(torch::Tensor logits, torch::Tensor idx, torch::Tensor step, torch::Tensor n_t,
                          torch::Tensor lp_buf, torch::Tensor top_id_buf, torch::Tensor top_lp_buf,
                          torch::Tensor workspace);
+// beam_search.hip
+std::tuple<int64_t, int64_t> beam_step_plan(int64_t V, int64_t W);
+void beam_step(torch::Tensor logits, torch::Tensor ctl, torch::Tensor cum, torch::Tensor inv_norm, torch::Tensor idx,
+               torch::Tensor parent, torch::Tensor hist, torch::Tensor fin_f, torch::Tensor fin_i,
+               torch::Tensor workspace, int64_t W, int64_t steps_cap, c10::optional<torch::Tensor> pos_t,
+               c10::optional<torch::Tensor> len_t, c10::optional<torch::Tensor> step_t);
+std::tuple<torch::Tensor, int64_t> beam_reorder_table(std::vector<torch::Tensor> ks, std::vector<torch::Tensor> vs);
+void beam_reorder(torch::Tensor host_table, torch::Tensor table, torch::Tensor parent, torch::Tensor n_t);
 // stop_check.hip
 void stop_begin(torch::Tensor tail, torch::Tensor n_gen, torch::Tensor done, torch::Tensor finish_at);
 void stop_observe(torch::Tensor seqs, torch::Tensor seq_len, torch::Tensor n_seqs, torch::Tensor tail,
@@ -326,6 +334,20 @@ PYBIND11_MODULE(penroz_kernels, m) {
         pybind11::arg("n_uniq"), pybind11::arg("params"), pybind11::arg("new_tok") = pybind11::none(),
         "logit penalties, one sampling: count new_tok (int64 [B]), then repetition / presence / frequency "
         "(params fp32 [3]) on the listed tokens of logits [B, V], in place");
+  m.def("beam_step_plan", &beam_step_plan, pybind11::arg("V"), pybind11::arg("W"),
+        "beam_step's launch plan: (parts per row, fp32 workspace floats per row); W outside 2..8 or V outside "
+        "[2 W, 256 Ki] is refused (host only)");
+  m.def("beam_step", &beam_step, pybind11::arg("logits"), pybind11::arg("ctl"), pybind11::arg("cum"),
+        pybind11::arg("inv_norm"), pybind11::arg("idx"), pybind11::arg("parent"), pybind11::arg("hist"),
+        pybind11::arg("fin_f"), pybind11::arg("fin_i"), pybind11::arg("workspace"), pybind11::arg("W"),
+        pybind11::arg("steps_cap"), pybind11::arg("pos_t") = c10::nullopt, pybind11::arg("len_t") = c10::nullopt,
+        pybind11::arg("step_t") = c10::nullopt,
+        "one beam-search step on the lm_head's logits (ops/beam_search.py): the 2 W best continuations, the next live "
+        "beams, the finished list and the counter advance, every value read from the device");
+  m.def("beam_reorder_table", &beam_reorder_table, pybind11::arg("ks"), pybind11::arg("vs"),
+        "beam_reorder's layer table for these suffix caches: (host table int64 [L + 1, 6], workgroups)");
+  m.def("beam_reorder", &beam_reorder, pybind11::arg("host_table"), pybind11::arg("table"), pybind11::arg("parent"),
+        pybind11::arg("n_t"), "row r of every suffix cache <- row parent[r], slots [0, n_t[0]), in place, one launch");
   m.def("spec_advance", &spec_advance, pybind11::arg("hist"), pybind11::arg("n_t"), pybind11::arg("cand"),
         pybind11::arg("idx"), pybind11::arg("pos_t"), pybind11::arg("len_t"), pybind11::arg("emitted_t"),
         pybind11::arg("limit_t"), pybind11::arg("steps_t"), pybind11::arg("accepted_t"), pybind11::arg("k"),

@@ -298,6 +298,32 @@ inline LogprobPlan plan_logprobs(int64_t V) {
   return {parts, (int64_t)parts * (2 + 2 * kLogprobMaxN)};
 }
 
+// ---- beam search launch plans (beam_search.hip) ----
+constexpr int kBeamPartN = 4096, kBeamMaxW = 8, kBeamMaxParts = 64;  // logits per part, widest beam, most parts
+struct BeamPlan {
+  int parts;          // part workgroups per row (0: W outside [2, 8] or V outside [2 W, 256 Ki])
+  int64_t ws_floats;  // workspace per row: m [P], s [P] and the parts' 2 W best as 64-bit keys [P, 16]
+};
+
+// The merge workgroup computes a row's lse with one lane per part, so a row has at most 64 parts: V <= 256 Ki.
+// V >= 2 W: the first step's one row then always yields W live beams behind at most one stop candidate.
+inline BeamPlan plan_beam_step(int64_t V, int64_t W) {
+  if (W < 2 || W > kBeamMaxW || V < 2 * W || V > (int64_t)kBeamMaxParts * kBeamPartN) return {0, 0};
+  const int parts = (int)((V + kBeamPartN - 1) / kBeamPartN);
+  return {parts, (int64_t)parts * (2 + 2 * 2 * kBeamMaxW)};
+}
+
+struct ReorderPlan {
+  int pieces;          // 4-KiB pieces (256 threads x 16 B) of one (row, KV head) plane of cap slots
+  int64_t workgroups;  // of one layer: K and V, every KV head, every piece
+};
+
+inline ReorderPlan plan_beam_reorder(int64_t Hkv, int64_t cap, int64_t D) {
+  const int64_t plane = cap * D * 2;
+  const int pieces = (int)((plane + 4095) / 4096);
+  return {pieces, 2 * Hkv * pieces};
+}
+
 // ---- logit bias launch plan (logit_bias.hip) ----
 constexpr int kBiasThreads = 256, kBiasMaxEntries = 1024, kBiasSpan = 2048;  // workgroup, most entries, tokens per mask part
 struct LogitBiasPlan {

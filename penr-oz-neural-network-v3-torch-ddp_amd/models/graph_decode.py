@@ -73,6 +73,12 @@ between steps lives on the device:
   ``csrc/kernels/shared_prefix_attn.hip``, which reads the prefix length and the total length from the device.
   The step is the uniform step otherwise: one ``pos_t``, one ``len_t``, the same programs and sampler.
 
+* beam search (``ops/beam_search.py``, ``csrc/kernels/beam_search.hip``): a ``GraphDecoder`` with ``beam=W`` is the
+  shared-prefix step over ``rows = W`` beams with the sampler replaced by ``beam_step`` — the W·V selection, the walk
+  into live beams and the finished list, and the counter advance — and ``beam_reorder`` appended, which re-parents the
+  rows' suffix caches in place. ``run_beam`` expands the prompt pass's one row eagerly, replays the other steps
+  without a host synchronisation and reads the history once.
+
 The host only tracks the cache length (one per replay) to switch to the reference's
 sliding-window re-prefill when the window is full, and copies each burst of tokens back once
 (stop-token checks per burst). Prefill and re-prefill run eagerly. RoPE models (Gemma) rotate
@@ -94,6 +100,7 @@ from penroz.models import kv_cache as kvc
 from penroz.ops import _ext
 from penroz.ops import activations as act_ops
 from penroz.ops import attention as attn_ops
+from penroz.ops import beam_search as beam_ops
 from penroz.ops import fused as fused_ops
 from penroz.ops import gemm as gemm_ops
 from penroz.ops import logit_bias as bias_ops
@@ -860,7 +867,7 @@ class GraphDecoder:
     def __init__(self, model, rows: int, capacity: int, temperature: float, top_k: int | None,
                  top_p: float | None = None, min_p: float | None = None, weight_quant: str | None = None,
                  ragged: bool = False, speculate: int | None = None, shared_prefix: bool = False,
-                 suffix_capacity: int | None = None):
+                 suffix_capacity: int | None = None, beam: int | None = None):
         # weak: the model caches its decoders (model.__dict__), so a strong reference would make a
         # cycle that only the cyclic GC frees — and a collection that runs while ANOTHER graph is
         # being captured destroys this one's graph mid-capture (a hard abort)
@@ -873,6 +880,12 @@ class GraphDecoder:
         self.shared_prefix = bool(shared_prefix)
         # (with ``ragged``: rows that share a prefix and differ behind it, each at its own length — ``share_prefix``)
         assert not self.shared_prefix or not (speculate or kvc.TURBO_QUANT_ENABLED), speculate
+        # beam search (ops/beam_search.py): the rows are the W beams of one prompt on the shared-prefix step
+        self.beam = int(beam or 0)
+        assert not self.beam or (self.shared_prefix and rows == self.beam and not ragged), (beam, rows, shared_prefix, ragged)
+        self.beam_state: beam_ops.BeamState | None = None  # made by the first ``run_beam`` (it knows V)
+        self._beam_table: beam_ops.ReorderTable | None = None  # ... and by the warm-up step, once the suffix caches exist
+        self._beam_snap: tuple[Tensor, Tensor] | None = None  # what ``_set_state`` loads: (the state, idx) behind the first expansion
         if self.shared_prefix:
             cls = SharedPrefixKVCache
         self.cache = cls(len(self.attn), capacity)
@@ -961,6 +974,8 @@ class GraphDecoder:
     def _step(self):
         if self.speculate:
             return self._spec_step()
+        if self.beam:
+            return self._beam_step()
         for p in self.pos_layers:
             p.position_offset_tensor = self.cache.pos_t
         self.cache.graph_mode = True
@@ -1032,6 +1047,52 @@ class GraphDecoder:
                            self.limit_t, self.steps_t, self.accepted_t, self.speculate, False)
         finally:
             self.cache.graph_mode = False
+
+    def _beam_step(self):
+        """One beam step: the program on the W beams' tokens, ``beam_step`` on its logits — the next tokens into
+        ``idx``, parents, cumulative scores, history, finished list, and the advance of pos_t / len_t / step_t — and
+        ``beam_reorder``, which makes row r of every suffix cache the row of its parent. No sampler."""
+        st = self.beam_state
+        self.cache.graph_mode = True
+        self.cache.begin_step()
+        try:
+            last = self.program.forward(self.idx, self.cache).contiguous()
+            st.step(last, self.idx, (self.cache.pos_t, self.cache.len_t, self.step_t))
+            if self._beam_table is None:  # (the warm-up step, outside any capture: the suffix caches exist now)
+                self._beam_table = beam_ops.ReorderTable(self.cache._ks, self.cache._vs)
+            self._beam_table.apply(st.parent, st.slots)
+        finally:
+            self.cache.graph_mode = False
+
+    @torch.inference_mode()
+    def run_beam(self, first_logits: Tensor, T: int, stop_token: int | None, length_penalty: float) -> list[dict]:
+        """The beams of a call whose prompt the cache holds (the eager prompt pass filled the prefix cache) and whose
+        last prompt position gave ``first_logits`` [1, V]: step 1 runs ``beam_step`` eagerly on that one row, steps
+        2..T replay the captured step with no host synchronisation, and one read at the end brings the history,
+        the scores and the finished list (``ops.beam_search.BeamState.beams``)."""
+        assert self.beam and first_logits.dim() == 2 and first_logits.shape[0] == 1, (self.beam, first_logits.shape)
+        cache_len = self.cache.seq_len()
+        assert 0 < cache_len and cache_len + T <= self.capacity and T <= self.cache.suffix_capacity, \
+            (cache_len, T, self.capacity, self.cache.suffix_capacity)
+        V = first_logits.shape[1]
+        if self.beam_state is None or self.beam_state.V != V:
+            self.beam_state = beam_ops.BeamState(self.beam, self.cache.suffix_capacity, V, self.device)
+            self.graph = None
+        st = self.beam_state
+        st.begin(T, stop_token, length_penalty)
+        st.step(first_logits, self.idx)  # R_in = 1, c = [0]: no cache row to re-parent yet, no counter to advance
+        self._beam_snap = (st.snapshot(), self.idx.clone())
+        self.cache.prefix_len = cache_len
+        self.cache.prefix_t.fill_(cache_len)
+        if T > 1:
+            if self.graph is None:
+                self._capture(None, cache_len)
+            else:
+                self._set_state(None, cache_len)
+            for _ in range(T - 1):
+                self.graph.replay()
+            self.cache._len = [cache_len + T - 1] * self.cache.num_layers
+        return st.beams()
 
     def _spec_load(self, tokens: list[int], limit: int):
         """The state of a call whose sequence so far is ``tokens`` and which wants ``limit`` more: history,
@@ -1144,6 +1205,9 @@ class GraphDecoder:
         speculative decoder's state is its call's (``run_speculative``), whatever the arguments."""
         if self.speculate:
             return self._spec_load(*self._spec_host)
+        if self.beam:  # the call's state behind its first expansion (``run_beam``)
+            self.beam_state.restore(self._beam_snap[0])
+            last_tok = self._beam_snap[1]
         self.seed_t.fill_(self._burst_seed(start))
         self.idx.copy_(last_tok)
         if self.ragged:
@@ -1264,7 +1328,7 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
                 top_p: float | None = None, min_p: float | None = None,
                 weight_quant: str | None = None, ragged: bool = False,
                 speculate: int | None = None, shared_prefix: bool = False,
-                suffix_capacity: int | None = None) -> GraphDecoder | None:
+                suffix_capacity: int | None = None, beam: int | None = None) -> GraphDecoder | None:
     """Cached per model and (rows, block size, sampling settings, weights identity, ragged or not, weight
     format in effect for ``weight_quant`` — as ``ops.weight_quant.resolve`` returned it); None when the
     model does not qualify (CPU, no attention, RoPE head_dim without a decode kernel) or ``PENROZ_GRAPH_DECODE=0``
@@ -1286,6 +1350,8 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
         base += (("speculate", int(speculate)),)
     if shared_prefix:  # (likewise): another cache, and the suffix capacity sizes it
         base += (("shared_prefix", int(suffix_capacity or block_size)),)
+    if beam:  # (likewise): another step — beam_step and beam_reorder in the sampler's place
+        base += (("beam", int(beam)),)
     cache = model.__dict__.setdefault("_graph_decoders", {})
     # the key holds the weight format IN EFFECT: a request for int8 that this step cannot honour
     # (more than 4 rows, no decode program, a K that does not fit) shares the bf16 decoder instead of
@@ -1297,6 +1363,8 @@ def get_decoder(model, rows: int, block_size: int, temperature: float, top_k: in
     if dec is None:
         spec = {"speculate": int(speculate)} if speculate else {}
         shared = {"shared_prefix": True, "suffix_capacity": suffix_capacity} if shared_prefix else {}
+        if beam:
+            shared["beam"] = int(beam)
         dec = GraphDecoder(model, rows, block_size, temperature, top_k, top_p, min_p, weight_quant, ragged=ragged,
                            **spec, **shared)
         if dec.weight_quant != weight_quant:  # asked for int8, runs bf16

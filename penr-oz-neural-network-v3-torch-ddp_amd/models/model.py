@@ -49,6 +49,7 @@ from penroz.ops import logprobs as lp_ops
 from penroz.ops import prompt_logprobs as plp_ops
 from penroz.ops import ragged as ragged_ops
 from penroz.ops import shared_prefix as sp_ops
+from penroz.ops import beam_search as beam_ops
 from penroz.ops import speculative as spec_ops
 from penroz.ops import stopping as stop_ops
 from penroz.ops.decode_options import KEYWORDS, DecodeCall, DecodeOptions, check_options
@@ -122,6 +123,8 @@ class NeuralNetworkModel(nn.Module):
     # an ``n`` call that ran on the shared-prefix step (ops/shared_prefix.py): {"rows", "prefix_len", "splits"}; a
     # ``share_prefix`` call that did: those and "remainders", the rows' own lengths behind the prefix; else None
     last_shared_prefix: dict | None = None
+    # a beam call (ops/beam_search.py): {"path": "device" | "reference", "rows", ...}
+    last_beam_search: dict | None = None
 
     def __init__(self, model_id: str, mapper: Mapper):
         super().__init__()
@@ -561,7 +564,8 @@ class NeuralNetworkModel(nn.Module):
                         banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                         min_tokens: int | None = None, speculate: int | None = None,
                         prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
-                        n: int | None = None, share_prefix: bool | None = None):
+                        n: int | None = None, share_prefix: bool | None = None, num_beams: int | None = None,
+                        length_penalty: float | None = None):
         """``weight_quant``: "int8" decodes batch 1-4 steps on int8 weight copies (models/graph_decode.py),
         "" on the bf16 weights, None takes the process default PENROZ_DECODE_WEIGHTS.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: ops/penalties.py, applied
@@ -591,11 +595,19 @@ class NeuralNetworkModel(nn.Module):
         ``prompt_top_logprobs`` n in 1..20, with ``prompt_logprobs`` only: that dict also holds ``top_n``, the n
         most likely tokens of every prompt position (``score_tokens``' ``top_n``). None or 0: off.
         ``n``: ``generate_batch``'s; here only None or 1 (this method returns one row). ``share_prefix``: likewise,
-        here only None or False."""
+        here only None or False.
+        ``num_beams`` W in 2..8 with ``length_penalty`` (ops/beam_search.py): beam search over the one prompt, with
+        ``stop_token`` and ``weight_quant`` as its only other options, ``temperature`` 1 and
+        ``len(prompt) + max_new_tokens <= block_size``. Returns ``(tokens, info)``: the prompt plus the best
+        hypothesis, and ``info["beams"]``, the W best as ``{"tokens", "cum_logprob", "score", "finished"}`` (generated
+        tokens only), best first. On the GPU the selection and the re-parenting of the KV cache run inside the
+        captured step; elsewhere the reference loop runs on W replicated rows. This method only."""
         options = _keywords(locals())
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
                                             stop_token, **options,
                                             call_shape=call_shape_of(input_context, block_size, single=True))
+        if prepared[2].num_beams:
+            return self._generate_beams(prepared[0], prepared[2], block_size, max_new_tokens)
         if prepared[2].prompt_logprobs:  # every step below sees the options of the call without it
             scored = self.score_tokens([prepared[0][0].tolist()], block_size, prepared[2].prompt_top_logprobs)[0]
             plain = (prepared[0], prepared[1], replace(prepared[2], prompt_logprobs=False, prompt_top_logprobs=0))
@@ -616,12 +628,14 @@ class NeuralNetworkModel(nn.Module):
                                banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                                min_tokens: int | None = None, speculate: int | None = None,
                                prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
-                               n: int | None = None, share_prefix: bool | None = None):
+                               n: int | None = None, share_prefix: bool | None = None,
+                               num_beams: int | None = None, length_penalty: float | None = None):
         """Yields row 0's tokens; with ``logprobs`` n, ``(token, logprob, [[id, logprob], ... n])``. With
         ``stop`` the stream ends with the token that completes a stop sequence. ``logit_bias`` /
         ``banned_token_ids`` / ``allowed_token_ids`` / ``min_tokens``: as in ``generate_tokens``.
         ``speculate`` is refused here: a speculative step emits several tokens at once. So are
-        ``prompt_logprobs`` and ``prompt_top_logprobs``: a prompt's scores come with a finished call."""
+        ``prompt_logprobs`` and ``prompt_top_logprobs``: a prompt's scores come with a finished call; and
+        ``num_beams``: beams are ranked when the call ends."""
         options = _keywords(locals())
         log.info("Streaming token generation started")
         prepared = self._prepare_generation(_rectangular(input_context), max_new_tokens, temperature, top_k,
@@ -803,6 +817,61 @@ class NeuralNetworkModel(nn.Module):
             plain = logprobs is None and (run is None or routed)
             yield context[0].tolist() if plain else (context[0].tolist(), info)
 
+    def _generate_beams(self, context: Tensor, opts: DecodeOptions, block_size: int, max_new_tokens: int):
+        """``(prompt + best hypothesis, {"beams": [...]})`` of a checked beam call (ops/beam_search.py). With the
+        shared-prefix decoder (``GraphDecoder(beam=W)``): the prompt pass fills the prefix cache and its last logits
+        start ``run_beam``. Where an ``n`` call would fall back, the reference loop runs over the module path: W rows
+        in a plain cache that ``index_select`` re-parents before every step; ``last_beam_search`` says which ran."""
+        from penroz.models import graph_decode
+        from penroz.ops import _ext
+        W, T, prompt = opts.num_beams, max_new_tokens, context[0].tolist()
+        if T <= 0:
+            return prompt, {"beams": []}
+        V = self._vocab_size()
+        why = graph_decode.shared_prefix_fallback(self, W, block_size)
+        if why is None and (V is None or V < 2 * W or V > 64 * 4096):
+            why = f"a vocabulary of {V} logits is outside the beam step's plan"
+        cap = -(-T // 64) * 64
+        dec = None if why is not None else graph_decode.get_decoder(self, W, block_size, 1.0, None,
+                                                                      weight_quant=opts.weight_quant, shared_prefix=True,
+                                                                      suffix_capacity=cap, beam=W)
+        if dec is not None:
+            dec.attach()
+            dec.cache.clear()
+            try:
+                logits = self(context[:1], skip_softmax=True)[0][-1]  # the prompt, once (it fits the window)
+                logits = logits[:, -1, :] if logits.ndim == 3 else logits
+                beams = dec.run_beam(logits.contiguous(), T, opts.stop_token, opts.length_penalty)
+            finally:
+                dec.cache.log_metrics()
+                dec.detach()
+            self.last_beam_search = {"path": "device", "rows": W, "prefix_len": len(prompt)}
+        else:
+            beam_ops.log_fallback(why or "no captured decode step here")
+            cache, pos = self._attach_kv_cache(capacity=block_size)
+            try:
+                def next_logits(seqs, parents):
+                    if parents is None or cache is None:  # the prompt pass — or a model without attention: full passes
+                        x = torch.tensor([prompt + q for q in seqs], dtype=torch.long, device=context.device)
+                    else:
+                        sel = torch.tensor(parents, dtype=torch.long, device=context.device)
+                        for name in ("_k", "_v", "_sk", "_sv"):  # row r of the cache <- the row of its parent
+                            store = getattr(cache, name, None)
+                            if store is not None:
+                                store[:] = [None if c is None else c.index_select(0, sel) for c in store]
+                        for p in pos:
+                            p.position_offset = cache.seq_len()
+                        x = torch.tensor([[q[-1]] for q in seqs], dtype=torch.long, device=context.device)
+                    out = self(x, skip_softmax=True)[0][-1]
+                    return out[:, -1, :] if out.ndim == 3 else out
+                beams = beam_ops.reference_generate(next_logits, W, T, opts.stop_token, opts.length_penalty)
+            finally:
+                if cache is not None:
+                    cache.log_metrics()
+                self._detach_kv_cache(pos)
+            self.last_beam_search = {"path": "reference", "rows": W, "why": why}
+        return prompt + beams[0]["tokens"], {"beams": beams}
+
     def _generate_speculative(self, context: Tensor, softmax_layer, opts: DecodeOptions, block_size, max_new_tokens):
         """The one row's prompt plus its tokens, from what ``_prepare_generation`` returned, by prompt-lookup
         speculative decoding (ops/speculative.py): the prompt is prefilled eagerly with the speculative
@@ -902,7 +971,8 @@ class NeuralNetworkModel(nn.Module):
                        banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                        min_tokens: int | None = None, speculate: int | None = None,
                        prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
-                       n: int | None = None, share_prefix: bool | None = None):
+                       n: int | None = None, share_prefix: bool | None = None, num_beams: int | None = None,
+                       length_penalty: float | None = None):
         """All rows' contexts (the reference returns row 0 only — bug 5). With ``logprobs`` n:
         ``(contexts, [info per row])``, each ``info`` (``generate_tokens``) as long as that row's
         returned continuation. With ``stop`` (ops/stopping.py) every row finishes on its own: the
@@ -931,10 +1001,14 @@ class NeuralNetworkModel(nn.Module):
         returns what it returns without the option; on the GPU the common prefix is prefilled and cached once, the
         rows' remainders are prefilled against it and the decode steps read it once for all rows
         (``last_shared_prefix`` then also holds "remainders"); elsewhere, and without a common prefix, the plain call
-        runs. Not with ``n`` or ``speculate``; ``max(len_b) + max_new_tokens <= block_size``. None or False: off."""
+        runs. Not with ``n`` or ``speculate``; ``max(len_b) + max_new_tokens <= block_size``. None or False: off.
+        ``num_beams`` / ``length_penalty``: ``generate_tokens``' (a beam call takes one prompt); refused here."""
         options = _keywords(locals())
         self.last_shared_prefix = None
         samples = None
+        if num_beams is not None or length_penalty is not None:  # refused, with every other check, before anything runs
+            check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
+                          call_shape={**call_shape_of(input_context, block_size), "batch": True})
         if share_prefix is not None and share_prefix is not False:  # checked against the call's shape before anything runs
             check_options(self._vocab_size(), max_new_tokens, temperature, top_k, stop_token, **options,
                           call_shape=call_shape_of(input_context, block_size))

@@ -5,7 +5,7 @@ The public generate methods take their options as keywords; everything behind th
 loops of models/model.py, the captured step of models/graph_decode.py, ``/generate``'s early 400 —
 takes the checked object. The checks themselves live with their features (ops/sampling.py,
 ops/weight_quant.py, ops/penalties.py, ops/logprobs.py, ops/stopping.py, ops/logit_bias.py,
-ops/speculative.py, ops/prompt_logprobs.py, ops/shared_prefix.py); this
+ops/speculative.py, ops/prompt_logprobs.py, ops/shared_prefix.py, ops/beam_search.py); this
 module is the one place that calls them, in one order.
 """
 from __future__ import annotations
@@ -15,6 +15,7 @@ from dataclasses import dataclass, field
 
 from torch import Tensor
 
+from penroz.ops import beam_search as beam_ops
 from penroz.ops import logit_bias as bias_ops
 from penroz.ops import logprobs as lp_ops
 from penroz.ops import penalties as pen_ops
@@ -49,6 +50,8 @@ class DecodeOptions:
     prompt_top_logprobs: int = 0  # ... and reports this many most likely tokens per prompt position (0: none)
     n: int | None = None  # ``check_n``'s k in 2..64: that many samples of the one prompt (ops/shared_prefix.py); None: off
     share_prefix: bool = False  # ``check_share_prefix``': the rows' common prefix is prefilled and cached once (ops/shared_prefix.py)
+    num_beams: int | None = None  # ``check_beams``' W in 2..8: beam search over the one prompt (ops/beam_search.py); None: off
+    length_penalty: float = 1.0  # ... whose hypotheses are scored c * t ** -length_penalty
     asked: str = field(default="", compare=False, repr=False)  # the options as given, in the words of the log line
 
     def describe(self) -> str:
@@ -67,7 +70,8 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
                   banned_token_ids: list | None = None, allowed_token_ids: list | None = None,
                   min_tokens: int | None = None, speculate: int | None = None,
                   prompt_logprobs: bool | None = None, prompt_top_logprobs: int | None = None,
-                  n: int | None = None, share_prefix: bool | None = None, call_shape: dict | None = None) -> DecodeOptions:
+                  n: int | None = None, share_prefix: bool | None = None, num_beams: int | None = None,
+                  length_penalty: float | None = None, call_shape: dict | None = None) -> DecodeOptions:
     """Every check of a generate call, once each, in this order; ValueError for the first that fails.
     ``call_shape`` is no option of the call: what the caller knows of its shape (``rows``, ``prompt_len``,
     ``block_size``, ``stream``), which ``speculate`` and ``n`` are checked against (ops/speculative.py,
@@ -96,6 +100,7 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
                                      ("min_tokens", bool(min_tokens))) if on]
     call_shape = dict(call_shape or {})
     single = bool(call_shape.pop("single", False))
+    batch = bool(call_shape.pop("batch", False))  # the caller is a batch method, which a beam call is refused for
     k = spec_ops.check_speculate(speculate, temperature=temperature, active=active, max_new_tokens=max_new_tokens,
                                  **call_shape)
     shared = sp_ops.check_share_prefix(share_prefix, n=n, max_new_tokens=max_new_tokens, speculate=k, single=single,
@@ -103,6 +108,9 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
     samples = sp_ops.check_n(n, max_new_tokens=max_new_tokens, speculate=k, single=single, **call_shape)
     scored = plp_ops.check_prompt_logprobs(prompt_logprobs, speculate=k, stream=bool(call_shape.get("stream")))
     scored_n = plp_ops.check_prompt_top_logprobs(prompt_top_logprobs, prompt_logprobs=scored)
+    beams = beam_ops.check_beams(num_beams, length_penalty, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                                 active=active, speculate=k, n=samples, share_prefix=shared, prompt_logprobs=scored,
+                                 max_new_tokens=max_new_tokens, batch=batch, **call_shape)
     asked = "" if top_k is None else f" top {top_k}"
     asked += "" if top_p is None else f" top_p {top_p}"
     asked += "" if min_p is None else f" min_p {min_p}"
@@ -119,8 +127,9 @@ def check_options(V: int | None, max_new_tokens: int, temperature: float, top_k:
     asked += "" if not scored_n else f" top {scored_n}"
     asked += "" if samples is None else f" n {samples}"
     asked += "" if not shared else " share_prefix"
+    asked += "" if beams is None else f" num_beams {beams[0]} length_penalty {beams[1]}"
     return DecodeOptions(temperature, top_k, top_p, min_p, quant, penalties, lp_n, seqs, stop_token, bias,
-                         min_tokens or 0, k, scored, scored_n, samples, shared, asked)
+                         min_tokens or 0, k, scored, scored_n, samples, shared, *(beams or (None, 1.0)), asked)
 
 
 # the option keywords of the public generate methods: ``check_options``' own, by name

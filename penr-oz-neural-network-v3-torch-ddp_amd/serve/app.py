@@ -208,6 +208,15 @@ class GenerateRequest(ModelRequest):
                                       description="With batch: the 2 to 64 prompts begin with the same tokens; the "
                                                   "common prefix is prefilled and cached once, the answer is the one "
                                                   "without the option; not with n, stream or speculate; null or false: off")
+    num_beams: StrictInt | None = Field(None, examples=[None],
+                                        description="Beam search with this many (2 to 8) beams over the one prompt: "
+                                                    "\"tokens\" is the best hypothesis and \"beams\" lists them, best "
+                                                    "first; temperature 1, stop_token and weight_quant as the only other "
+                                                    "options, prompt + max_new_tokens <= block_size; not with stream or "
+                                                    "batch; null: off")
+    length_penalty: float | None = Field(None, examples=[None],
+                                         description="With num_beams: a hypothesis of t tokens is scored by its "
+                                                     "log-probability times t ** -length_penalty; null: 1.0")
     stream: bool = Field(False, examples=[False], description="Stream tokens as text/plain lines")
     batch: bool = Field(False, examples=[False],
                         description="Return every row: {\"sequences\": [[...], ...]}, each row's prompt plus its "
@@ -517,7 +526,8 @@ def model_generate(body: GenerateRequest = Body(...)):
     # (and everything a speculative call does not take: its shape is the request's own)
     early = check_options(NOT_LOADED, body.max_new_tokens, body.temperature, body.top_k, body.stop_token,
                           **{name: getattr(body, name) for name in KEYWORDS},
-                          call_shape=call_shape_of(body.input, body.block_size, stream=body.stream))
+                          call_shape={**call_shape_of(body.input, body.block_size, stream=body.stream),
+                                      **({"batch": True} if body.batch else {})})
     stop = early.stop
     model = load_for_serving(body.model_id)
     penalties = dict(repetition_penalty=body.repetition_penalty, presence_penalty=body.presence_penalty,
@@ -539,6 +549,8 @@ def model_generate(body: GenerateRequest = Body(...)):
         penalties["n"] = early.n
     if early.share_prefix:  # (likewise)
         penalties["share_prefix"] = True
+    if early.num_beams:  # (likewise; never with stream or batch: the early check refused those)
+        penalties.update(num_beams=early.num_beams, length_penalty=early.length_penalty)
 
     def with_prompt_scores(out: dict, scores) -> dict:
         if scores is not None:
@@ -590,6 +602,8 @@ def model_generate(body: GenerateRequest = Body(...)):
         speculation = model.last_speculation
     if early.speculate:
         return {"tokens": tokens, "speculation": speculation}
+    if early.num_beams:
+        return {"tokens": tokens[0], "beams": tokens[1]["beams"]}
     tokens, scores = split_prompt_scores(tokens, rows=False)
     if body.logprobs is None and stop is None:
         return with_prompt_scores({"tokens": tokens}, scores)
