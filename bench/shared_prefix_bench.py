@@ -4,7 +4,10 @@ every arm is warmed up, a round times `--iters` launches between two synchronise
 min-max spread of `--rounds` rounds are reported. Then generate_batch(n = R) against the replicated call:
 ms per decode step (from two call lengths) and the time to the first token, the arms alternating as well.
 
-    python bench/shared_prefix_bench.py [--rounds 7] [--iters 200] [--no-e2e] [--out FILE]
+    python bench/shared_prefix_bench.py [--rounds 7] [--iters 200] [--no-e2e] [--int8] [--out FILE]
+
+--int8: the same arms over the int8 KV cache (csrc/kernels/shared_prefix_attn_q8.hip against decode_attention's fused
+int8 append on the replicated int8 cache; end to end with the TurboQuant cache switched on for the process).
 """
 import argparse
 import json
@@ -39,7 +42,13 @@ def stats(xs):
     return {"median": round(statistics.median(xs), 2), "min": round(min(xs), 2), "max": round(max(xs), 2)}
 
 
-def attention_rows(rounds, iters, emit):
+def _q8(shape):
+    """A random int8 cache of this shape and its per-token scales."""
+    return (torch.randint(-127, 128, shape, device=DEV, dtype=torch.int8),
+            (0.5 + torch.rand(shape[:3], device=DEV)) / 127)
+
+
+def attention_rows(rounds, iters, emit, int8=False):
     for name, (H, Hkv, D), prefixes in SHAPES:
         for P in prefixes:
             for R in ROWS:
@@ -58,6 +67,14 @@ def attention_rows(rounds, iters, emit):
                     arms = {"shared": lambda: A.shared_prefix_attention(q, k, v, kp, vp, ks, vs, pt, lt),
                             "replicated": lambda: A.decode_attention(q.unsqueeze(1), kc, vc, P + suffix, seq_len_dev=lt,
                                                                      k_new=k.unsqueeze(1), v_new=v.unsqueeze(1))}
+                    if int8:  # the same arms over int8 caches of the same shapes
+                        (kp8, kps), (vp8, vps) = _q8(kp.shape), _q8(vp.shape)
+                        (ks8, kss), (vs8, vss) = _q8(ks.shape), _q8(vs.shape)
+                        kc8, vc8 = (torch.cat([p_.expand(R, -1, -1, -1), s_], dim=2).contiguous() for p_, s_ in ((kp8, ks8), (vp8, vs8)))
+                        kcs, vcs = (torch.cat([p_.expand(R, -1, -1), s_], dim=2).contiguous() for p_, s_ in ((kps, kss), (vps, vss)))
+                        arms = {"shared": lambda: A.shared_prefix_attention_q8(q, k, v, (kp8, vp8, kps, vps), (ks8, vs8, kss, vss), pt, lt),
+                                "replicated": lambda: A.decode_attention(q.unsqueeze(1), kc8, vc8, P + suffix, kcs, vcs, seq_len_dev=lt,
+                                                                         k_new=k.unsqueeze(1), v_new=v.unsqueeze(1))}
                     outs = {n_: f() for n_, f in arms.items()}
                     diff = (outs["shared"].float() - outs["replicated"].view(R, -1).float()).abs().max().item()
                     for f in arms.values():
@@ -66,12 +83,13 @@ def attention_rows(rounds, iters, emit):
                     for _ in range(rounds):
                         for n_, f in arms.items():
                             us[n_].append(timed(f, iters))
-                    emit({"shape": name, "H": H, "Hkv": Hkv, "D": D, "R": R, "prefix": P, "suffix": suffix,
+                    emit({"cache": "int8" if int8 else "bf16", "shape": name, "H": H, "Hkv": Hkv, "D": D, "R": R, "prefix": P, "suffix": suffix,
                           "splits": kernels().shared_prefix_plan(R, H, Hkv, D, P)[3], "max_abs_diff": round(diff, 5),
                           **{n_ + "_us": stats(x) for n_, x in us.items()}})
 
 
 def e2e_rows(rounds, emit):
+    from penroz.models import kv_cache as kvc
     from penroz.models.mapper import Mapper
     from penroz.models.model import NeuralNetworkModel
     for name, layers, block, plen in (("gpt2", B_.gpt2_layers(), 1024, 896), ("gemma3-1b", B_.gemma3_1b_layers(), 2048, 1024)):
@@ -91,7 +109,7 @@ def e2e_rows(rounds, emit):
             for _ in range(rounds):
                 for a_, f in arms.items():
                     ms[a_].append(timed(f, 1) / 1e3)
-            row = {"e2e": name, "prompt": plen, "R": R}
+            row = {"e2e": name, "cache": "int8" if kvc.TURBO_QUANT_ENABLED else "bf16", "prompt": plen, "R": R}
             for k_ in ("shared", "replicated"):
                 med = {new: statistics.median(ms[(k_, new)]) for new in (1, 2, 66)}
                 row[k_ + "_ttft_ms"] = stats(ms[(k_, 1)])
@@ -106,6 +124,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=200)  # a window of 2-8 ms at 10-40 µs a launch
     ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--int8", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
@@ -118,7 +137,10 @@ def main():
             out.write(line + "\n")
             out.flush()
 
-    attention_rows(a.rounds, a.iters, emit)
+    if a.int8:
+        from penroz.models import kv_cache as kvc
+        kvc.TURBO_QUANT_ENABLED = True
+    attention_rows(a.rounds, a.iters, emit, a.int8)
     if not a.no_e2e:
         e2e_rows(a.rounds, emit)
 

@@ -102,6 +102,20 @@ torch::Tensor shared_prefix_prefill_attn(torch::Tensor q, torch::Tensor k_new, t
                                          double scale, int64_t splits);
 std::tuple<bool, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t> shared_prefix_prefill_plan(
     int64_t R, int64_t Tq, int64_t H, int64_t Hkv, int64_t D, int64_t capP, int64_t capS, int64_t splits);
+// shared_prefix_attn_q8.hip
+torch::Tensor shared_prefix_attn_q8(torch::Tensor q, torch::Tensor k_new, torch::Tensor v_new, torch::Tensor kp,
+                                    torch::Tensor vp, torch::Tensor kps, torch::Tensor vps, torch::Tensor ks, torch::Tensor vs,
+                                    torch::Tensor kss, torch::Tensor vss, torch::Tensor prefix_t, torch::Tensor len_t,
+                                    double scale, int64_t splits);
+std::tuple<bool, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t> shared_prefix_q8_plan(int64_t R, int64_t H, int64_t Hkv,
+                                                                                            int64_t D, int64_t capP,
+                                                                                            int64_t splits);
+torch::Tensor shared_prefix_prefill_attn_q8(torch::Tensor q, torch::Tensor k_new, torch::Tensor v_new, torch::Tensor kp,
+                                            torch::Tensor vp, torch::Tensor kps, torch::Tensor vps, torch::Tensor ks,
+                                            torch::Tensor vs, torch::Tensor kss, torch::Tensor vss, torch::Tensor prefix_t,
+                                            double scale, int64_t splits);
+std::tuple<bool, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t> shared_prefix_prefill_q8_plan(
+    int64_t R, int64_t Tq, int64_t H, int64_t Hkv, int64_t D, int64_t capP, int64_t capS, int64_t splits);
 // lmhead_lse.hip
 std::vector<torch::Tensor> lmhead_lse_raw(torch::Tensor h, torch::Tensor w, c10::optional<torch::Tensor> bias,
                                           torch::Tensor targets, int64_t splits, int64_t top_n);
@@ -163,7 +177,9 @@ void beam_step(torch::Tensor logits, torch::Tensor ctl, torch::Tensor cum, torch
                torch::Tensor parent, torch::Tensor hist, torch::Tensor fin_f, torch::Tensor fin_i,
                torch::Tensor workspace, int64_t W, int64_t steps_cap, c10::optional<torch::Tensor> pos_t,
                c10::optional<torch::Tensor> len_t, c10::optional<torch::Tensor> step_t);
-std::tuple<torch::Tensor, int64_t> beam_reorder_table(std::vector<torch::Tensor> ks, std::vector<torch::Tensor> vs);
+std::tuple<torch::Tensor, int64_t> beam_reorder_table(std::vector<torch::Tensor> ks, std::vector<torch::Tensor> vs,
+                                                      c10::optional<std::vector<torch::Tensor>> k_scales,
+                                                      c10::optional<std::vector<torch::Tensor>> v_scales);
 void beam_reorder(torch::Tensor host_table, torch::Tensor table, torch::Tensor parent, torch::Tensor n_t);
 // stop_check.hip
 void stop_begin(torch::Tensor tail, torch::Tensor n_gen, torch::Tensor done, torch::Tensor finish_at);
@@ -345,7 +361,9 @@ PYBIND11_MODULE(penroz_kernels, m) {
         "one beam-search step on the lm_head's logits (ops/beam_search.py): the 2 W best continuations, the next live "
         "beams, the finished list and the counter advance, every value read from the device");
   m.def("beam_reorder_table", &beam_reorder_table, pybind11::arg("ks"), pybind11::arg("vs"),
-        "beam_reorder's layer table for these suffix caches: (host table int64 [L + 1, 6], workgroups)");
+        pybind11::arg("k_scales") = pybind11::none(), pybind11::arg("v_scales") = pybind11::none(),
+        "beam_reorder's layer table for these suffix caches: (host table int64 [L + 1, 6], workgroups); with the fp32 "
+        "scale planes of int8 caches: two entries per layer, [2 L + 1, 6]");
   m.def("beam_reorder", &beam_reorder, pybind11::arg("host_table"), pybind11::arg("table"), pybind11::arg("parent"),
         pybind11::arg("n_t"), "row r of every suffix cache <- row parent[r], slots [0, n_t[0]), in place, one launch");
   m.def("spec_advance", &spec_advance, pybind11::arg("hist"), pybind11::arg("n_t"), pybind11::arg("cand"),
@@ -399,6 +417,24 @@ PYBIND11_MODULE(penroz_kernels, m) {
         pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("capP"), pybind11::arg("capS"), pybind11::arg("splits") = 0,
         "shared_prefix_prefill_attn's plan: (admitted, tile rows, prefix query tiles per KV head, suffix query tiles per "
         "(row, KV head), key ranges S, workgroups of launch 1, LDS bytes, fp32 workspace floats) (host only)");
+  m.def("shared_prefix_attn_q8", &shared_prefix_attn_q8, pybind11::arg("q"), pybind11::arg("k_new"), pybind11::arg("v_new"),
+        pybind11::arg("kp"), pybind11::arg("vp"), pybind11::arg("kps"), pybind11::arg("vps"), pybind11::arg("ks"),
+        pybind11::arg("vs"), pybind11::arg("kss"), pybind11::arg("vss"), pybind11::arg("prefix_t"), pybind11::arg("len_t"),
+        pybind11::arg("scale"), pybind11::arg("splits") = 0,
+        "shared_prefix_attn over int8 caches with per-token fp32 scales (kps / vps [1, Hkv, capP], kss / vss [R, Hkv, "
+        "capS]); the step's K / V rows are quantised into their suffix slot by the kernel -> [R, H·D]");
+  m.def("shared_prefix_q8_plan", &shared_prefix_q8_plan, pybind11::arg("R"), pybind11::arg("H"), pybind11::arg("Hkv"),
+        pybind11::arg("D"), pybind11::arg("capP"), pybind11::arg("splits") = 0,
+        "shared_prefix_attn_q8's plan, laid out as shared_prefix_plan's (host only)");
+  m.def("shared_prefix_prefill_attn_q8", &shared_prefix_prefill_attn_q8, pybind11::arg("q"), pybind11::arg("k_new"),
+        pybind11::arg("v_new"), pybind11::arg("kp"), pybind11::arg("vp"), pybind11::arg("kps"), pybind11::arg("vps"),
+        pybind11::arg("ks"), pybind11::arg("vs"), pybind11::arg("kss"), pybind11::arg("vss"), pybind11::arg("prefix_t"),
+        pybind11::arg("scale"), pybind11::arg("splits") = 0,
+        "shared_prefix_prefill_attn over int8 caches with per-token fp32 scales; the new K / V are quantised into suffix "
+        "slots 0..Tq-1 and attended as stored -> [R, Tq, H·D]");
+  m.def("shared_prefix_prefill_q8_plan", &shared_prefix_prefill_q8_plan, pybind11::arg("R"), pybind11::arg("Tq"),
+        pybind11::arg("H"), pybind11::arg("Hkv"), pybind11::arg("D"), pybind11::arg("capP"), pybind11::arg("capS"),
+        pybind11::arg("splits") = 0, "shared_prefix_prefill_attn_q8's plan, laid out as shared_prefix_prefill_plan's (host only)");
   m.def("lmhead_lse",
         [](torch::Tensor h, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor targets, int64_t splits,
            int64_t top_n) -> pybind11::tuple {

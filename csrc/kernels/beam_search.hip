@@ -332,12 +332,65 @@ __global__ void __launch_bounds__(kBeamThreads) beam_reorder_kernel(const int64_
     if (par[r] != r) *reinterpret_cast<float4_t*>(base + r * row_bytes) = val[r];
 }
 
+// The int8 form, for TurboQuant suffix caches: the same design over planes described in bytes. table: int64
+// [E + 1, 6], per entry (first base, second base, Hkv, bytes per slot, capacity in slots, first workgroup): a layer
+// is two entries, its int8 K / V caches [W, Hkv, cap, D] (slot bytes D, a multiple of 16: moved in 16-B units) and
+// its fp32 K / V scale planes [W, Hkv, cap] (slot bytes 4: moved in 4-B units, since n scales end on no 16-B
+// boundary and nothing at or behind slot n may be written). A workgroup owns 256 units of one plane for all W rows.
+template <int W, class U>
+__device__ __forceinline__ void reorder_units(char* base, int64_t row_bytes, const int (&par)[W]) {
+  U val[W];  // (a native type: the array stays in registers)
+#pragma unroll
+  for (int r = 0; r < W; ++r) val[r] = *reinterpret_cast<const U*>(base + par[r] * row_bytes);
+#pragma unroll
+  for (int r = 0; r < W; ++r)
+    if (par[r] != r) *reinterpret_cast<U*>(base + r * row_bytes) = val[r];
+}
+
+template <int W>
+__global__ void __launch_bounds__(kBeamThreads) beam_reorder_bytes_kernel(const int64_t* __restrict__ table, int E,
+                                                                          const int* __restrict__ parent,
+                                                                          const int* __restrict__ n_dev) {
+  const int t = threadIdx.x;
+  int par[W];
+  bool identity = true, valid = true;
+#pragma unroll
+  for (int r = 0; r < W; ++r) {
+    par[r] = parent[r];
+    identity = identity && par[r] == r;
+    valid = valid && par[r] >= 0 && par[r] < W;
+  }
+  PZ_DEVICE_CHECK(valid);
+  if (identity || !valid) return;  // (uniform)
+  int l = 0;
+  while (l + 1 < E && (int64_t)blockIdx.x >= table[6 * (l + 1) + 5]) ++l;
+  const int64_t* e = table + 6 * l;
+  const int Hkv = (int)e[2], sb = (int)e[3], cap = (int)e[4];
+  const int unit = sb % 16 == 0 ? 16 : 4;  // (uniform)
+  const int64_t plane = (int64_t)cap * sb;  // bytes of one (row, head)
+  const int pieces = (int)((plane + kBeamThreads * unit - 1) / (kBeamThreads * unit));
+  int rel = (int)((int64_t)blockIdx.x - e[5]);
+  const int piece = rel % pieces;
+  rel /= pieces;
+  const int head = rel % Hkv, which = rel / Hkv;  // which: the entry's first or second base
+  if (which > 1) return;
+  const int n = min(max(*n_dev, 0), cap);
+  const int64_t used = (int64_t)n * sb;  // bytes of a plane in use: a multiple of the unit
+  const int64_t off = ((int64_t)piece * kBeamThreads + t) * unit;
+  if (off >= used) return;  // behind the last slot: the whole workgroup when its piece is, else this thread
+  char* base = reinterpret_cast<char*>(e[which]) + (int64_t)head * plane + off;
+  const int64_t row_bytes = (int64_t)Hkv * plane;
+  if (unit == 16) reorder_units<W, float4_t>(base, row_bytes, par);
+  else reorder_units<W, float>(base, row_bytes, par);
+}
+
 template <int W>
 static void launch_reorder(int64_t w, unsigned grid, hipStream_t stream, const int64_t* table, int L, const int* par,
-                           const int* n) {
+                           const int* n, bool bytes = false) {
   if constexpr (W <= kBeamMaxW) {
-    if (w == W) hipLaunchKernelGGL(beam_reorder_kernel<W>, dim3(grid), dim3(kBeamThreads), 0, stream, table, L, par, n);
-    else launch_reorder<W + 1>(w, grid, stream, table, L, par, n);
+    if (w != W) launch_reorder<W + 1>(w, grid, stream, table, L, par, n, bytes);
+    else if (bytes) hipLaunchKernelGGL(beam_reorder_bytes_kernel<W>, dim3(grid), dim3(kBeamThreads), 0, stream, table, L, par, n);
+    else hipLaunchKernelGGL(beam_reorder_kernel<W>, dim3(grid), dim3(kBeamThreads), 0, stream, table, L, par, n);
   }
 }
 
@@ -413,33 +466,55 @@ void beam_step(torch::Tensor logits, torch::Tensor ctl, torch::Tensor cum, torch
 // The device table of beam_reorder for these suffix caches (each [W, Hkv, cap, D] bf16, contiguous, 16-B
 // aligned; K and V of a layer alike): (table int64 [L + 1, 6] on the HOST, workgroups). beam_reorder takes the
 // host table (it reads W, the grid and L from its last row) and a device copy of it.
-std::tuple<torch::Tensor, int64_t> beam_reorder_table(std::vector<torch::Tensor> ks, std::vector<torch::Tensor> vs) {
+// With k_scales / v_scales (per layer fp32 [W, Hkv, cap], contiguous) the caches are int8 (D % 16 == 0) and the
+// table is the byte form's: two entries per layer, [2 L + 1, 6], its last row flagged.
+std::tuple<torch::Tensor, int64_t> beam_reorder_table(std::vector<torch::Tensor> ks, std::vector<torch::Tensor> vs,
+                                                      c10::optional<std::vector<torch::Tensor>> k_scales,
+                                                      c10::optional<std::vector<torch::Tensor>> v_scales) {
   const char* who = "beam_reorder_table";
   TORCH_CHECK(!ks.empty() && ks.size() == vs.size(), who, ": one K and one V cache per layer");
-  const int64_t L = (int64_t)ks.size(), W = ks[0].size(0);
-  auto host = torch::zeros({L + 1, 6}, torch::dtype(torch::kInt64));
+  const bool q8 = k_scales.has_value() || v_scales.has_value();
+  TORCH_CHECK(!q8 || (k_scales.has_value() && v_scales.has_value() && k_scales->size() == ks.size() &&
+                      v_scales->size() == ks.size()),
+              who, ": one K and one V scale plane per layer, or none");
+  const int64_t L = (int64_t)ks.size(), W = ks[0].size(0), E = q8 ? 2 * L : L;
+  const auto kind = q8 ? torch::kInt8 : torch::kBFloat16;
+  auto host = torch::zeros({E + 1, 6}, torch::dtype(torch::kInt64));
   int64_t* h = host.data_ptr<int64_t>();
   int64_t wgs = 0;
   for (int64_t l = 0; l < L; ++l) {
     const torch::Tensor &k = ks[l], &v = vs[l];
-    TORCH_CHECK(k.is_cuda() && k.scalar_type() == torch::kBFloat16 && k.dim() == 4 && k.is_contiguous() &&
-                    la_aligned(k, 16) && k.size(0) == W && k.size(3) % 8 == 0 && v.is_cuda() && v.device() == k.device() &&
-                    v.scalar_type() == torch::kBFloat16 && v.is_contiguous() && la_aligned(v, 16) && v.sizes() == k.sizes() &&
+    TORCH_CHECK(k.is_cuda() && k.scalar_type() == kind && k.dim() == 4 && k.is_contiguous() &&
+                    la_aligned(k, 16) && k.size(0) == W && k.size(3) % (q8 ? 16 : 8) == 0 && v.is_cuda() && v.device() == k.device() &&
+                    v.scalar_type() == kind && v.is_contiguous() && la_aligned(v, 16) && v.sizes() == k.sizes() &&
                     k.device() == ks[0].device(),
-                who, ": layer ", l, ": bf16 contiguous 16-B aligned [W, Hkv, cap, D % 8 == 0] K and V on one device");
-    const ReorderPlan p = plan_beam_reorder(k.size(1), k.size(2), k.size(3));
-    h[6 * l] = reinterpret_cast<int64_t>(k.data_ptr());
-    h[6 * l + 1] = reinterpret_cast<int64_t>(v.data_ptr());
-    h[6 * l + 2] = k.size(1);
-    h[6 * l + 3] = k.size(3);
-    h[6 * l + 4] = k.size(2);
-    h[6 * l + 5] = wgs;
-    wgs += p.workgroups;
+                who, ": layer ", l, ": ", q8 ? "int8" : "bf16", " contiguous 16-B aligned [W, Hkv, cap, D % ", q8 ? 16 : 8,
+                " == 0] K and V on one device");
+    int64_t* e = h + 6 * (q8 ? 2 * l : l);
+    e[0] = reinterpret_cast<int64_t>(k.data_ptr());
+    e[1] = reinterpret_cast<int64_t>(v.data_ptr());
+    e[2] = k.size(1);
+    e[3] = k.size(3);
+    e[4] = k.size(2);
+    e[5] = wgs;
+    wgs += (q8 ? plan_beam_reorder_bytes(k.size(1), k.size(2), k.size(3)) : plan_beam_reorder(k.size(1), k.size(2), k.size(3))).workgroups;
+    if (q8) {
+      const torch::Tensor &sk = (*k_scales)[l], &sv = (*v_scales)[l];
+      la_one_device(who, k, {sk, sv});
+      e[6] = reinterpret_cast<int64_t>(la_f32_shape(who, "K scales", sk, {W, k.size(1), k.size(2)}));
+      e[7] = reinterpret_cast<int64_t>(la_f32_shape(who, "V scales", sv, {W, k.size(1), k.size(2)}));
+      e[8] = k.size(1);
+      e[9] = 4;
+      e[10] = k.size(2);
+      e[11] = wgs;
+      wgs += plan_beam_reorder_bytes(k.size(1), k.size(2), 4).workgroups;
+    }
   }
   TORCH_CHECK(W >= 2 && W <= kBeamMaxW && wgs >= 1 && wgs < (int64_t)1 << 31, who, ": 2 <= W <= ", kBeamMaxW);
-  h[6 * L] = W;
-  h[6 * L + 1] = wgs;
-  h[6 * L + 2] = L;
+  h[6 * E] = W;
+  h[6 * E + 1] = wgs;
+  h[6 * E + 2] = E;
+  h[6 * E + 3] = q8 ? 1 : 0;
   return {host, wgs};
 }
 
@@ -459,5 +534,5 @@ void beam_reorder(torch::Tensor host_table, torch::Tensor table, torch::Tensor p
   la_one_device(who, table, {parent, n_t});
   const int* par = beam_i32(who, "parent", parent, W);
   const int* n = beam_i32(who, "n_t", n_t, 1);
-  launch_reorder<2>(W, (unsigned)workgroups, at::hip::getCurrentHIPStream(), table.data_ptr<int64_t>(), (int)L, par, n);
+  launch_reorder<2>(W, (unsigned)workgroups, at::hip::getCurrentHIPStream(), table.data_ptr<int64_t>(), (int)L, par, n, h[3] != 0);
 }

@@ -524,6 +524,44 @@ inline SharedPrefixPrefillPlan plan_shared_prefix_prefill(int64_t R, int64_t Tq,
   return {true, tile_rows, (int)tiles, (int)suffix_tiles, (int)s, (int)copy_wgs, grid, lds, (s + 1) * R * Tq * H * (D + 2)};
 }
 
+// ---- the int8 forms (shared_prefix_attn_q8.hip): TurboQuant caches, int8 [·, Hkv, cap, D] with one fp32 scale
+// per (row, KV head, token) ----
+// Admission, tiles, key ranges and workspace are the bf16 forms': a deployment that switches the int8 cache on
+// keeps every shape it had. What differs is LDS — the K / V tiles are widened to the same bf16 image, and two
+// stages of the tile's K and V scales sit behind it; the decode form's suffix workgroups stage 16 KiB of int8 V
+// per chunk — and the prefill form's copy workgroups, which quantise 16-value chunks (1024 of K and of V each).
+constexpr int sp_q8_suffix_keys(int D) { return 16384 / D; }  // keys per suffix chunk: 256 / 128 / 64
+constexpr int sp_q8_prefix_lds(int D, int tile_rows) {
+  return 4 * prefill_keys(D) * D * 2 + (D >= 256 ? tile_rows * D * 2 : 0) + 4 * prefill_keys(D) * 4;
+}
+constexpr int sp_q8_suffix_lds(int D) { return 16384 + 8 * D * 4 + 8 * sp_q8_suffix_keys(D) * 4 + 80 * 4; }
+
+inline SharedPrefixPlan plan_shared_prefix_q8(int64_t R, int64_t H, int64_t Hkv, int64_t D, int64_t capP, int splits_forced = 0) {
+  SharedPrefixPlan p = plan_shared_prefix(R, H, Hkv, D, capP, splits_forced);
+  if (p.ok) p.lds_bytes = std::max(sp_q8_prefix_lds((int)D, p.tile_rows), sp_q8_suffix_lds((int)D));
+  return p;
+}
+
+inline SharedPrefixPrefillPlan plan_shared_prefix_prefill_q8(int64_t R, int64_t Tq, int64_t H, int64_t Hkv, int64_t D,
+                                                             int64_t capP, int64_t capS, int splits_forced = 0) {
+  SharedPrefixPrefillPlan p = plan_shared_prefix_prefill(R, Tq, H, Hkv, D, capP, capS, splits_forced);
+  if (!p.ok) return p;
+  const int64_t copy_wgs = (R * Tq * Hkv * (D / 16) + 1023) / 1024;
+  p.grid += copy_wgs - p.copy_wgs;  // (fewer than the bf16 form's: the admitted grid only shrinks)
+  p.copy_wgs = (int)copy_wgs;
+  p.lds_bytes = sp_q8_prefix_lds((int)D, p.tile_rows);
+  return p;
+}
+
+// beam_reorder over int8 suffix caches: a layer is two table entries, the int8 K / V planes (slot bytes D, 16-B
+// units) and the fp32 K / V scale planes (slot bytes 4, 4-B units: a scale plane's length is no multiple of 16).
+// A workgroup owns a piece of 256 units of one (K or V, KV head) plane for all W rows.
+inline ReorderPlan plan_beam_reorder_bytes(int64_t Hkv, int64_t cap, int64_t slot_bytes) {
+  const int64_t unit = slot_bytes % 16 == 0 ? 16 : 4, plane = cap * slot_bytes;
+  const int pieces = (int)((plane + 256 * unit - 1) / (256 * unit));
+  return {pieces, 2 * Hkv * pieces};
+}
+
 // ---- lm_head scoring launch plan (lmhead_lse.hip) ----
 constexpr int kLmheadColTile = 128, kLmheadKStep = 32;  // vocabulary columns per tile, reduction depth per stage
 constexpr int kLmheadMaxC = 16384, kLmheadMaxSplits = 1024;

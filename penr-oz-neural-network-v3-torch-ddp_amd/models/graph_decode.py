@@ -247,11 +247,11 @@ class StaticTurboKVCache(_GraphMode, kvc.TurboQuantKVCache):
                                          seq_len_dev=self.len_t)
 
 
-class SharedPrefixKVCache(_GraphMode, kvc.KVCache):
-    """The cache of an ``n`` call (ops/shared_prefix.py). Prefix side: this batch-1 bf16 ``KVCache``, which the
-    eager prompt pass fills through the module path (``prefill_attn.hip``, as for any prompt). Suffix side: per
-    layer ``[rows, Hkv, suffix_capacity, D]``, allocated by the warm-up step, and ``prefix_t``, the prompt's length
-    on the device. ``seq_len`` counts prompt and generated tokens together; ``len_t`` is that plus one."""
+class _SharedSide:
+    """Mixin: what the bf16 and the int8 shared-prefix cache have in common — the suffix side's bookkeeping and the
+    bracket around a ``share_prefix`` call's remainder pass. ``_suffix(l)`` is the class's own."""
+
+    _remainder = False
 
     def init_shared(self, rows: int, suffix_capacity: int, device):
         self.rows, self.suffix_capacity = rows, suffix_capacity
@@ -264,13 +264,6 @@ class SharedPrefixKVCache(_GraphMode, kvc.KVCache):
         super().clear()
         self.prefix_len = None
         self._remainder = False
-
-    def _suffix(self, l: int):
-        if self._ks[l] is None:  # (an ``n`` call: the warm-up step, outside any capture)
-            kp = self._k[l]
-            shape = (self.rows, kp.shape[1], self.suffix_capacity, kp.shape[3])
-            self._ks[l], self._vs[l] = kp.new_zeros(shape), kp.new_zeros(shape)
-        return self._ks[l], self._vs[l]
 
     def begin_remainder(self):
         """A ``share_prefix`` call, behind its prefix pass: what the cache holds is the prefix. The suffix caches
@@ -287,7 +280,19 @@ class SharedPrefixKVCache(_GraphMode, kvc.KVCache):
         self._remainder = False
         self._len = [total] * self.num_layers
 
-    _remainder = False
+
+class SharedPrefixKVCache(_SharedSide, _GraphMode, kvc.KVCache):
+    """The cache of an ``n`` call (ops/shared_prefix.py). Prefix side: this batch-1 bf16 ``KVCache``, which the
+    eager prompt pass fills through the module path (``prefill_attn.hip``, as for any prompt). Suffix side: per
+    layer ``[rows, Hkv, suffix_capacity, D]``, allocated by the warm-up step, and ``prefix_t``, the prompt's length
+    on the device. ``seq_len`` counts prompt and generated tokens together; ``len_t`` is that plus one."""
+
+    def _suffix(self, l: int):
+        if self._ks[l] is None:  # (an ``n`` call: the warm-up step, outside any capture)
+            kp = self._k[l]
+            shape = (self.rows, kp.shape[1], self.suffix_capacity, kp.shape[3])
+            self._ks[l], self._vs[l] = kp.new_zeros(shape), kp.new_zeros(shape)
+        return self._ks[l], self._vs[l]
 
     def attend(self, l: int, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
         if self._remainder and not self.graph_mode:
@@ -300,6 +305,41 @@ class SharedPrefixKVCache(_GraphMode, kvc.KVCache):
         self._suffix(l)
         return attn_ops.shared_prefix_attention(q.squeeze(1), k.squeeze(1), v.squeeze(1), kp, vp, self._ks[l],
                                                 self._vs[l], self.prefix_t, self.len_t)
+
+
+class SharedPrefixTurboKVCache(_SharedSide, _GraphMode, kvc.TurboQuantKVCache):
+    """``SharedPrefixKVCache`` under ``TURBO_QUANT_KV_CACHE=1``. Prefix side: this batch-1 int8 ``TurboQuantKVCache``
+    with its per-token scales, which the eager prompt pass fills (``kv_quantize``, ``prefill_attn.hip``'s int8
+    path). Suffix side: per layer int8 ``[rows, Hkv, suffix_capacity, D]`` K and V and their fp32 scales
+    ``[rows, Hkv, suffix_capacity]``; csrc/kernels/shared_prefix_attn_q8.hip quantises the rows' new K/V into them
+    with the cache's own quantiser, so a slot holds what ``StaticTurboKVCache`` would hold."""
+
+    def init_shared(self, rows: int, suffix_capacity: int, device):
+        super().init_shared(rows, suffix_capacity, device)
+        self._sks: list[Tensor | None] = [None] * self.num_layers
+        self._svs: list[Tensor | None] = [None] * self.num_layers
+
+    def _suffix(self, l: int):
+        if self._ks[l] is None:  # (an ``n`` call: the warm-up step, outside any capture)
+            kp = self._k[l]
+            shape = (self.rows, kp.shape[1], self.suffix_capacity, kp.shape[3])
+            self._ks[l], self._vs[l] = kp.new_zeros(shape), kp.new_zeros(shape)
+            self._sks[l], self._svs[l] = (torch.ones(shape[:3], dtype=torch.float32, device=kp.device) for _ in "kv")
+        return self._ks[l], self._vs[l], self._sks[l], self._svs[l]
+
+    def _prefix(self, l: int):
+        return self._k[l], self._v[l], self._sk[l], self._sv[l]
+
+    def attend(self, l: int, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
+        if self._remainder and not self.graph_mode:
+            self._dtype[l] = k.dtype
+            return attn_ops.shared_prefix_prefill_attention_q8(q, k, v, self._prefix(l), self._suffix(l), self.prefix_t)
+        return super().attend(l, q, k, v)
+
+    def _attend_graph(self, l: int, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
+        self._dtype[l] = k.dtype
+        return attn_ops.shared_prefix_attention_q8(q.squeeze(1), k.squeeze(1), v.squeeze(1), self._prefix(l),
+                                                   self._suffix(l), self.prefix_t, self.len_t)
 
 
 def _attention_shapes(model) -> list[tuple[int, int, int]]:
@@ -326,10 +366,9 @@ def shared_prefix_fallback(model, rows: int, capacity: int) -> str | None:
         return "no captured decode step here: CPU, PENROZ_GRAPH_DECODE=0 or a model it does not take"
     if not ragged_program_ok(model):
         return "the model has no decode program (bf16 GPT-2-pattern or Gemma-family, PENROZ_DECODE_PROGRAM=1)"
-    if kvc.TURBO_QUANT_ENABLED:
-        return "the int8 KV cache: the kernel takes bf16 caches"
     shapes = _attention_shapes(model)
-    if not all(attn_ops.shared_prefix_applies(rows, H, Hkv, D, capacity) for H, Hkv, D in shapes):
+    applies = attn_ops.shared_prefix_q8_applies if kvc.TURBO_QUANT_ENABLED else attn_ops.shared_prefix_applies
+    if not all(applies(rows, H, Hkv, D, capacity) for H, Hkv, D in shapes):
         return f"the kernel's plan refuses {rows} rows at heads {sorted(set(shapes))}"
     return None
 
@@ -340,8 +379,9 @@ def share_prefix_fallback(model, rows: int, capacity: int, remainder: int, suffi
     why = shared_prefix_fallback(model, rows, capacity)
     if why is None:
         shapes = _attention_shapes(model)
-        if not all(attn_ops.shared_prefix_prefill_applies(rows, remainder, H, Hkv, D, capacity, suffix_capacity)
-                   for H, Hkv, D in shapes):
+        applies = (attn_ops.shared_prefix_prefill_q8_applies if kvc.TURBO_QUANT_ENABLED
+                   else attn_ops.shared_prefix_prefill_applies)
+        if not all(applies(rows, remainder, H, Hkv, D, capacity, suffix_capacity) for H, Hkv, D in shapes):
             why = f"the kernel's plan refuses {rows} rows of {remainder} positions at heads {sorted(set(shapes))}"
     return why
 
@@ -879,7 +919,7 @@ class GraphDecoder:
         # n samples of one prompt (ops/shared_prefix.py): ``rows`` rows over one prefix cache and their own suffixes
         self.shared_prefix = bool(shared_prefix)
         # (with ``ragged``: rows that share a prefix and differ behind it, each at its own length — ``share_prefix``)
-        assert not self.shared_prefix or not (speculate or kvc.TURBO_QUANT_ENABLED), speculate
+        assert not self.shared_prefix or not speculate, speculate
         # beam search (ops/beam_search.py): the rows are the W beams of one prompt on the shared-prefix step
         self.beam = int(beam or 0)
         assert not self.beam or (self.shared_prefix and rows == self.beam and not ragged), (beam, rows, shared_prefix, ragged)
@@ -887,7 +927,7 @@ class GraphDecoder:
         self._beam_table: beam_ops.ReorderTable | None = None  # ... and by the warm-up step, once the suffix caches exist
         self._beam_snap: tuple[Tensor, Tensor] | None = None  # what ``_set_state`` loads: (the state, idx) behind the first expansion
         if self.shared_prefix:
-            cls = SharedPrefixKVCache
+            cls = SharedPrefixTurboKVCache if kvc.TURBO_QUANT_ENABLED else SharedPrefixKVCache
         self.cache = cls(len(self.attn), capacity)
         # ragged (ops/ragged.py): every row at its own position and cache length — pos_t / len_t are [rows]
         self.ragged = bool(ragged)
@@ -1059,7 +1099,8 @@ class GraphDecoder:
             last = self.program.forward(self.idx, self.cache).contiguous()
             st.step(last, self.idx, (self.cache.pos_t, self.cache.len_t, self.step_t))
             if self._beam_table is None:  # (the warm-up step, outside any capture: the suffix caches exist now)
-                self._beam_table = beam_ops.ReorderTable(self.cache._ks, self.cache._vs)
+                scales = ((self.cache._sks, self.cache._svs) if isinstance(self.cache, SharedPrefixTurboKVCache) else ())
+                self._beam_table = beam_ops.ReorderTable(self.cache._ks, self.cache._vs, *scales)
             self._beam_table.apply(st.parent, st.slots)
         finally:
             self.cache.graph_mode = False

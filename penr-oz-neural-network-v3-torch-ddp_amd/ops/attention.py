@@ -362,3 +362,56 @@ def shared_prefix_prefill_attention(q: Tensor, k_new: Tensor, v_new: Tensor, kp:
     ks[:, :, :Tq] = k_new.transpose(1, 2)
     vs[:, :, :Tq] = v_new.transpose(1, 2)
     return reference_prefill_attention(q, kp, vp, ks, vs, int(prefix_t.item())).to(q.dtype).reshape(R, Tq, H * D)
+
+
+# --------------------------------------------------------------------------- ... over the int8 KV cache
+def shared_prefix_q8_applies(R: int, H: int, Hkv: int, D: int, capP: int) -> bool:
+    """The int8 shared-prefix kernel's own launch plan admits the shape (``shared_prefix_q8_plan``, host_plan.h)."""
+    return bool(kernels().shared_prefix_q8_plan(R, H, Hkv, D, capP)[0])
+
+
+def shared_prefix_attention_q8(q: Tensor, k_new: Tensor, v_new: Tensor, prefix: tuple, suffix: tuple,
+                               prefix_t: Tensor, len_t: Tensor, splits: int = 0) -> Tensor:
+    """``shared_prefix_attention`` over TurboQuant caches: ``prefix`` = (kp, vp int8 ``[1, Hkv, capP, D]``, their fp32
+    scales ``[1, Hkv, capP]``), ``suffix`` = (ks, vs int8 ``[R, Hkv, capS, D]``, their scales ``[R, Hkv, capS]``). The
+    step's ``k_new`` / ``v_new`` are quantised (``ops/sampling.py: reference_quantize``) into suffix slot
+    ``len_t - 1 - prefix_t`` and attended as stored. GPU: csrc/kernels/shared_prefix_attn_q8.hip (a shape its plan
+    refuses is an error — ask ``shared_prefix_q8_applies`` first). CPU: the reference with host-side lengths."""
+    R, H, D = q.shape
+    kp, vp, kps, vps = prefix
+    ks, vs, kss, vss = suffix
+    if use_kernels(q):
+        return kernels().shared_prefix_attn_q8(q, k_new, v_new, kp, vp, kps, vps, ks, vs, kss, vss, prefix_t, len_t,
+                                               1.0 / math.sqrt(D), int(splits))
+    from penroz.ops.shared_prefix import reference_attention_q8
+    P, outs = int(prefix_t.item()), []
+    for b, n in enumerate(len_t.tolist() * (R if len_t.numel() == 1 else 1)):  # one length for all rows, or each row's
+        one = slice(b, b + 1)
+        out, (qk, sk, qv, sv) = reference_attention_q8(q[one], k_new[one], v_new[one], prefix,
+                                                       tuple(t[one] for t in suffix), P, n - P)
+        ks[one, :, n - 1 - P], kss[one, :, n - 1 - P], vs[one, :, n - 1 - P], vss[one, :, n - 1 - P] = qk, sk, qv, sv
+        outs.append(out)
+    return torch.cat(outs).to(q.dtype).reshape(R, H * D)
+
+
+def shared_prefix_prefill_q8_applies(R: int, Tq: int, H: int, Hkv: int, D: int, capP: int, capS: int) -> bool:
+    """The int8 prefill form's own launch plan admits the shape (``shared_prefix_prefill_q8_plan``, host_plan.h)."""
+    return bool(kernels().shared_prefix_prefill_q8_plan(R, Tq, H, Hkv, D, capP, capS)[0])
+
+
+def shared_prefix_prefill_attention_q8(q: Tensor, k_new: Tensor, v_new: Tensor, prefix: tuple, suffix: tuple,
+                                       prefix_t: Tensor, splits: int = 0) -> Tensor:
+    """``shared_prefix_prefill_attention`` over TurboQuant caches (``prefix`` / ``suffix`` as in
+    ``shared_prefix_attention_q8``): the rows' new K/V are quantised into suffix slots ``0..Tq-1`` and every query
+    attends them as stored — what write-then-attend on the plain int8 cache computes. GPU: the prefill form of
+    csrc/kernels/shared_prefix_attn_q8.hip. CPU: the reference."""
+    R, Tq, H, D = q.shape
+    kp, vp, kps, vps = prefix
+    ks, vs, kss, vss = suffix
+    if use_kernels(q):
+        return kernels().shared_prefix_prefill_attn_q8(q, k_new, v_new, kp, vp, kps, vps, ks, vs, kss, vss, prefix_t,
+                                                       1.0 / math.sqrt(D), int(splits))
+    from penroz.ops.shared_prefix import reference_prefill_attention_q8
+    out, (qk, sk, qv, sv) = reference_prefill_attention_q8(q, k_new, v_new, prefix, suffix, int(prefix_t.item()))
+    ks[:, :, :Tq], kss[:, :, :Tq], vs[:, :, :Tq], vss[:, :, :Tq] = qk, sk, qv, sv
+    return out.to(q.dtype).reshape(R, Tq, H * D)

@@ -207,11 +207,15 @@ class BeamState:
 
 
 class ReorderTable:
-    """``beam_reorder``'s layer table for these suffix caches (per layer [W, Hkv, cap, D] bf16); keeps them alive."""
+    """``beam_reorder``'s layer table for these suffix caches (per layer [W, Hkv, cap, D] bf16); keeps them alive.
+    With ``k_scales`` / ``v_scales`` (per layer fp32 [W, Hkv, cap]) the caches are the int8 KV cache's, and their
+    scale planes are re-parented in the same launch."""
 
-    def __init__(self, ks: list[Tensor], vs: list[Tensor]):
-        self.caches = (list(ks), list(vs))
-        self.host, self.workgroups = _ext.kernels().beam_reorder_table(list(ks), list(vs))
+    def __init__(self, ks: list[Tensor], vs: list[Tensor], k_scales: list[Tensor] | None = None,
+                 v_scales: list[Tensor] | None = None):
+        self.caches = (list(ks), list(vs), list(k_scales or ()), list(v_scales or ()))
+        scales = (list(k_scales), list(v_scales)) if k_scales is not None else ()
+        self.host, self.workgroups = _ext.kernels().beam_reorder_table(list(ks), list(vs), *scales)
         self.dev = self.host.to(ks[0].device)
 
     def apply(self, parent: Tensor, n_t: Tensor) -> None:

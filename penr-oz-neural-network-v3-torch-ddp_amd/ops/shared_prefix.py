@@ -12,10 +12,12 @@ into a batch-1 *prefix* cache, gives every row a *suffix* cache for the tokens i
 ``csrc/kernels/shared_prefix_attn.hip``: every prefix key is read once per KV head and scored against all rows
 on the matrix cores. Row r's keys are the prefix keys followed by row r's own suffix keys
 (``reference_attention``). A row's bits depend on its own query, the prefix, its suffix, the prefix length and
-the number of prefix key ranges S, which sets the order of the sums. At equal S they do not depend on the
+the number of prefix key ranges S, which sets the order of the sums. Under the int8 KV cache
+(``TURBO_QUANT_KV_CACHE=1``) the same step runs over int8 caches with per-token scales
+(``csrc/kernels/shared_prefix_attn_q8.hip``, ``reference_attention_q8``). At equal S they do not depend on the
 row count or on the other rows; the launch plan chooses S from the row count (with the heads and the
 capacity), so calls with different ``n`` may run different S and round a row differently. Elsewhere — the CPU, ``PENROZ_GRAPH_DECODE=0``, a model without a decode program, fp32
-parameters, the int8 KV cache, a shape the kernel's plan refuses, ``PENROZ_SHARED_PREFIX=0`` — the replicated
+parameters, a shape the kernel's plan refuses, ``PENROZ_SHARED_PREFIX=0`` — the replicated
 call runs, which is the same thing by definition; logged once per process.
 
 An ``n`` call takes one prompt row, does not stream, does not speculate, is ``generate_batch``'s (the other
@@ -182,3 +184,47 @@ def reference_attention(q: Tensor, kp: Tensor, vp: Tensor, ks: Tensor, vs: Tenso
     v = v.repeat_interleave(H // Hkv, dim=1)
     s = torch.einsum("rhd,rhkd->rhk", q.double(), k) * scale
     return torch.einsum("rhk,rhkd->rhd", torch.softmax(s, dim=-1), v)
+
+
+def _dequantize(x: Tensor, scale: Tensor) -> Tensor:
+    return x.double() * scale.double()[..., None]
+
+
+def _quantize_rows(x: Tensor) -> tuple[Tensor, Tensor]:
+    """x [R, T, Hkv, D] -> (int8 [R, Hkv, T, D], fp32 scales [R, Hkv, T]): the cache's quantiser, on fp32 as the
+    kernels compute it."""
+    from penroz.ops.sampling import reference_quantize
+    xq, s = reference_quantize(x.float().transpose(1, 2))
+    return xq, s.squeeze(-1)
+
+
+def reference_attention_q8(q: Tensor, k_new: Tensor, v_new: Tensor, prefix: tuple, suffix: tuple, prefix_len: int,
+                           suffix_len: int, scale: float | None = None):
+    """The int8 decode form's definition, in fp64: ``prefix`` = (kp, vp int8 [1, Hkv, capP, D], scales [1, Hkv,
+    capP]), ``suffix`` = (ks, vs int8 [R, Hkv, capS, D], scales [R, Hkv, capS]) holding slots ``0..suffix_len - 2``;
+    the step's bf16 ``k_new`` / ``v_new [R, Hkv, D]`` are quantised (``reference_quantize``) into slot
+    ``suffix_len - 1``, everything is dequantised and ``reference_attention`` runs. The suffix caches are not
+    written. -> ([R, H, D] fp64, (int8 K row, K scale, int8 V row, V scale) of the new slot)."""
+    kp, vp, kps, vps = prefix
+    ks, vs, kss, vss = suffix
+    qk, sk = _quantize_rows(k_new.unsqueeze(1))
+    qv, sv = _quantize_rows(v_new.unsqueeze(1))
+    ksd, vsd = _dequantize(ks, kss), _dequantize(vs, vss)
+    ksd[:, :, suffix_len - 1] = _dequantize(qk, sk)[:, :, 0]
+    vsd[:, :, suffix_len - 1] = _dequantize(qv, sv)[:, :, 0]
+    out = reference_attention(q, _dequantize(kp, kps), _dequantize(vp, vps), ksd, vsd, prefix_len, suffix_len, scale)
+    return out, (qk[:, :, 0], sk[:, :, 0], qv[:, :, 0], sv[:, :, 0])
+
+
+def reference_prefill_attention_q8(q: Tensor, k_new: Tensor, v_new: Tensor, prefix: tuple, suffix: tuple,
+                                   prefix_len: int, scale: float | None = None):
+    """The int8 prefill form's definition, in fp64: the rows' bf16 ``k_new`` / ``v_new [R, Tq, Hkv, D]`` are quantised
+    into suffix slots ``0..Tq-1``, dequantised, and ``reference_prefill_attention`` runs over the dequantised prefix
+    and those slots (``suffix`` gives the shapes; it is not written).
+    -> ([R, Tq, H, D] fp64, (int8 K [R, Hkv, Tq, D], K scales [R, Hkv, Tq], int8 V, V scales))."""
+    kp, vp, kps, vps = prefix
+    qk, sk = _quantize_rows(k_new)
+    qv, sv = _quantize_rows(v_new)
+    out = reference_prefill_attention(q, _dequantize(kp, kps), _dequantize(vp, vps), _dequantize(qk, sk),
+                                      _dequantize(qv, sv), prefix_len, scale)
+    return out, (qk, sk, qv, sv)

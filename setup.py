@@ -62,10 +62,11 @@ def _newer(src: str, obj: str, deps: list[str]) -> bool:
     return any(os.path.getmtime(d) > t for d in [src] + deps)
 
 
-# per-source flags: prefill_attn.hip, lmhead_lse.hip and shared_prefix_attn.hip are compiled without the
+# per-source flags: prefill_attn.hip, lmhead_lse.hip and the shared_prefix_attn files are compiled without the
 # packed-fp32 VALU forms
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"prefill_attn.hip": _NO_PK_F32, "lmhead_lse.hip": _NO_PK_F32, "shared_prefix_attn.hip": _NO_PK_F32}
+EXTRA_FLAGS = {"prefill_attn.hip": _NO_PK_F32, "lmhead_lse.hip": _NO_PK_F32, "shared_prefix_attn.hip": _NO_PK_F32,
+               "shared_prefix_attn_q8.hip": _NO_PK_F32}
 
 
 def _compile(src: str, obj: str, flags: list[str]):
